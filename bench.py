@@ -7,19 +7,26 @@ and fp32 CTC.  A "step" = one full optimisation step over one batch: 11 conv lay
 gradient, 10 dgrads + 11 wgrads + 11 bias grads, [gradient exchange over RCCL when N > 1], Adam, weight repack.
 Inputs, labels and lengths are resident in HBM when the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own N ranks (it re-executes itself under
 torch.distributed.run on 127.0.0.1); started under torch.distributed.run it is one of those ranks.
 
+A plain run sets up, runs W warm-up steps, times exactly K steps and prints the headline line (`value`, `ms_per_step`,
+...).  --dump-outputs DIR writes what the timed path computed in its last timed step as DIR/<name>.npy (see
+Bench.dump_outputs).  Everything else is measured with --full only: the per-launch / roofline passes (`kernels`,
+`roofline`, `conv_stack_mfma_frac`), the host-buffer note, the `data_parallel` object of N > 1 runs, config 2's bf16 /
+bf16x3 legs and, for the default configuration on one GPU, the `also` legs, the `cpu_baseline` leg and `parity`.
+
 --config 2 / --config 5 run BASELINE.json's other single-GPU-shardable configurations with the same contract (they are
 not the headline line): 2 = forward + greedy decode only on the same batch; 5 = long-form 257-bin power spectrograms, 8
 utterances per GPU, lengths U{2000..8000} frames in length-bucketed batches, full training step, reported with the
-achieved GB/s of its HBM-bound kernels next to the MFMA fraction.  The default invocation (config 3, one GPU) also runs
-short versions of both and attaches them as `also.config2` / `also.config5`, and compares the GPU step with the CPU
-step of the `cpu_baseline` leg at the benchmark's own batch size (`parity`).
+achieved GB/s of its HBM-bound kernels next to the MFMA fraction.  With --full the default invocation (config 3, one GPU)
+also runs short versions of both and attaches them as `also.config2` / `also.config5`, and compares the GPU step with the
+CPU step of the `cpu_baseline` leg at the benchmark's own batch size (`parity`).
 
-Rank 0 prints ONE JSON line (see the contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...); with --full it
+holds `roofline` and `cpu_baseline` objects.
 """
 import argparse
 import json
@@ -39,6 +46,7 @@ MEL, FRAMES, BATCH_PER_GPU, K_CLASSES = 128, 1000, 32, 29
 BF16_DENSE_PEAK_TFLOPS = 2500.0  # /opt/skills/guides/MI355X_MICROARCH.md: ~2.5 PF dense bf16 MFMA
 F32_MFMA_PEAK_TFLOPS = 157.3     # same guide: v_mfma_f32_32x32x2_f32, exact fp32 = the fp32 vector peak
 HBM_PEAK_GBPS = 8000.0           # same guide: HBM3E ~8 TB/s
+DUMP_SEED, DUMP_SAMPLE = 0, 1 << 21  # --dump-outputs: the fixed sample of the weights / gradients (8 MB per array)
 
 
 def layer_flops_per_utt(specs, t_out):
@@ -396,7 +404,8 @@ class Bench:
                 "sequences": len(decoded32), "note": notes[dtype]}
 
     def run(self, steps, warmup):
-        """Times the configuration and assembles its part of the JSON line (every rank runs it; rank 0 keeps it)."""
+        """Times the configuration and assembles its part of the JSON line (every rank runs it; rank 0 keeps it).  What
+        the last timed step returned stays in self.last_out (dump_outputs)."""
         self.args_steps, self.args_warmup = steps, warmup
         if self.config == 5:
             # one untimed pass over every length bucket before the W warm-up steps: a bucket's first step allocates its
@@ -414,11 +423,43 @@ class Bench:
             "frames_per_sec": self.frames_per_step * world * steps / elapsed,
             "step_mfma_frac": self.flops_per_step * world * steps / elapsed / 1e12 / (self.peak * world),
         }
-        if config == 2:
+        self.elapsed, self.last_out = elapsed, out
+        return result
+
+    def other_forward_legs(self, result):
+        """config 2 (--full): the bf16x3 and bf16 forward paths timed beside the fp32 headline path"""
+        if self.config == 2:
             result["bf16x3_path"] = self.other_forward_leg("bf16x3")
             result["bf16_path"] = self.other_forward_leg("bf16")
-        self.elapsed = elapsed
         return result
+
+    def dump_outputs(self, out_dir):
+        """What the timed path computed in its LAST timed step, as float32 .npy files under out_dir (< 64 MB in all).
+        Training configurations (3, 5): `losses` (per utterance, the step's return value), and the same fixed seeded
+        sample (with replacement) of the weights after the step and of the step's weight gradients (Keras layout, all
+        layers' W and b flattened and concatenated in order: get_weights / get_gradients).  Config 2: `probs` (B, T', K),
+        `frame_argmax` (B, T') and `decoded` (B, T') padded with -1 (greedy_decode's return value)."""
+        out_dir = Path(out_dir)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        self.torch.cuda.synchronize()
+        arrays = {}
+        if self.config == 2:
+            decoded, argmax = self.last_out
+            padded = -np.ones(argmax.shape, dtype=np.float32)
+            for i, seq in enumerate(decoded):
+                padded[i, :len(seq)] = seq
+            arrays["probs"] = self.eng.cur.probs.float().cpu().numpy()
+            arrays["frame_argmax"] = argmax.astype(np.float32)
+            arrays["decoded"] = padded
+        else:
+            arrays["losses"] = self.last_out.float().cpu().numpy()
+            for name, tensors in (("weights", self.eng.get_weights()), ("gradients", self.eng.get_gradients())):
+                flat = np.concatenate([a.ravel() for wb in tensors for a in wb]).astype(np.float32)
+                idx = np.random.RandomState(DUMP_SEED).randint(0, flat.size, size=min(DUMP_SAMPLE, flat.size))
+                arrays[name + "_sample"] = flat[idx]
+        for name, a in arrays.items():
+            np.save(str(out_dir / (name + ".npy")), np.ascontiguousarray(a, dtype=np.float32))
+        return sorted(arrays)
 
     def kernel_report(self, result):
         """per-launch durations, groups and the roofline object(s) of this configuration"""
@@ -787,6 +828,12 @@ def main():
     ap.add_argument("--split-last-bucket", action="store_true",
                     help="N > 1: close inner_conv_4..7's gradients as a bucket of their own (Engine.split_last_bucket: the "
                          "fused input-gradient launch and the balanced weight-gradient launch cut in two)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: per-launch / roofline passes, host-buffer note, "
+                         "data-parallel diagnostics, config 2's other paths, and (config 3, one GPU) the also / "
+                         "cpu_baseline / parity legs")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -826,9 +873,14 @@ def main():
 
     bench = Bench(args.config, args, world, rank, device, reducer_factory)
     result = bench.run(args.steps, args.warmup)
-    dp = bench.data_parallel_report() if bench.reducer is not None else None
-    bench.kernel_report(result)
-    h2d = bench.host_buffer_note(result["ms_per_step"]) if (args.config == 3 and rank == 0) else None
+    if args.dump_outputs and rank == 0:
+        bench.dump_outputs(args.dump_outputs)
+    dp = h2d = None
+    if args.full:
+        bench.other_forward_legs(result)
+        dp = bench.data_parallel_report() if bench.reducer is not None else None
+        bench.kernel_report(result)
+        h2d = bench.host_buffer_note(result["ms_per_step"]) if (args.config == 3 and rank == 0) else None
 
     if rank != 0:
         if world > 1:
@@ -852,7 +904,7 @@ def main():
         line["data_parallel"] = dp
     if h2d is not None:
         line["host_buffers"] = h2d
-    headline = world == 1 and args.config == 3
+    headline = world == 1 and args.config == 3 and args.full
     # ---- the other single-GPU configurations, witnessed in the same run (short legs; not the headline)
     if headline and not args.no_also:
         also = {}
@@ -862,6 +914,7 @@ def main():
             t0 = time.perf_counter()
             b = Bench(cfg, args, 1, 0, device)
             r = b.run(steps, warm)
+            b.other_forward_legs(r)
             b.kernel_report(r)
             r.update({"metric": METRICS[cfg], "workload": WORKLOADS[cfg], "steps": steps, "warmup": warm,
                       "leg_seconds": round(time.perf_counter() - t0, 2)})

@@ -34,6 +34,11 @@ def test_reference_signature_decodes_config2_bit_exactly_against_the_cpu_port():
     rng = np.random.RandomState(0)
     x = rng.randn(32, 1000, 128).astype(np.float32)
     ospecs = o.layer_specs(128, 29)
+    # Fixed glorot weights instead of the unseeded draw of the constructor: at random init the softmax is nearly flat,
+    # and about one draw in six has a frame whose two largest CPU probabilities lie within the two float32
+    # implementations' distance (~2e-8), so an exact argmax comparison would fail by chance.  Seed 26: smallest top-2
+    # gap of the CPU probabilities 1.7e-7, nine times the largest GPU-vs-CPU difference measured on it.
+    net.predictive_net.set_weights(Wav2Letter._glorot_uniform(ospecs, 26))
 
     def cpu_probs():
         with torch.no_grad():

@@ -232,8 +232,10 @@ def test_bench_two_ranks_emit_the_data_parallel_diagnostics(shard):
     from pathlib import Path
     root = Path(__file__).resolve().parent.parent
     env = dict(os.environ, SL_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
-    # plain `python bench.py --gpus 2`: the script starts its own ranks (the shape of the driver's command)
-    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--profile-steps", "1"] + \
+    # `python bench.py --gpus 2 --full`: the script starts its own ranks (the shape of the driver's command); the
+    # `data_parallel` object is part of the --full run
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--profile-steps", "1",
+           "--full"] + \
         (["--shard-optimizer"] if shard else [])
     res = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=str(root), timeout=900)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -265,7 +267,7 @@ def test_bench_eight_ranks_control_flow(config):
     root = Path(__file__).resolve().parent.parent
     env = dict(os.environ, SL_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--profile-steps", "1",
-           "--config", str(config)]
+           "--config", str(config), "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd=str(root), timeout=1500)
     assert res.returncode == 0, res.stderr[-2000:]
     line = [l for l in res.stdout.splitlines() if l.startswith("{")][-1]

@@ -41,7 +41,7 @@ run_one() {  # config exchange comm_cus split rccl_name rccl_env
     local cfg=$1 exch=$2 cus=$3 split=$4 rname=$5 renv=$6
     local tag="c${cfg}_${exch}_cus${cus}_split${split}_${rname}"
     local args=(--gpus "$N" --config "$cfg" --steps "$STEPS" --warmup "$WARMUP" --no-cpu-baseline --no-also --profile-steps 1
-                --comm-cus "$cus")
+                --comm-cus "$cus" --full)
     [ "$exch" = shard ] && args+=(--shard-optimizer)
     [ "$split" = 1 ] && args+=(--split-last-bucket)
     local envs=()
@@ -54,7 +54,7 @@ run_one() {  # config exchange comm_cus split rccl_name rccl_env
 : > "$OUT/status.txt"
 for cfg in $CONFIGS; do
     # the single-GPU rate of the same configuration: the denominator of the efficiency column
-    python bench.py --gpus 1 --config "$cfg" --steps "$STEPS" --warmup "$WARMUP" --no-cpu-baseline --no-also --profile-steps 1 \
+    python bench.py --gpus 1 --config "$cfg" --steps "$STEPS" --warmup "$WARMUP" --no-cpu-baseline --no-also --profile-steps 1 --full \
         > "$OUT/c${cfg}_single.json" 2> "$OUT/c${cfg}_single.err"
     for exch in ${EXCHANGES:-allreduce shard}; do
         for cus in ${COMM_CUS:-0 32}; do
