@@ -312,6 +312,27 @@ int sl_ctc_select(int variant);
 int sl_greedy_decode(const float* probs, const int32_t* input_len, int32_t* out, int32_t* out_len,
                      int32_t* frame_argmax, int batch, int t_out, int k, int blank, void* stream);
 
+/* ---- CTC forced alignment (Viterbi over the CTC lattice).  No reference counterpart: the reference's data model consumes
+ *      word timings (speechless/labeled_example.py:32-60 PositionalLabel, :219-234 sections()); this produces them. -------
+ * logq: float[B][t_out][k] (sl_softmax_logq / sl_output_softmax); labels, label_len: as for sl_ctc_loss_grad (label_len
+ * clamped to [0, l_max]); input_len: T_b, clamped to [0, t_out].  blank = k-1.  Limits: 1 < k <= 64, 0 <= l_max <= 511,
+ * SL_ERR_UNSUPPORTED otherwise.  Every operation is an exact max or ONE fp32 add (no multiply, nothing to contract), so a
+ * float32 restatement of the following reproduces score and path bit for bit:
+ *   states s in [0, S), S = 2L+1: even s blank, odd s label position (s-1)/2.
+ *   delta_0(0) = logq_0(blank), delta_0(1) = logq_0(l_0), every other state -inf;
+ *   delta_t(s) = max(delta_{t-1}(s), delta_{t-1}(s-1), delta_{t-1}(s-2)) + logq_t(label(s)) for 0 < t < T_b, where the s-2
+ *   term counts only for an odd s >= 3 whose label differs from l_{(s-1)/2 - 1}.  Ties: strict > in the order stay, s-1,
+ *   s-2 (the earlier candidate wins).  End state: S-2 if delta(S-2) > delta(S-1), else S-1.
+ * Outputs: score[b] = the best path's log-probability (delta of the end state at T_b - 1); path int32[B][t_out]: path[b][t]
+ * = the state the best path occupies at frame t for t < T_b, -1 for t >= T_b.  No feasible path (T_b < L + number of
+ * adjacent equal labels): score -inf, the whole row -1.  L = 0 aligns every frame to blank; T_b = 0 with L = 0: score 0.
+ * workspace: sl_ctc_align_workspace_bytes(batch, t_out, l_max) bytes, 0 when the backpointers (2 bits per state and frame)
+ * fit the work-group's LDS -- otherwise they go to HBM (monotonic in t_out and l_max).  One wave per utterance. */
+size_t sl_ctc_align_workspace_bytes(int batch, int t_out, int l_max);
+int sl_ctc_align(const float* logq, const int32_t* labels, const int32_t* label_len, const int32_t* input_len,
+                 int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* The same fused update for SEVERAL layers in one launch (the small layers' launches are pure latency): layer i's
  * block starts `offset` floats into param / grad / m / v (weights [k][cin_pad][cout_pad] followed by cout_pad biases). */
 #define SL_ADAM_MAX_LAYERS 16

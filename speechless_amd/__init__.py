@@ -11,6 +11,9 @@ def __getattr__(name):
                 "ExpectationsVsPredictionsInBatches", "ExpectationsVsPredictionsInGroupedBatches"):
         from . import net
         return getattr(net, name)
+    if name in ("PositionalLabel", "CtcAlignment"):
+        from . import alignment
+        return getattr(alignment, name)
     if name == "Engine":
         from .engine import Engine
         return Engine

@@ -51,6 +51,7 @@ class _Buffers:
         self._decoded_flat = torch.zeros((batch * self.tt_pad,), dtype=torch.int32, device=dev)
         self._argmax_flat = torch.zeros((batch * self.tt_pad,), dtype=torch.int32, device=dev)
         self.g = [None] * n  # allocated lazily by ensure_backward()
+        self.align_labels = self.align_ws = None  # allocated lazily by ensure_align()
         self.decoded_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
         self.input_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
         self.loss = torch.zeros((batch,), dtype=torch.float32, device=dev)
@@ -382,3 +383,16 @@ class _Buffers:
             self.launch_lists = {}
         if self.labels is None or self.labels.shape[1] < l_max:
             self.labels = torch.zeros((self.batch, l_max), dtype=torch.int32, device=eng.device)
+
+    def ensure_align(self, eng, l_max):
+        """Tensors of Engine.ctc_align, apart from those of the CTC loss (a forward-only engine aligns without gradient
+        buffers): labels of up to l_max graphemes, lengths, the (B, tt_pad) path / (B,) score results and the workspace,
+        allocated on first use and grown with l_max only."""
+        if self.align_labels is None or self.align_labels.shape[1] < l_max:
+            self.align_labels = torch.zeros((self.batch, l_max), dtype=torch.int32, device=eng.device)
+            self.align_label_len = torch.zeros((self.batch,), dtype=torch.int32, device=eng.device)
+            self._align_path_flat = torch.zeros((self.batch * self.tt_pad,), dtype=torch.int32, device=eng.device)
+            self.align_score = torch.zeros((self.batch,), dtype=torch.float32, device=eng.device)
+        need = lib().raw("sl_ctc_align_workspace_bytes")(self.batch, self.tt_pad, l_max)  # covers every length
+        if self.align_ws is None or self.align_ws.numel() < need:
+            self.align_ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=eng.device)

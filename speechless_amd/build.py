@@ -12,7 +12,7 @@ HOST_LIB_PATH = PACKAGE_DIR / "libspeechless_host.so"  # plain C++ helpers of th
 HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csrc_host" / "beam_search.cpp"]
 CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "misc.hip", "spectrogram.hip", "conv_chain_bf16.hip",
-           "conv1x1_bwd_bf16.hip", "split3.hip"]
+           "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
 # f16x3 parity path (csrc/common.h: SL_MFMA16; only the fp32 / plane-output instantiations, about a third of the bf16 build)
 F16_VARIANTS = {"conv_nt_f16": "conv_nt_bf16.hip", "wgrad_tn_f16": "wgrad_tn_bf16.hip"}
@@ -29,7 +29,8 @@ def _newest_source_mtime():
 # These files read LDS fragments through inline asm with hand-counted s_waitcnt (the compiler does not know the
 # registers are still being filled).  A register spill would store such a register before its data has arrived, so a
 # kernel of these files that needs scratch memory is a BUILD ERROR, not a slow kernel.
-NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip"}
+# (ctc_align.hip: its lattice states and backtrace windows live in registers by design; a spill there is a bug, too)
+NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip"}
 
 
 def _scratch_users(remarks):

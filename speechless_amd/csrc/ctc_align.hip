@@ -1,0 +1,291 @@
+// ctc_align.hip -- CTC forced alignment (Viterbi over the CTC lattice + backtrace) for gfx950.
+//
+// No reference counterpart: the reference only CONSUMES word timings (speechless/labeled_example.py:32-60, PositionalLabel,
+// and :219-234, LabeledExampleFromFile.sections()).  This produces them from a net's output distribution and a transcript.
+// Semantics (bit for bit, fp32): include/speechless_hip.h, sl_ctc_align.
+//
+// Kernel ctc_align_kernel<NJ, BP_LDS>: ONE WAVE per utterance, NJ consecutive lattice states per lane in registers (lane l
+// holds states l*NJ .. l*NJ + NJ - 1; NJ = 4 / 8 / 16 for S = 2L+1 <= 256 / 512 / 1024, as ctc_grad_kernel<NJ, ...> picks
+// by l_max).  Per frame: the highest state of the lane below arrives by one DPP wave_shr:1 move (a lane's first state
+// is a blank, which never skips), every state takes max(stay, s-1, s-2) with the tie rule and adds its emission (one
+// exact max chain + ONE rounded add: no FMA can form), and the 2-bit backpointers of the lane's NJ states -- one byte /
+// short / dword -- are stored as one row of 16*NJ bytes per frame in which state s sits at bits 2s.  Emissions come from LDS: the wave stages CH frames of logq rows (k <= 64
+// floats, one coalesced read per frame) while it works on the previous CH frames.
+//   BP_LDS = 1: the T' rows fit the work-group's LDS (config 3: 500 frames x 128 bytes) and the backtrace reads them there.
+//   BP_LDS = 0: rows go to the workspace in HBM; the backtrace copies windows of W frames (the whole rows: contiguous
+//   bytes) into LDS, the next window's loads in flight while the current one is resolved, so that no frame of the T'-long
+//   backtrace waits on a dependent HBM load.
+// The backtrace is run by every lane of the wave on the same (wave-uniform) state: its LDS reads are broadcasts, and lane
+// t - w0 keeps the state of frame t, so the path leaves as one coalesced store per window.
+#include "common.h"
+
+namespace {
+
+constexpr int CH = 16;  // frames of logq per LDS staging chunk
+constexpr int W = 64;   // frames per backtrace window (one per lane)
+constexpr int LDS_MAX = 160 * 1024;
+
+__device__ __forceinline__ float dpp_float_from_lower_lane(float v, float lane0_value) {  // lane l <- lane l-1
+    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0_value), __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+
+template <int NJ>
+struct BpWord;
+template <>
+struct BpWord<4> { typedef uint8_t T; };
+template <>
+struct BpWord<8> { typedef uint16_t T; };
+template <>
+struct BpWord<16> { typedef uint32_t T; };
+
+__host__ __device__ constexpr int row_bytes(int nj) { return 16 * nj; }  // 64 lanes x 2 bits x nj states
+
+// backtrace window w of an utterance's HBM rows (rows w*W .. min(T, w*W + W) - 1: one contiguous range) into registers, and
+// from there into LDS window buffer w & 1
+template <int V, int R>
+__device__ __forceinline__ void load_window(u32x4 (&wreg)[V], const uint8_t* bp_utt, int w, int T, int lane) {
+    const int w0 = w * W;
+    const int n16 = ((T - w0 < W ? T - w0 : W) * R) / 16;
+    const u32x4* src = (const u32x4*)(bp_utt + (long)w0 * R);
+#pragma unroll
+    for (int m = 0; m < V; ++m) {
+        const int i = m * 64 + lane;
+        if (i < n16) wreg[m] = src[i];
+    }
+}
+template <int V, int R>
+__device__ __forceinline__ void store_window(const u32x4 (&wreg)[V], uint8_t* rows, int w, int lane) {
+    u32x4* dst = (u32x4*)(rows + (w & 1) * W * R);
+#pragma unroll
+    for (int m = 0; m < V; ++m) dst[m * 64 + lane] = wreg[m];
+}
+
+// LDS: [logq chunk CH x 64 floats][final scores 64*NJ floats][backpointer rows: T' rows (BP_LDS) or two windows of W rows]
+template <int NJ, bool BP_LDS>
+__global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__ logq, const int32_t* __restrict__ labels,
+                                                        const int32_t* __restrict__ label_len,
+                                                        const int32_t* __restrict__ input_len, int32_t* __restrict__ path,
+                                                        float* __restrict__ score, uint8_t* __restrict__ bp_hbm, int t_out,
+                                                        int k, int l_max) {
+    typedef typename BpWord<NJ>::T Word;
+    constexpr int R = row_bytes(NJ);
+    extern __shared__ float smem[];
+    float* em = smem;
+    float* fin = em + CH * 64;
+    uint8_t* rows = (uint8_t*)(fin + 64 * NJ);
+
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int blank = k - 1;
+    int L = label_len[b];
+    L = L < 0 ? 0 : (L > l_max ? l_max : L);
+    int T = input_len[b];
+    T = T < 0 ? 0 : (T > t_out ? t_out : T);
+    const int S = 2 * L + 1;
+    const int32_t* lab = labels + (long)b * l_max;
+    int32_t* prow = path + (long)b * t_out;
+
+    // feasibility: T >= L + (adjacent equal labels)
+    int reps = 0;
+    for (int i0 = 1; i0 < L; i0 += 64) {
+        const int i = i0 + lane;
+        const bool eq = i < L && lab[i] == lab[i - 1];
+        reps += __popcll(__ballot(eq));
+    }
+    for (int t = T + lane; t < t_out; t += 64) prow[t] = -1;
+    if (T < L + reps || T == 0) {
+        for (int t = lane; t < T; t += 64) prow[t] = -1;
+        if (lane == 0) score[b] = (T == 0 && L == 0) ? 0.f : -INFINITY;
+        return;
+    }
+
+    // per-lane lattice: label columns (as LDS float offsets) of the odd states, skip permissions
+    int col[NJ / 2];
+    bool skip[NJ / 2];
+#pragma unroll
+    for (int q = 0; q < NJ / 2; ++q) {
+        const int s = lane * NJ + 2 * q + 1;
+        const int pos = (s - 1) >> 1;
+        int c = blank;
+        bool sk = false;
+        if (s < S) {
+            c = lab[pos];
+            c = c < 0 ? 0 : (c > blank ? blank : c);
+            sk = pos >= 1 && lab[pos - 1] != lab[pos];
+        }
+        col[q] = c;
+        skip[q] = sk;
+    }
+    // delta of a virtual frame -1: state 0 at 0, the rest at -inf, so that frame 0 yields delta_0(0) = logq_0(blank) and
+    // delta_0(1) = logq_0(l_0) exactly (0 + x == x) and every other state -inf
+    float d[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) d[j] = -INFINITY;
+    if (lane == 0) d[0] = 0.f;
+
+    const float* lq = logq + (long)b * t_out * k;
+    const bool col_on = lane < k;
+    float pre[CH];
+#pragma unroll
+    for (int f = 0; f < CH; ++f) {
+        const int t = f < T ? f : T - 1;
+        pre[f] = col_on ? lq[(long)t * k + lane] : 0.f;
+    }
+    Word* bp_lds = (Word*)rows + lane;
+    Word* bp_g = (Word*)(bp_hbm + (long)b * t_out * R) + lane;
+    for (int t0 = 0; t0 < T; t0 += CH) {
+        __syncthreads();
+#pragma unroll
+        for (int f = 0; f < CH; ++f) em[f * 64 + lane] = pre[f];
+        __syncthreads();
+        if (t0 + CH < T) {
+#pragma unroll
+            for (int f = 0; f < CH; ++f) {
+                const int t = t0 + CH + f < T ? t0 + CH + f : T - 1;
+                pre[f] = col_on ? lq[(long)t * k + lane] : 0.f;
+            }
+        }
+        const int nf = T - t0 < CH ? T - t0 : CH;
+#pragma unroll
+        for (int f = 0; f < CH; ++f) {
+            if (f >= nf) continue;  // (wave-uniform; a break keeps the loop from unrolling)
+            const float* e = em + f * 64;
+            const float eb = e[blank];
+            // state lane*NJ - 1: s-1 of the lane's first state (even: never skips) and s-2 of its second
+            const float lo1 = dpp_float_from_lower_lane(d[NJ - 1], -INFINITY);
+            uint32_t word = 0;
+#pragma unroll
+            for (int j = NJ - 1; j >= 0; --j) {  // descending: d[j-1], d[j-2] still hold frame t-1
+                const float p1 = j >= 1 ? d[j - 1] : lo1;
+                float best = d[j];
+                uint32_t bp = 0;
+                if (p1 > best) {
+                    best = p1;
+                    bp = 1;
+                }
+                if (j & 1) {
+                    const float p2 = j >= 2 ? d[j - 2] : lo1;
+                    if (skip[j >> 1] && p2 > best) {
+                        best = p2;
+                        bp = 2;
+                    }
+                    d[j] = best + e[col[j >> 1]];
+                } else {
+                    d[j] = best + eb;
+                }
+                word |= bp << (2 * j);
+            }
+            const int t = t0 + f;
+            if (BP_LDS)
+                bp_lds[(long)t * (R / sizeof(Word))] = (Word)word;
+            else
+                bp_g[(long)t * (R / sizeof(Word))] = (Word)word;
+        }
+    }
+
+    // end state: the better of S-1 and S-2, S-1 on a tie
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) fin[lane * NJ + j] = d[j];
+    __syncthreads();
+    int s = S - 1;
+    if (S >= 2 && fin[S - 2] > fin[S - 1]) s = S - 2;
+    if (lane == 0) score[b] = fin[s];
+
+    // backtrace, windows [w0, w0 + W) from the last one down
+    const int nwin = (T + W - 1) / W;
+    constexpr int V = W * R / 16 / 64;  // u32x4 per lane of one window
+    constexpr int VR = BP_LDS ? 1 : V;  // (no window registers when the rows stay in LDS)
+    u32x4 wreg[VR];
+    const uint8_t* bp_utt = bp_hbm + (long)b * t_out * R;
+    if (!BP_LDS) {
+        load_window<VR, R>(wreg, bp_utt, nwin - 1, T, lane);
+        store_window<VR, R>(wreg, rows, nwin - 1, lane);
+    }
+    for (int w = nwin - 1; w >= 0; --w) {
+        const int w0 = w * W;
+        const int w1 = T - w0 < W ? T : w0 + W;
+        if (!BP_LDS && w > 0) load_window<VR, R>(wreg, bp_utt, w - 1, T, lane);
+        __syncthreads();
+        const uint8_t* base = BP_LDS ? rows + (long)w0 * R : rows + (w & 1) * W * R;
+        int mine = -1;
+        for (int t = w1 - 1; t >= w0; --t) {
+            if (lane == t - w0) mine = s;
+            if (t > 0) {
+                const uint32_t byte = base[(t - w0) * R + (s >> 2)];
+                s -= (byte >> (2 * (s & 3))) & 3u;
+            }
+        }
+        if (w0 + lane < w1) prow[w0 + lane] = mine;
+        if (!BP_LDS && w > 0) {
+            __syncthreads();
+            store_window<VR, R>(wreg, rows, w - 1, lane);
+        }
+    }
+}
+
+template <int NJ, bool BP_LDS>
+size_t align_lds_bytes(int t_out) {
+    return (size_t)(CH * 64 + 64 * NJ) * sizeof(float) + (size_t)(BP_LDS ? t_out : 2 * W) * row_bytes(NJ);
+}
+
+int states_per_lane(int l_max) { return 2 * l_max + 1 <= 256 ? 4 : (2 * l_max + 1 <= 512 ? 8 : 16); }
+
+bool bp_in_lds(int nj, int t_out) {
+    switch (nj) {
+        case 4: return align_lds_bytes<4, true>(t_out) <= (size_t)LDS_MAX;
+        case 8: return align_lds_bytes<8, true>(t_out) <= (size_t)LDS_MAX;
+        default: return align_lds_bytes<16, true>(t_out) <= (size_t)LDS_MAX;
+    }
+}
+
+template <int NJ, bool BP_LDS>
+int launch_align(const float* logq, const int32_t* labels, const int32_t* label_len, const int32_t* input_len, int32_t* path,
+                 float* score, void* workspace, int batch, int t_out, int k, int l_max, hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)ctc_align_kernel<NJ, BP_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        attr_set = true;
+    }
+    const size_t lds = align_lds_bytes<NJ, BP_LDS>(t_out);
+    hipLaunchKernelGGL((ctc_align_kernel<NJ, BP_LDS>), dim3(batch), dim3(64), lds, s, logq,
+                       labels, label_len, input_len, path, score, (uint8_t*)workspace, t_out, k, l_max);
+    return sl_check_launch("sl_ctc_align");
+}
+
+}  // namespace
+
+extern "C" size_t sl_ctc_align_workspace_bytes(int batch, int t_out, int l_max) {
+    if (batch <= 0 || t_out <= 0 || l_max < 0 || l_max > 511) return 0;
+    const int nj = states_per_lane(l_max);
+    return bp_in_lds(nj, t_out) ? 0 : (size_t)batch * t_out * row_bytes(nj);
+}
+
+extern "C" int sl_ctc_align(const float* logq, const int32_t* labels, const int32_t* label_len, const int32_t* input_len,
+                            int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    SL_CHECK_ARG(batch > 0 && t_out > 0 && l_max >= 0, "sl_ctc_align: need batch, t_out > 0 and l_max >= 0");
+    SL_CHECK_ARG(logq && label_len && input_len && path && score && (labels || l_max == 0), "sl_ctc_align: null pointer");
+    if (k <= 1 || k > 64) {
+        sl_set_error("sl_ctc_align: k = %d outside 1 < k <= 64 (one lane per class)", k);
+        return SL_ERR_UNSUPPORTED;
+    }
+    if (l_max > 511) {
+        sl_set_error("sl_ctc_align: label length %d > 511 unsupported (at most 1023 lattice states)", l_max);
+        return SL_ERR_UNSUPPORTED;
+    }
+    const size_t need = sl_ctc_align_workspace_bytes(batch, t_out, l_max);
+    if (workspace_bytes < need || (need > 0 && workspace == nullptr)) {
+        sl_set_error("sl_ctc_align: workspace too small (%zu < %zu)", workspace_bytes, need);
+        return SL_ERR_WORKSPACE_TOO_SMALL;
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    const int nj = states_per_lane(l_max);
+    const bool lds = need == 0;
+#define SL_ALIGN(NJ_)                                                                                                      \
+    return lds ? launch_align<NJ_, true>(logq, labels, label_len, input_len, path, score, workspace, batch, t_out, k, l_max, s) \
+               : launch_align<NJ_, false>(logq, labels, label_len, input_len, path, score, workspace, batch, t_out, k, l_max, s)
+    if (nj == 4) SL_ALIGN(4);
+    if (nj == 8) SL_ALIGN(8);
+    SL_ALIGN(16);
+#undef SL_ALIGN
+}

@@ -512,6 +512,42 @@ class Wav2Letter:
             [ExpectationVsPrediction(predicted=p, expected=x.label, loss=float(l))
              for p, x, l in zip(predictions, labeled_spectrogram_batch, losses)])
 
+    def alignment_batch(self, labeled_spectrogram_batch):
+        """Extension (no reference counterpart): CTC forced alignment of every example's label, one forward pass on the
+        evaluation engine and one sl_ctc_align launch over the distribution the CTC loss sees.  Inputs and lengths are
+        packed as test_and_predict_batch packs them.  Returns a list of alignment.CtcAlignment (frames = output frames)."""
+        from .alignment import CtcAlignment
+        inputs = self._input_dictionary_for_loss_net(labeled_spectrogram_batch)
+        names = Wav2Letter.InputNames
+        engine = self.eval_engine
+        engine.forward(inputs[names.input_batch])
+        paths, scores = engine.ctc_align(inputs[names.label_batch], inputs[names.label_lengths],
+                                         inputs[names.prediction_lengths])
+        return [CtcAlignment.from_path(x.label, score, path)
+                for x, score, path in zip(labeled_spectrogram_batch, scores, paths)]
+
+    def positional_label_batch(self, labeled_spectrogram_batch, seconds_per_input_step=None):
+        """Word timings in seconds (alignment.PositionalLabel, as labeled_example.py:32-60 holds them) of every example,
+        None where the label cannot be aligned or has no words.  Output frame t covers input steps [r t, r (t + 1)), r =
+        input_to_prediction_length_ratio.  One input step lasts seconds_per_input_step if given, else hop_length /
+        sample_rate of the example (speechless_amd.spectrogram.LabeledExample) -- 1 / sample_rate on a raw-wave net."""
+        seconds = [self._seconds_per_input_step(x, seconds_per_input_step) for x in labeled_spectrogram_batch]
+        ratio = self.input_to_prediction_length_ratio
+        return [a.positional_label(ratio * s) for a, s in zip(self.alignment_batch(labeled_spectrogram_batch), seconds)]
+
+    def _seconds_per_input_step(self, example, seconds_per_input_step):
+        if seconds_per_input_step is not None:
+            return float(seconds_per_input_step)
+        rate = getattr(example, "sample_rate", None)
+        if rate:
+            if self.use_raw_wave_input:
+                return 1.0 / rate
+            hop = getattr(example, "hop_length", None)
+            if hop:
+                return hop / rate
+        raise ValueError("example {} carries no sample_rate / hop_length: pass seconds_per_input_step".format(
+            getattr(example, "id", None)))
+
     def test_and_predict(self, labeled_spectrogram):
         # the reference duplicates the example because TF fails on batches of one (net.py:491-495); kept for parity
         return self.test_and_predict_batch([labeled_spectrogram, labeled_spectrogram]).results[0]
