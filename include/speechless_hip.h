@@ -333,6 +333,43 @@ int sl_ctc_align(const float* logq, const int32_t* labels, const int32_t* label_
                  int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- CTC beam search, optionally scored by an n-gram language model: the device twin of sl_host_ctc_beam_search
+ *      (include/speechless_host.h; speechless/net.py:444-451).  The host decoder is the specification: for the same
+ *      inputs the result is the same search, step for step --
+ *   frame: logf(p + eps), minus max + logf(sum over j = 0..k-1 in that order of expf(x_j - max));
+ *   branches = the beam stable-sorted by total, descending; first loop from the parents' old probabilities with the
+ *   `previous` rule of merge_repeated; child loop over branches in that order with is_candidate / push, a full beam
+ *   evicting the FIRST minimum in slot order, the new entry taking its slot; an equal total never displaces the bottom;
+ *   prefixes are trie nodes with a canonical id per (parent, label), so a prefix that leaves the beam and comes back is
+ *   the same node; at the end expand_state_end + end_expansion_score, then LabelSeq(merge_repeated) of the first best
+ *   leaf in slot order.
+ * probs: float[batch][t_max][k] probabilities (device); lengths: int32[batch] (device), clamped to [0, t_max] (0 = the
+ * empty result).  out: int32[batch][t_max], -1 behind out_len[batch] labels; log_prob: float[batch] or NULL.
+ * lm: NULL = plain search; otherwise device pointers to the tables that sl_host_scorer_export of speechless_host.h
+ * fills, and the scalars it returns.  With lm, blank must be k - 1.
+ * Numerics: logf / expf / log1pf are evaluated in double and rounded to float (glibc's float functions are within an
+ * ulp or so of that), everything else is the host's float arithmetic without contraction: transcripts agree with the
+ * host decoder, log_prob to about 1e-6 relative (tests require 1e-4 * max(1, |log_prob|)); not bit-identical.
+ * Limits: 2 <= k <= 64 (one lane per class), 1 <= beam_width <= 128, 1 <= lm->order <= 6, t_max * beam_width < 2^25;
+ * SL_ERR_UNSUPPORTED otherwise.  workspace: sl_ctc_beam_search_workspace_bytes(batch, t_max, k, beam_width) bytes
+ * (node arena + hash map per utterance, cleared by the call).  One wave per utterance; out_len[b] = -1 flags an arena
+ * overflow, which the workspace bound rules out. */
+typedef struct {
+    const int32_t* trie_child;  /* [n_trie_nodes][k - 1] */
+    const float* trie_min;      /* [n_trie_nodes][k - 1] */
+    const int32_t* trie_word;   /* [n_trie_nodes] */
+    const uint32_t* ngrams;     /* [ngram_slots][8] */
+    int64_t n_trie_nodes;
+    int64_t ngram_slots;        /* power of two */
+    int order;
+    int bos, eos, space_label;  /* space_label -1: no word boundary in the alphabet */
+    float oov_score, lm_weight, word_count_weight, valid_word_count_weight;
+} sl_beam_lm;
+size_t sl_ctc_beam_search_workspace_bytes(int batch, int t_max, int k, int beam_width);
+int sl_ctc_beam_search(const float* probs, const int32_t* lengths, int batch, int t_max, int k, int blank, int beam_width,
+                       int merge_repeated, float eps, const sl_beam_lm* lm, int32_t* out, int32_t* out_len,
+                       float* log_prob, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The same fused update for SEVERAL layers in one launch (the small layers' launches are pure latency): layer i's
  * block starts `offset` floats into param / grad / m / v (weights [k][cin_pad][cout_pad] followed by cout_pad biases). */
 #define SL_ADAM_MAX_LAYERS 16

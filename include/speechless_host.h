@@ -50,6 +50,27 @@ int sl_host_ctc_beam_search(const float* probs, const int32_t* lengths, int batc
                             int beam_width, int merge_repeated, float eps, void* scorer, int32_t* out, int32_t* out_len,
                             float* out_log_prob, int n_threads);
 
+/* ---- the scorer flattened for the GPU decoder (sl_ctc_beam_search, speechless_hip.h; no reference counterpart) ---------
+ * Built from the very structures sl_host_ctc_beam_search reads, so both decoders agree on which words exist.
+ * sl_host_scorer_export_sizes: n_trie_nodes, ngram_slots (a power of two), the model's order and n_labels = the
+ * alphabet's size (= k - 1).  sl_host_scorer_export fills caller-allocated arrays of those sizes:
+ *   trie_child int32[n_trie_nodes][n_labels]: child node of a node by grapheme index, -1 = none.  Node 0 is the root (the
+ *     empty word).  The trie is the scorer's vocabulary trie extended by every vocabulary word the alphabet spells
+ *     without a space (<s> and </s> included), so that it also answers lm.index(word);
+ *   trie_min float[n_trie_nodes][n_labels]: what extending a word by that grapheme scores: the minimum unigram of the
+ *     scorer-trie words under the child, or params[0] (the <unk> unigram) when the child is not in the scorer's trie;
+ *   trie_word int32[n_trie_nodes]: the vocabulary id of the word a node spells exactly, 0 (<unk>) for none;
+ *   ngrams uint32[ngram_slots][8]: open-addressed n-gram table, linear probing.  Words 0..5 are the key: the n word ids
+ *     right-aligned (words 6-n..5, oldest first, the rest 0) with n << 29 or-ed into word 0; word 0 == 0 marks an empty
+ *     slot.  Words 6, 7: log10 probability and log10 back-off (float bits).  Home slot: hash(words 0..5) & (slots - 1),
+ *     hash = FNV-1a over the six words with h ^= h >> 15 after each, then the murmur3 finaliser;
+ *   params float[4]: <unk> unigram (oov score), lm_weight, word_count_weight, valid_word_count_weight;
+ *   ids int32[3]: bos, eos, space label (-1 = none).
+ * Status: 0, -1 bad arguments, -2 two graphemes share a code point, -3 an n-gram longer than 6 or a word id >= 2^29. */
+int sl_host_scorer_export_sizes(void* scorer, int64_t* n_trie_nodes, int64_t* ngram_slots, int* order, int* n_labels);
+int sl_host_scorer_export(void* scorer, int32_t* trie_child, float* trie_min, int32_t* trie_word, uint32_t* ngrams,
+                          float* params, int32_t* ids);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,9 @@ HOST_SIGNATURES = {
     "sl_host_scorer_free": (None, [c_void_p]),
     "sl_host_ctc_beam_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_int]),
+    "sl_host_scorer_export_sizes": (c_int, [c_void_p, POINTER(ctypes.c_int64), POINTER(ctypes.c_int64), POINTER(c_int),
+                                            POINTER(c_int)]),
+    "sl_host_scorer_export": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _HOST_LIB = None

@@ -56,6 +56,14 @@ class ConvGeom(ctypes.Structure):
     ]
 
 
+class BeamLm(ctypes.Structure):
+    """Mirror of sl_beam_lm (include/speechless_hip.h): device pointers of the flat scorer tables."""
+    _fields_ = [("trie_child", c_void_p), ("trie_min", c_void_p), ("trie_word", c_void_p), ("ngrams", c_void_p),
+                ("n_trie_nodes", c_int64), ("ngram_slots", c_int64), ("order", c_int), ("bos", c_int), ("eos", c_int),
+                ("space_label", c_int), ("oov_score", c_float), ("lm_weight", c_float), ("word_count_weight", c_float),
+                ("valid_word_count_weight", c_float)]
+
+
 class WgradJob(ctypes.Structure):
     """Mirror of sl_wgrad_job (include/speechless_hip.h)."""
     _fields_ = [("x", c_void_p), ("g", c_void_p), ("dw", c_void_p), ("geom", ConvGeom)]
@@ -104,6 +112,9 @@ SIGNATURES = {
     "sl_ctc_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sl_ctc_align": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_void_p, c_size_t, c_void_p]),
+    "sl_ctc_beam_search_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "sl_ctc_beam_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, POINTER(BeamLm),
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "sl_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_float,
                              c_float, c_void_p]),
     "sl_adam_pack_layer": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -12,7 +12,8 @@ HOST_LIB_PATH = PACKAGE_DIR / "libspeechless_host.so"  # plain C++ helpers of th
 HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csrc_host" / "beam_search.cpp"]
 CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "misc.hip", "spectrogram.hip", "conv_chain_bf16.hip",
-           "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip"]
+           "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip",
+           "ctc_beam.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
 # f16x3 parity path (csrc/common.h: SL_MFMA16; only the fp32 / plane-output instantiations, about a third of the bf16 build)
 F16_VARIANTS = {"conv_nt_f16": "conv_nt_bf16.hip", "wgrad_tn_f16": "wgrad_tn_bf16.hip"}
@@ -30,7 +31,10 @@ def _newest_source_mtime():
 # registers are still being filled).  A register spill would store such a register before its data has arrived, so a
 # kernel of these files that needs scratch memory is a BUILD ERROR, not a slow kernel.
 # (ctc_align.hip: its lattice states and backtrace windows live in registers by design; a spill there is a bug, too)
-NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip"}
+# (ctc_beam.hip: one wave per utterance whose per-lane state is a handful of registers; scratch there means a dynamically
+# indexed local array crept in)
+NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
+              "ctc_beam.hip"}
 
 
 def _scratch_users(remarks):
@@ -48,7 +52,8 @@ def _scratch_users(remarks):
 
 # ctc.hip: the probability-domain lattice is a lone wave's dependent chain of scalar fp32 operations; packed fp32 VALU
 # (v_pk_mul_f32 out of the SLP vectorizer) costs such a wave more than the two scalar instructions it replaces
-FILE_FLAGS = {"ctc.hip": ["-fno-slp-vectorize"]}
+# ctc_beam.hip: the host decoder rounds lm_weight * delta and the add separately (no FMA may form)
+FILE_FLAGS = {"ctc.hip": ["-fno-slp-vectorize"], "ctc_beam.hip": ["-ffp-contract=off"]}
 
 
 def _compile(unit):

@@ -448,6 +448,106 @@ void decode_range(const float* probs, const int32_t* lengths, int b0, int b1, in
     }
 }
 
+// ---------------------------------------------------------------------------------------------- flat export (GPU decoder)
+// The scorer and its model flattened into the plain arrays of sl_host_scorer_export (speechless_host.h).  The trie here is
+// the scorer's trie EXTENDED by the paths of every vocabulary word the alphabet spells (<s> and </s> included), so that
+// a node also answers lm->index(incomplete_word); `in_scoring` marks the nodes of the scorer's own trie.
+struct FlatExport {
+    int n_labels = 0;
+    std::vector<int32_t> child;  // [node][n_labels]
+    std::vector<float> min_unigram;
+    std::vector<uint8_t> in_scoring;
+    std::vector<int32_t> word;
+    std::vector<uint32_t> ngrams;  // [slots][8]
+    int64_t slots = 0;
+};
+
+uint32_t ngram_hash(const uint32_t* w6) {  // w6: the 6 key words of a table entry (speechless_host.h)
+    uint32_t h = 0x811C9DC5u;
+    for (int i = 0; i < 6; ++i) {
+        h = (h ^ w6[i]) * 0x01000193u;
+        h ^= h >> 15;
+    }
+    h ^= h >> 16;
+    h *= 0x85EBCA6Bu;
+    h ^= h >> 13;
+    h *= 0xC2B2AE35u;
+    h ^= h >> 16;
+    return h;
+}
+
+int build_export(const Scorer& s, FlatExport* x) {
+    const NGramModel& lm = *s.lm;
+    const int nl = (int)s.alphabet.size();
+    x->n_labels = nl;
+    std::unordered_map<uint32_t, int> label_of;
+    for (int i = 0; i < nl; ++i) {
+        if (label_of.count(s.alphabet[i])) return -2;  // two labels of one character: the scorer's trie keeps only one
+        label_of[s.alphabet[i]] = i;
+    }
+    auto new_node = [&]() {
+        x->child.insert(x->child.end(), nl, -1);
+        x->min_unigram.push_back(std::numeric_limits<float>::max());
+        x->in_scoring.push_back(0);
+        x->word.push_back(0);
+        return (int32_t)x->word.size() - 1;
+    };
+    new_node();
+    x->in_scoring[0] = 1;
+    for (uint32_t id = 1; id < lm.words.size(); ++id) {
+        const std::string& w = lm.words[id];
+        std::vector<int> labels;
+        bool ok = true;
+        for (uint32_t cp : Scorer::decode_utf8(w)) {
+            auto l = label_of.find(cp);
+            if (l == label_of.end() || l->second == s.space_label) {
+                ok = false;
+                break;
+            }
+            labels.push_back(l->second);
+        }
+        if (!ok) continue;
+        std::string spelled;
+        for (int l : labels) Scorer::append_utf8(&spelled, s.alphabet[l]);
+        const bool scoring = w != "<s>" && w != "</s>" && lm.grams.count(NGramModel::key(&id, 1));
+        const float unigram = scoring ? lm.grams.at(NGramModel::key(&id, 1)).first : 0.f;
+        int32_t node = 0;
+        for (int l : labels) {
+            int32_t c = x->child[(size_t)node * nl + l];
+            if (c < 0) {
+                c = new_node();
+                x->child[(size_t)node * nl + l] = c;
+            }
+            node = c;
+            if (scoring) {
+                x->in_scoring[node] = 1;
+                x->min_unigram[node] = std::min(x->min_unigram[node], unigram);
+            }
+        }
+        if (spelled == w) x->word[node] = (int32_t)id;  // what lm.index(incomplete_word) returns at this node
+    }
+    // n-gram table: open addressing, linear probing, at most half full
+    int64_t slots = 16;
+    while (slots < 2 * (int64_t)lm.grams.size()) slots *= 2;
+    x->slots = slots;
+    x->ngrams.assign((size_t)slots * 8, 0u);
+    for (const auto& g : lm.grams) {
+        const int n = (int)(g.first.size() / sizeof(uint32_t));
+        if (n < 1 || n > 6) return -3;
+        uint32_t w6[6] = {0, 0, 0, 0, 0, 0};
+        memcpy(w6 + 6 - n, g.first.data(), n * sizeof(uint32_t));
+        if (w6[0] >> 29) return -3;
+        w6[0] |= (uint32_t)n << 29;
+        int64_t i = ngram_hash(w6) & (slots - 1);
+        while (x->ngrams[(size_t)i * 8] != 0) i = (i + 1) & (slots - 1);
+        uint32_t* e = &x->ngrams[(size_t)i * 8];
+        memcpy(e, w6, sizeof(w6));
+        memcpy(e + 6, &g.second.first, 4);
+        memcpy(e + 7, &g.second.second, 4);
+    }
+    return 0;
+}
+
 void set_err(char* err, int err_len, const std::string& msg) {
     if (err && err_len > 0) {
         strncpy(err, msg.c_str(), err_len - 1);
@@ -526,6 +626,48 @@ int sl_host_ctc_beam_search(const float* probs, const int32_t* lengths, int batc
                           out_len, out_log_prob);
     }
     for (auto& t : pool) t.join();
+    return 0;
+}
+
+int sl_host_scorer_export_sizes(void* scorer, int64_t* n_trie_nodes, int64_t* ngram_slots, int* order, int* n_labels) {
+    if (!scorer || !n_trie_nodes || !ngram_slots || !order || !n_labels) return -1;
+    const Scorer* s = static_cast<const Scorer*>(scorer);
+    FlatExport x;
+    const int rc = build_export(*s, &x);
+    if (rc != 0) return rc;
+    *n_trie_nodes = (int64_t)x.word.size();
+    *ngram_slots = x.slots;
+    *order = s->lm->order;
+    *n_labels = x.n_labels;
+    return 0;
+}
+
+int sl_host_scorer_export(void* scorer, int32_t* trie_child, float* trie_min, int32_t* trie_word, uint32_t* ngrams,
+                          float* params, int32_t* ids) {
+    if (!scorer || !trie_child || !trie_min || !trie_word || !ngrams || !params || !ids) return -1;
+    const Scorer* s = static_cast<const Scorer*>(scorer);
+    FlatExport x;
+    const int rc = build_export(*s, &x);
+    if (rc != 0) return rc;
+    const int nl = x.n_labels;
+    for (size_t node = 0; node < x.word.size(); ++node) {
+        trie_word[node] = x.word[node];
+        for (int l = 0; l < nl; ++l) {
+            const int32_t c = x.child[node * nl + l];
+            trie_child[node * nl + l] = c;
+            // what expand_state reads for a character child: the child's minimum unigram, or the <unk> unigram once the
+            // prefix has left the scorer's trie (a node outside it has no descendant inside it)
+            trie_min[node * nl + l] = (c >= 0 && x.in_scoring[c]) ? x.min_unigram[c] : s->oov_score;
+        }
+    }
+    memcpy(ngrams, x.ngrams.data(), x.ngrams.size() * sizeof(uint32_t));
+    params[0] = s->oov_score;
+    params[1] = s->lm_weight;
+    params[2] = s->word_count_weight;
+    params[3] = s->valid_word_count_weight;
+    ids[0] = (int32_t)s->lm->bos;
+    ids[1] = (int32_t)s->lm->eos;
+    ids[2] = s->space_label;
     return 0;
 }
 

@@ -108,3 +108,131 @@ class CtcBeamSearchDecoder:
         if getattr(self, "_scorer", None):
             self._lib.sl_host_scorer_free(self._scorer)
             self._scorer = None
+
+
+# limits of the device decoder (sl_ctc_beam_search, include/speechless_hip.h)
+GPU_MAX_CLASSES = 64
+GPU_MAX_BEAM_WIDTH = 128
+GPU_MAX_LM_ORDER = 6
+
+
+class BeamSearchLimitError(ValueError):
+    """A shape or model outside what the GPU beam-search kernel supports."""
+
+
+def export_scorer_tables(scorer_handle):
+    """The host scorer flattened into numpy arrays (sl_host_scorer_export, include/speechless_host.h)."""
+    lib = _lib()
+    nodes, slots = ctypes.c_int64(), ctypes.c_int64()
+    order, n_labels = ctypes.c_int(), ctypes.c_int()
+    rc = lib.sl_host_scorer_export_sizes(scorer_handle, ctypes.byref(nodes), ctypes.byref(slots), ctypes.byref(order),
+                                         ctypes.byref(n_labels))
+    if rc != 0:
+        raise ValueError("sl_host_scorer_export_sizes failed with status {} (-2: two characters of the alphabet are the "
+                         "same code point)".format(rc))
+    t = dict(trie_child=np.empty((nodes.value, n_labels.value), np.int32),
+             trie_min=np.empty((nodes.value, n_labels.value), np.float32),
+             trie_word=np.empty((nodes.value,), np.int32),
+             ngrams=np.empty((slots.value, 8), np.uint32),
+             params=np.empty((4,), np.float32), ids=np.empty((3,), np.int32))
+    rc = lib.sl_host_scorer_export(scorer_handle, t["trie_child"].ctypes.data, t["trie_min"].ctypes.data,
+                                   t["trie_word"].ctypes.data, t["ngrams"].ctypes.data, t["params"].ctypes.data,
+                                   t["ids"].ctypes.data)
+    if rc != 0:
+        raise ValueError("sl_host_scorer_export failed with status {}".format(rc))
+    t["order"] = order.value
+    return t
+
+
+class GpuCtcBeamSearchDecoder:
+    """CtcBeamSearchDecoder on the GPU (ctc_beam.hip): the same search and the same results, one wave per utterance.
+    The language model's tables are exported from the host scorer and uploaded once.  Limits: at most 64 classes,
+    beam width 1..128, language-model order <= 6 (BeamSearchLimitError, a ValueError, otherwise)."""
+
+    def __init__(self, allowed_characters, language_model=None, beam_width=DEFAULT_BEAM_WIDTH, merge_repeated=False,
+                 kenlm_weight=KENLM_WEIGHT, word_count_weight=WORD_COUNT_WEIGHT,
+                 valid_word_count_weight=VALID_WORD_COUNT_WEIGHT, epsilon=1e-8, threads=8, device="cuda:0"):
+        import torch
+        from . import _lib as hip
+        self.allowed_characters = list(allowed_characters)
+        k = len(self.allowed_characters) + 1
+        if not 2 <= k <= GPU_MAX_CLASSES:
+            raise BeamSearchLimitError("the GPU beam search takes 2..{} classes (one lane each), not {}".format(
+                GPU_MAX_CLASSES, k))
+        if not 1 <= beam_width <= GPU_MAX_BEAM_WIDTH:
+            raise BeamSearchLimitError("the GPU beam search takes a beam width of 1..{}, not {}".format(
+                GPU_MAX_BEAM_WIDTH, beam_width))
+        if language_model is not None and not 1 <= language_model.order <= GPU_MAX_LM_ORDER:
+            raise BeamSearchLimitError("the GPU beam search takes a language model of order 1..{}, not {}".format(
+                GPU_MAX_LM_ORDER, language_model.order))
+        self.beam_width = beam_width
+        self.merge_repeated = merge_repeated
+        self.epsilon = epsilon
+        self.threads = threads  # unused: kept so that the constructor matches CtcBeamSearchDecoder's
+        self.language_model = language_model
+        self.device = torch.device(device)
+        self._hip = hip
+        self._tables = None
+        self._lm = None
+        self._workspace = None
+        if language_model is not None:
+            host = CtcBeamSearchDecoder(self.allowed_characters, language_model, beam_width=1,
+                                        kenlm_weight=kenlm_weight, word_count_weight=word_count_weight,
+                                        valid_word_count_weight=valid_word_count_weight)
+            t = export_scorer_tables(host._scorer)
+            dev = {name: torch.from_numpy(t[name].view(np.int32) if name == "ngrams" else t[name]).to(self.device)
+                   for name in ("trie_child", "trie_min", "trie_word", "ngrams")}
+            self._tables = dev  # keeps the device memory alive
+            p, ids = t["params"], t["ids"]
+            self._lm = hip.BeamLm(dev["trie_child"].data_ptr(), dev["trie_min"].data_ptr(), dev["trie_word"].data_ptr(),
+                                  dev["ngrams"].data_ptr(), t["trie_word"].shape[0], t["ngrams"].shape[0], t["order"],
+                                  int(ids[0]), int(ids[1]), int(ids[2]), float(p[0]), float(p[1]), float(p[2]),
+                                  float(p[3]))
+
+    @classmethod
+    def from_kenlm_directory(cls, kenlm_directory, allowed_characters, **kw):
+        return cls(allowed_characters, NGramLanguageModel(find_arpa(kenlm_directory)), **kw)
+
+    def decode(self, probabilities, prediction_lengths):
+        """probabilities: (B, T', K) numpy array or float32 tensor on the GPU (used in place); prediction_lengths: (B,)
+        numbers, numpy or tensor.  Returns (list of index lists, log-probabilities (B,) numpy), as CtcBeamSearchDecoder."""
+        import torch
+        if isinstance(probabilities, torch.Tensor):
+            probs = probabilities
+            if probs.device.type != "cuda":
+                probs = probs.to(self.device)
+            probs = probs.to(torch.float32).contiguous()
+        else:
+            probs = torch.from_numpy(np.ascontiguousarray(probabilities, dtype=np.float32)).to(self.device)
+        if probs.dim() != 3:
+            raise ValueError("probabilities must be (B, T', K)")
+        b, t, k = probs.shape
+        if k != len(self.allowed_characters) + 1:
+            raise ValueError("{} classes for an alphabet of {} characters + blank".format(k, len(self.allowed_characters)))
+        if isinstance(prediction_lengths, torch.Tensor):
+            lengths = prediction_lengths.reshape(-1).to(device=probs.device, dtype=torch.int32).contiguous()
+        else:
+            lengths = torch.from_numpy(np.ascontiguousarray(np.asarray(prediction_lengths).reshape(-1),
+                                                            dtype=np.int32)).to(probs.device)
+        if lengths.numel() != b:
+            raise ValueError("{} lengths for a batch of {}".format(lengths.numel(), b))
+        lib = self._hip.lib()
+        need = lib.raw("sl_ctc_beam_search_workspace_bytes")(b, t, k, self.beam_width)
+        if need == 0:
+            raise BeamSearchLimitError("the GPU beam search cannot take a ({}, {}, {}) batch at beam width {}".format(
+                b, t, k, self.beam_width))
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != probs.device:
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=probs.device)
+        out = torch.empty((b, t), dtype=torch.int32, device=probs.device)
+        out_len = torch.empty((b,), dtype=torch.int32, device=probs.device)
+        log_prob = torch.empty((b,), dtype=torch.float32, device=probs.device)
+        with torch.cuda.device(probs.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            lib.call("sl_ctc_beam_search", probs.data_ptr(), lengths.data_ptr(), b, t, k, k - 1, self.beam_width,
+                     1 if self.merge_repeated else 0, self.epsilon,
+                     ctypes.byref(self._lm) if self._lm is not None else None, out.data_ptr(), out_len.data_ptr(),
+                     log_prob.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), stream)
+        out, out_len, log_prob = out.cpu().numpy(), out_len.cpu().numpy(), log_prob.cpu().numpy()
+        if (out_len < 0).any():
+            raise RuntimeError("sl_ctc_beam_search: node arena overflow")
+        return [list(map(int, out[i, :out_len[i]])) for i in range(b)], log_prob

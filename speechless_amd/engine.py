@@ -776,6 +776,15 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         lens = buf.decoded_len.cpu().numpy()
         return [list(map(int, dec[i, :lens[i]])) for i in range(buf.batch)], buf.frame_argmax.cpu().numpy()
 
+    def beam_search(self, decoder, prediction_lengths=None):
+        """CTC beam search (decoder: decoder.GpuCtcBeamSearchDecoder) over the current probabilities, in place on the
+        device: no host copy of the probabilities, no gradient buffers.  Returns (list of index lists, log-probabilities
+        (B,) numpy), as the decoder's decode()."""
+        buf = self.cur
+        if prediction_lengths is not None:
+            self.set_input_lengths(prediction_lengths)
+        return decoder.decode(buf.probs, buf.input_len)  # launched on the current stream, behind forward()
+
     # ------------------------------------------------------------------ loss + backward
 
     def set_labels(self, label_batch, label_lengths, prediction_lengths):

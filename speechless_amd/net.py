@@ -245,7 +245,7 @@ class Wav2Letter:
                  asg_initial_probabilities=None, kenlm_directory=None,
                  # --- extensions of this implementation (keyword-only in spirit) ---
                  compute_dtype=None, device="cuda:0", seed=None, ctc_epsilon=1e-8, layer_sizes=None,
-                 load_optimizer_state=False, eval_dtype=None):
+                 load_optimizer_state=False, eval_dtype=None, beam_search_device="host"):
         if frozen_layer_count > 0 and load_model_from_directory is None:
             raise ValueError("Layers cannot be frozen if model is trained from scratch.")
         if use_asg:
@@ -253,6 +253,9 @@ class Wav2Letter:
         if dropout is not None and not 0.0 <= dropout < 1.0:
             raise ValueError("dropout must be a rate in [0, 1)")
         self.kenlm_directory = kenlm_directory
+        if beam_search_device not in ("host", "gpu"):
+            raise ValueError("beam_search_device must be 'host' or 'gpu', not {!r}".format(beam_search_device))
+        self.beam_search_device = beam_search_device
         self.grapheme_encoding = CtcGraphemeEncoding(allowed_characters=allowed_characters)
         self.use_asg = use_asg
         self.frozen_layer_count = frozen_layer_count
@@ -306,8 +309,13 @@ class Wav2Letter:
             if list(allowed_characters) != expected:
                 raise ValueError("Allowed characters {} differ from those expected by kenlm decoder: {}".format(
                     allowed_characters, expected))
-            self._beam_decoder = CtcBeamSearchDecoder.from_kenlm_directory(self.kenlm_directory, allowed_characters,
-                                                                           epsilon=ctc_epsilon)
+            if beam_search_device == "gpu":  # extension: the same search in ctc_beam.hip (Engine.beam_search)
+                from .decoder import GpuCtcBeamSearchDecoder
+                self._beam_decoder = GpuCtcBeamSearchDecoder.from_kenlm_directory(
+                    self.kenlm_directory, allowed_characters, epsilon=ctc_epsilon, device=device)
+            else:
+                self._beam_decoder = CtcBeamSearchDecoder.from_kenlm_directory(self.kenlm_directory, allowed_characters,
+                                                                               epsilon=ctc_epsilon)
         if load_model_from_directory is not None:
             self.load_weights(allowed_characters_for_loaded_model, load_epoch, load_model_from_directory,
                               loaded_first_layers_count=frozen_layer_count if reinitialize_trainable_loaded_layers
@@ -502,7 +510,9 @@ class Wav2Letter:
         engine.set_labels(inputs[names.label_batch], inputs[names.label_lengths],
                           inputs[names.prediction_lengths])
         losses = engine.ctc().cpu().numpy()
-        if self._beam_decoder is not None:  # net.py:444-451: beam search scored by the language model
+        if self._beam_decoder is not None and self.beam_search_device == "gpu":
+            decoded, _ = engine.beam_search(self._beam_decoder, inputs[names.prediction_lengths])
+        elif self._beam_decoder is not None:  # net.py:444-451: beam search scored by the language model
             decoded, _ = self._beam_decoder.decode(engine.cur.probs.cpu().numpy(),
                                                    inputs[names.prediction_lengths])
         else:
