@@ -11,6 +11,8 @@ import torch  # noqa: F401  (plumbing: device memory, streams, torch.distributed
 
 import os
 
+from .launch_list import HipLibraryError, raise_status  # noqa: F401  (the error every failing library call raises)
+
 # SL_LIB_PATH: experiments only (a probe build of the library next to the real one)
 LIB_PATH = Path(os.environ.get("SL_LIB_PATH") or Path(__file__).resolve().parent / "libspeechless_hip.so")
 
@@ -54,6 +56,15 @@ class ConvGeom(ctypes.Structure):
         ("y_batch_stride", c_int64),
         ("acc_scale", c_float),
     ]
+
+    def copy_from(self, src):
+        for name, _ in ConvGeom._fields_:
+            setattr(self, name, getattr(src, name))
+
+    def copy(self):
+        g = ConvGeom()
+        g.copy_from(self)
+        return g
 
 
 class BeamLm(ctypes.Structure):
@@ -162,10 +173,6 @@ SIGNATURES = {
 }
 
 
-class HipLibraryError(RuntimeError):
-    pass
-
-
 class HipLibrary:
     """Loaded libspeechless_hip.so with typed entry points.  `call(name, *args)` raises on a non-zero status."""
 
@@ -199,7 +206,7 @@ class HipLibrary:
     def call(self, name, *args):
         rc = self._fn[name](*args)
         if rc != 0:
-            raise HipLibraryError("{} failed with status {}: {}".format(name, rc, self.last_error()))
+            raise_status(name, rc, self.last_error)
 
 
 _LIB = None

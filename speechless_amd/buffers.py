@@ -16,7 +16,7 @@ class _Buffers:
     only the rows between the new length and the previous high-water mark."""
 
     def __init__(self, eng, batch, tt_pad):
-        dev = eng.device
+        dev = self.device = eng.device
         dt = eng.torch_dtype
         p0 = eng.plans[0]
         pl = eng.planes  # 3 on the bf16x3 path: every tensor row holds the planes [hi | lo | hi] (csrc/split3.hip)
@@ -113,15 +113,10 @@ class _Buffers:
                 # gradient is two launches -- the [hi | lo] prefix of the windows against gx0's hi plane (front_geom with
                 # cin = 2 K_pad) and their hi plane against gx0's lo plane (front_wgrad_geom_b) -- plus sl_split3_wgrad_combine
                 self.frames32 = torch.zeros((batch, 2 * tt_pad, fp.cin_pad), dtype=torch.float32, device=dev)
-                sg = ConvGeom()
-                for name, _ in ConvGeom._fields_:
-                    setattr(sg, name, getattr(g, name))
+                sg = g.copy()
                 sg.y_row0, sg.y_row_stride, sg.y_batch_stride = 0, fp.cout_pad, 2 * tt_pad * fp.cout_pad
                 self.front_stage_geom = sg
-                wa, wb = ConvGeom(), ConvGeom()
-                for w in (wa, wb):
-                    for name, _ in ConvGeom._fields_:
-                        setattr(w, name, getattr(g, name))
+                wa, wb = g.copy(), g.copy()
                 wa.cin, wb.cin = 2 * fp.cin_pad, fp.cin_pad
                 self.front_wgrad_geom_a, self.front_wgrad_geom_b = wa, wb
         self.half_geoms = {}   # split top (Engine.split_top): (kind, layer) -> the layer's geometry for half the batch
@@ -136,7 +131,7 @@ class _Buffers:
         self.bwd_ready = False
         self.nt_ws = None
         self.wgrad_ws = None
-        self.launch_lists = {}   # recorded launch lists (Engine._replay); dropped whenever a pointer they hold changes
+        self.launch_lists = {}   # recorded launch lists (launch_list.py); dropped whenever a pointer they hold changes: grow()
         self.chain_tables = {}   # sl_conv1d_chain pointer tables of this buffer set (Engine._chain_table)
         self.multi_tables = {}   # sl_conv1d_wgrad_multi job tables (their geometries follow set_length)
         self.wgrad_multi_ws = None
@@ -174,17 +169,12 @@ class _Buffers:
         self.logq = self._logq_flat[:b * t_out * k].view(b, t_out, k)
         self.decoded = self._decoded_flat[:b * t_out].view(b, t_out)
         self.frame_argmax = self._argmax_flat[:b * t_out].view(b, t_out)
-        for geoms in (self.fwd_geom, self.wgrad_geom, self.dgrad_geom):
-            for g in geoms:
-                if g is not None:
-                    g.t_out = t_out
+        for g in (*self.fwd_geom, *self.wgrad_geom, *self.dgrad_geom, *self.plane_geoms.values(), *self.half_geoms.values()):
+            if g is not None:
+                g.t_out = t_out
         for table in self.multi_tables.values():
             for job in (table[0] if isinstance(table, tuple) else table):  # (bf16x3: (table, partial buffers, ...))
                 job.geom.t_out = t_out
-        for g in self.plane_geoms.values():
-            g.t_out = t_out
-        for g in self.half_geoms.values():
-            g.t_out = t_out
         for g in (self.front_geom, self.front_stage_geom, getattr(self, "front_wgrad_geom_a", None), self.front_wgrad_geom_b):
             if g is not None:
                 g.t_out = t_in
@@ -196,18 +186,31 @@ class _Buffers:
         if self.bwd_ready and t_out not in self._ws_sized_bwd:
             self.size_backward_workspaces(eng)
 
-    def size_nt_workspace(self, eng, geoms, kind):
-        need = 16
-        for hint in eng.cu_hints():  # (the split choosers consult sl_set_available_cus: size for every setting in use)
-            lib().call("sl_set_available_cus", hint)
-            for p, g in zip(eng.plans, geoms):
-                if g is not None:
-                    need = max(need, lib().raw("sl_conv1d_nt_workspace_bytes")(
-                        ctypes.byref(g), eng.dtype_code, eng.nt_cfg.get((kind, p.spec.name), 0)))
-        lib().call("sl_set_available_cus", eng._cu_hint_active)
-        if self.nt_ws is None or self.nt_ws.numel() < need:
-            self.nt_ws = torch.empty((need,), dtype=torch.uint8, device=eng.device)
+    def grow(self, name, need, floor=0, first_drops=True):
+        """Makes the byte workspace `name` hold at least `need` bytes: if it is missing or smaller, allocates max(need, floor)
+        bytes AND drops the recorded launch lists -- they hold the pointer that is freed here.  first_drops=False: not when the
+        workspace did not exist yet (no list can hold a pointer to it).  Returns whether it allocated."""
+        ws = getattr(self, name, None)
+        if ws is not None and ws.numel() >= need:
+            return False
+        setattr(self, name, torch.empty((max(need, floor),), dtype=torch.uint8, device=self.device))
+        if ws is not None or first_drops:
             self.launch_lists = {}
+        return True
+
+    def invalidate(self):
+        """after a change of what the step launches (CU setting, an A/B knob): the recorded lists and the balanced
+        weight-gradient job tables with their workspace (sized for the settings in use) are rebuilt by the next step"""
+        self.launch_lists.clear()
+        self.multi_tables = {}
+        self.wgrad_multi_ws = None
+
+    def size_nt_workspace(self, eng, geoms, kind):
+        # (the split choosers consult sl_set_available_cus: size for every setting in use)
+        self.grow("nt_ws", eng._max_over_cu_hints(lambda: max(
+            [16] + [lib().raw("sl_conv1d_nt_workspace_bytes")(ctypes.byref(g), eng.dtype_code,
+                                                               eng.nt_cfg.get((kind, p.spec.name), 0))
+                    for p, g in zip(eng.plans, geoms) if g is not None])))
 
     def ensure_backward(self, eng):
         if self.bwd_ready:
@@ -233,10 +236,7 @@ class _Buffers:
                 self._g0_keepalive = full
                 self._blocks.append(self.g[p.index].unsqueeze(0))
             pl = eng.planes
-            wg = ConvGeom()
-            f = self.fwd_geom[p.index]
-            for name, _ in ConvGeom._fields_:
-                setattr(wg, name, getattr(f, name))
+            wg = self.fwd_geom[p.index].copy()
             wg.y_row0 = HALO
             wg.y_row_stride = p.cout_pad * pl
             wg.y_batch_stride = self.rows * p.cout_pad * pl
@@ -248,9 +248,7 @@ class _Buffers:
                 # up to lo1 (five planes where that is a whole number of 128-wide tiles, else all six) and B the window
                 # [hi0 | hi1] in its middle (Engine.x3_b_window: x pointer + 2 cin_pad, frame stride cin_pad inside RB): two
                 # planes instead of six (round 5; the whole row for both was 0.18 + 0.18 ms at config 3)
-                wb = ConvGeom()
-                for name, _ in ConvGeom._fields_:
-                    setattr(wb, name, getattr(wg, name))
+                wb = wg.copy()
                 if p.index == 0 and p.spec.stride == 2:
                     # (the window decision is frozen HERE, with the geometries: the launch-time pointer offset and the
                     # combine read it back from the buffer set, not from the engine attribute -- ADVICE r5)
@@ -298,10 +296,7 @@ class _Buffers:
                 # of the FRAME rows (a pair row of 2 cin_pad floats = two frame rows of cin_pad)
                 dg.y_row0, dg.y_batch_stride = 0, (self.tt_pad + eng.FRONT_DGRAD_EXTRA_ROWS) * p0.cin_view
             self.front_dgrad_geom = dg
-        self.bias_ws = None
-        self.bwd1x1_ws = None
-        self.ctc_ws = None
-        self.labels = None
+        self.bias_ws = self.bwd1x1_ws = self.ctc_ws = self.labels = None
         self.label_len = torch.zeros((self.batch,), dtype=torch.int32, device=dev)
         self.bwd_ready = True
         self.size_backward_workspaces(eng)
@@ -310,24 +305,17 @@ class _Buffers:
         L = lib()
         self._ws_sized_bwd.add(self.t_out)
         first = eng.frozen_layer_count
-        ws_bytes = 0
-        bias_ws = 0
-        for hint in eng.cu_hints():
-            L.call("sl_set_available_cus", hint)
-            for p in eng.plans[first:]:
-                wg = self.wgrad_geom[p.index]
-                ws_bytes = max(ws_bytes, L.raw("sl_conv1d_wgrad_workspace_bytes")(
-                    ctypes.byref(wg), eng.dtype_code, eng.nt_cfg.get(("wgrad", p.spec.name), 0)))
-                bias_ws = max(bias_ws, L.raw("sl_bias_grad_workspace_bytes")(ctypes.byref(wg)))
-        L.call("sl_set_available_cus", eng._cu_hint_active)
+        ws_bytes = eng._max_over_cu_hints(lambda: max(
+            [0] + [L.raw("sl_conv1d_wgrad_workspace_bytes")(ctypes.byref(self.wgrad_geom[p.index]), eng.dtype_code,
+                                                            eng.nt_cfg.get(("wgrad", p.spec.name), 0))
+                   for p in eng.plans[first:]]))
+        bias_ws = eng._max_over_cu_hints(lambda: max(
+            [0] + [L.raw("sl_bias_grad_workspace_bytes")(ctypes.byref(self.wgrad_geom[p.index])) for p in eng.plans[first:]]))
         self.size_nt_workspace(eng, self.dgrad_geom, "dgrad")
         if eng.front_plan is not None:
             for g in (self.front_geom, self.front_stage_geom, self.front_dgrad_geom):
                 if g is not None:
-                    need = L.raw("sl_conv1d_nt_workspace_bytes")(ctypes.byref(g), eng.dtype_code, 0)
-                    if self.nt_ws.numel() < need:
-                        self.nt_ws = torch.empty((need,), dtype=torch.uint8, device=eng.device)
-                        self.launch_lists = {}
+                    self.grow("nt_ws", L.raw("sl_conv1d_nt_workspace_bytes")(ctypes.byref(g), eng.dtype_code, 0))
             for g in ((self.front_wgrad_geom_a, self.front_wgrad_geom_b) if eng.planes > 1 else (self.front_geom,)):
                 ws_bytes = max(ws_bytes, L.raw("sl_conv1d_wgrad_workspace_bytes")(ctypes.byref(g), eng.dtype_code, 0))
             bias_ws = max(bias_ws, L.raw("sl_bias_grad_workspace_bytes")(ctypes.byref(self.front_geom)))
@@ -347,12 +335,8 @@ class _Buffers:
                 if e0 > lo:
                     ws_bytes = max(ws_bytes, L.raw("sl_conv1d_wgrad_grouped_workspace_bytes")(
                         ctypes.byref(self.wgrad_geom[lo]), e0 - lo + 1, 0))
-        if self.wgrad_ws is None or self.wgrad_ws.numel() < ws_bytes:
-            self.wgrad_ws = torch.empty((max(ws_bytes, 16),), dtype=torch.uint8, device=eng.device)
-            self.launch_lists = {}
-        if self.bias_ws is None or self.bias_ws.numel() < bias_ws:
-            self.bias_ws = torch.empty((max(bias_ws, 16),), dtype=torch.uint8, device=eng.device)
-            self.launch_lists = {}
+        self.grow("wgrad_ws", ws_bytes, 16)
+        self.grow("bias_ws", bias_ws, 16)
         last = len(eng.plans) - 1
         if eng.dtype == "bf16" and last > first:
             # (its split count only shrinks with fewer CUs: the whole-chip size covers every hint)
@@ -360,15 +344,12 @@ class _Buffers:
                                                                    eng.grapheme_set_size, eng.dtype_code, 0)
             # a PART of the batch (Engine.split_top) can pick more chunk ranges than the whole batch does (33 chunks: 11
             # ranges of 3, 32 chunks: 16 of 2): size for the most any chunk count gets -- that of a very long batch
-            many = ConvGeom()
-            for name, _ in ConvGeom._fields_:
-                setattr(many, name, getattr(self.wgrad_geom[last], name))
+            many = self.wgrad_geom[last].copy()
             many.batch = 4096
             need = max(need, L.raw("sl_conv1d_backward_1x1_workspace_bytes")(ctypes.byref(many), eng.grapheme_set_size,
                                                                              eng.dtype_code, 0))
-            if need and (self.bwd1x1_ws is None or self.bwd1x1_ws.numel() < need):
-                self.bwd1x1_ws = torch.empty((need,), dtype=torch.uint8, device=eng.device)
-                self.launch_lists = {}
+            if need:
+                self.grow("bwd1x1_ws", need)
 
     def ensure_ctc(self, eng, l_max):
         """CTC workspace for label rows of up to l_max graphemes: sized in BYTES and never shrunk (the library's need
@@ -378,9 +359,7 @@ class _Buffers:
             half = _round_up(lib().raw("sl_ctc_workspace_bytes")(self.batch - 1, self.tt_pad, l_max), 256)
             self.ctc_half_bytes = max(self.ctc_half_bytes, half)
             need = max(need, 2 * self.ctc_half_bytes)
-        if self.ctc_ws is None or self.ctc_ws.numel() < need:
-            self.ctc_ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=eng.device)
-            self.launch_lists = {}
+        self.grow("ctc_ws", need, 16)
         if self.labels is None or self.labels.shape[1] < l_max:
             self.labels = torch.zeros((self.batch, l_max), dtype=torch.int32, device=eng.device)
 

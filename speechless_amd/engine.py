@@ -17,8 +17,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ConvGeom, lib
+from . import _lib, launch_list
+from ._lib import lib
 from .buffers import _Buffers
 from .engine_front import FrontLayerMixin
 from .engine_split import SplitTopMixin
@@ -164,7 +164,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self._dropout_steps = 0
         self.cur = None
         self.timeline = None
-        self.kernel_timeline = None  # (set of tags, list of (tag, start, stop)): see _launch
+        self.kernel_timeline = None  # (set of tags, list of (tag, start, stop)): see _around
         self._side_stream = None
         # "ones channel": the last padded output channel of every hidden layer carries the constant 1 (bias 1, zero weights),
         # so the next layer's weight-gradient GEMM -- which multiplies the padding through anyway -- leaves that layer's
@@ -190,8 +190,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         # instead of the whole row (buffers.py; A/B knob, read when a buffer set's backward geometries are built)
         self.x3_b_window = os.environ.get("SL_X3_B_WINDOW", "1") != "0"
         self.nt_cfg = {}  # optional per-launch tile configuration overrides {("fwd"|"dgrad", layer name): cfg word}
-        # Launch lists: the ~60 C-ABI calls and 4 stream hand-overs of a step are recorded the first time a buffer set
-        # runs them and replayed afterwards with their arguments already marshalled -- the Python around each launch
+        # Launch lists (launch_list.py): the ~60 C-ABI calls and 4 stream hand-overs of a step are recorded the first time a
+        # buffer set runs them and replayed afterwards with their arguments already marshalled -- the Python around each launch
         # (tensor views of the flat parameter buffers, data_ptr() calls, geometry look-ups: ~10 us per launch) was what
         # capped the host-fed loop below the rate of the resident step.  Geometries are passed by reference and
         # re-targeted in place (_Buffers.set_length), so one list serves every batch length of a buffer set.
@@ -245,9 +245,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             raise ValueError("comm_cus must be in 0 .. 128")
         self.comm_cus = comm_cus
         for buf in self._buffers.values():
-            buf.launch_lists = {}
-            buf.multi_tables = {}  # (their workspaces are sized for the CU settings in use: rebuilt by the next backward)
-            buf.wgrad_multi_ws = None
+            buf.invalidate()
             buf.size_nt_workspace(self, buf.fwd_geom, "fwd")
             if buf.bwd_ready:
                 buf.size_backward_workspaces(self)
@@ -260,37 +258,50 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
     def _set_cu_hint(self, cus):
         """sl_set_available_cus for the launches this THREAD enqueues from here on (the library keeps the setting per thread)
         and this engine's record of it -- one op of a recorded backward, so that a replayed step tracks it too and the sizing
-        helpers that run in between (_part_geom, _wgrad_multi_workspace_need) restore the right value"""
+        helpers that run in between (_max_over_cu_hints) restore the right value"""
         self.lib.call("sl_set_available_cus", cus)
         self._cu_hint_active = cus
+
+    def _max_over_cu_hints(self, fn):
+        """max of fn() under EVERY sl_set_available_cus setting this engine launches under -- the library's split choosers
+        consult it, so a workspace sized under the data-parallel CU hint alone would be too small for a later step without it
+         -- with the active setting restored whatever happens: it is process-wide library state"""
+        need = 0
+        try:
+            for hint in self.cu_hints():
+                self.lib.call("sl_set_available_cus", hint)
+                need = max(need, fn())
+        finally:
+            self.lib.call("sl_set_available_cus", self._cu_hint_active)
+        return need
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
     def _launch(self, tag, name, *args):
-        """One C-ABI call.  With self.timeline set (a list), brackets it with HIP events on the launch stream so
-        that bench.py can read per-kernel durations live (tag = logical kernel instance, e.g. 'fwd:big_conv_1')."""
-        if self.kernel_timeline is not None and tag in self.kernel_timeline[0]:
-            # events immediately around the MAIN kernel of this call (sl_profile_next_kernel), none anywhere else: the
-            # step runs as in the timed region and the duration is what rocprofv3 reports for that kernel
-            start = torch.cuda.Event(enable_timing=True)
-            stop = torch.cuda.Event(enable_timing=True)
-            start.record()  # creates the HIP events; the library records them again around the kernel
-            stop.record()
-            self.lib.call("sl_profile_next_kernel", start.cuda_event, stop.cuda_event)
+        """One C-ABI call (tag = logical kernel instance, e.g. 'fwd:big_conv_1'): recorded while a launch list is being built,
+        instrumented as a replayed launch would be while a measurement mode is on (_around)."""
+        if self.timeline is None and self.kernel_timeline is None:
             self.lib.call(name, *args)
-            self.kernel_timeline[1].append((tag, start, stop))
+            if self._rec is not None:  # the raw entry point and its arguments
+                self._rec.launch(self.lib.raw(name), args, name, tag, torch.cuda.current_stream(self.device))
             return
-        if self.timeline is None:
-            self.lib.call(name, *args)
-            if self._rec is not None:  # building a launch list (see _replay): the raw entry point and its arguments
-                self._rec.append((0, self.lib.raw(name), args, name, tag, torch.cuda.current_stream(self.device)))
-            return
-        start, stop = TimingEvent(), TimingEvent()  # (timestamps only: no system-scope release between the launches)
-        start.record()
-        self.lib.call(name, *args)
-        stop.record()
-        self.timeline.append((tag, start, stop))
+        rc = self._around()(self.lib.raw(name), args, tag, None)
+        if rc != 0:
+            launch_list.raise_status(name, rc, self.lib.last_error)
+
+    def _around(self):
+        """How a launch is instrumented right now (the `around` of launch_list.replay, and of _launch on the eager path), or
+        None in the timed region.  self.timeline set (a list): HIP events on the launch stream around every call, for bench.py's
+        per-launch table.  self.kernel_timeline set ((tags, list)): events attached to the main kernels of the tagged launches,
+        for bench.py's roofline leg."""
+        if self.timeline is not None:
+            return launch_list.timed(self.timeline, TimingEvent)  # (timestamps only: no system-scope release between launches)
+        if self.kernel_timeline is not None:
+            return launch_list.profiled(
+                *self.kernel_timeline, new_event=lambda: torch.cuda.Event(enable_timing=True),
+                attach=lambda start, stop: self.lib.call("sl_profile_next_kernel", start.cuda_event, stop.cuda_event))
+        return None
 
     def _hand_over(self, src, dst):
         """dst waits for everything enqueued on src so far (event record on src + wait on dst)."""
@@ -298,77 +309,13 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         ev.record(src)
         dst.wait_event(ev)
         if self._rec is not None:
-            self._rec.append((1, ev, src, dst))
+            self._rec.hand_over(ev, src, dst)
 
-    def _replay(self, ops, callback=None):
-        if self.timeline is not None:
-            return self._replay_timeline(ops, callback)
-        if self.kernel_timeline is not None:
-            return self._replay_profiled(ops, callback)
-        for op in ops:
-            kind = op[0]
-            if kind == 0:
-                rc = op[1](*op[2])
-                if rc != 0:
-                    raise _lib.HipLibraryError("{} failed with status {}: {}".format(op[3], rc, self.lib.last_error()))
-            elif kind == 1:
-                op[1].record(op[2])
-                op[3].wait_event(op[1])
-            elif kind == 2:
-                callback(op[1])
-            else:  # a step of the sequence that has to be marshalled afresh every time (pointers / sizes that change per batch)
-                op[1](*op[2])
-
-    def _replay_timeline(self, ops, callback):
-        """_replay with HIP events on the launch stream around every C-ABI call (self.timeline, bench.py's per-launch table):
-        the step still runs from its recorded lists -- marshalled eagerly, the Python between the launches starves the GPU and
-        the MFMA-bound kernels behind the gaps run at lower clocks (round 5: their durations came out 17 % above the kernel's
-        own timestamps)"""
-        out = self.timeline
-        for op in ops:
-            kind = op[0]
-            if kind == 0:
-                start, stop = TimingEvent(), TimingEvent()
-                start.record(op[5])  # (the stream the launch was recorded on: bias passes run on the side stream)
-                rc = op[1](*op[2])
-                stop.record(op[5])
-                out.append((op[4], start, stop))
-                if rc != 0:
-                    raise _lib.HipLibraryError("{} failed with status {}: {}".format(op[3], rc, self.lib.last_error()))
-            elif kind == 1:
-                op[1].record(op[2])
-                op[3].wait_event(op[1])
-            elif kind == 2:
-                callback(op[1])
-            else:
-                op[1](*op[2])
-
-    def _replay_profiled(self, ops, callback):
-        """_replay with events attached to the main kernels of the launches named in self.kernel_timeline (bench.py's roofline
-        leg): the step runs from its recorded lists exactly as in the timed region -- launched eagerly, the Python between the
-        launches leaves gaps on the GPU and the kernels behind them run at other clocks (live 0.237 against 0.212 ms under
-        rocprofv3 in the same process, round 5)"""
-        tags, out = self.kernel_timeline
-        for op in ops:
-            kind = op[0]
-            if kind == 0:
-                if op[4] in tags:
-                    start = torch.cuda.Event(enable_timing=True)
-                    stop = torch.cuda.Event(enable_timing=True)
-                    start.record()  # creates the HIP events; the library attaches them to the kernel's dispatch
-                    stop.record()
-                    self.lib.call("sl_profile_next_kernel", start.cuda_event, stop.cuda_event)
-                    out.append((op[4], start, stop))
-                rc = op[1](*op[2])
-                if rc != 0:
-                    raise _lib.HipLibraryError("{} failed with status {}: {}".format(op[3], rc, self.lib.last_error()))
-            elif kind == 1:
-                op[1].record(op[2])
-                op[3].wait_event(op[1])
-            elif kind == 2:
-                callback(op[1])
-            else:
-                op[1](*op[2])
+    def _bucket_ready(self, on_bucket_ready, b):
+        """every launch that writes gradient bucket b is enqueued on the main stream"""
+        on_bucket_ready(b)
+        if self._rec is not None:
+            self._rec.bucket_ready(b)
 
     def _eager_op(self, fn, *args):
         """fn(*args) now; while a launch list is being recorded it becomes ONE op of the list that calls fn again at
@@ -379,14 +326,28 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         finally:
             self._rec = rec
         if rec is not None:
-            rec.append((3, fn, args))
+            rec.eager(fn, args)
 
-    def _launch_list(self, buf, key):
-        """The recorded launch list of `key` for this buffer set, or None (then the caller runs eagerly; with
-        self._rec set by start_recording() that run records the list)."""
-        if not self.use_launch_lists or self._rec is not None:
-            return None
-        return buf.launch_lists.get(key)  # (with self.timeline / self.kernel_timeline set: _replay_timeline / _replay_profiled)
+    def _run_recorded(self, buf, key, eager, callback=None):
+        """One sequence of the step on buffer set `buf`: replays the launch list recorded under `key` (True), or runs eager()
+        -- and keeps what it launches as that list unless a measurement mode instruments the launches, a list is already being
+        recorded, or key is None (the sequence takes per-step values).  callback: on_bucket_ready of backward()."""
+        usable = key is not None and self.use_launch_lists and self._rec is None
+        ops = buf.launch_lists.get(key) if usable else None
+        measuring = self.timeline is not None or self.kernel_timeline is not None
+        if ops is not None:
+            launch_list.replay(ops, callback, self._around() if measuring else None)
+            return True
+        if not usable or measuring:
+            eager()
+            return False
+        self._rec = launch_list.Recorder(self.lib.last_error)
+        try:
+            eager()
+            buf.launch_lists[key] = self._rec
+        finally:
+            self._rec = None
+        return False
 
     def buffers(self, batch, t_in):
         """Buffers for batches of `batch` utterances padded to t_in frames: one set per (batch, output frames rounded
@@ -466,20 +427,26 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
 
     # ------------------------------------------------------------------ weights
 
-    def set_weights(self, weights):
-        """weights: [(W (k,Cin,Cout), b (Cout,))] numpy, Keras layout."""
-        assert len(weights) == len(self.all_plans)
-        self.params.zero_()
-        for p, (w, b) in zip(self._public_plans(), weights):
+    def _write_padded(self, flat, arrays, what):
+        """arrays: [(W (k,Cin,Cout), b (Cout,))] numpy, Keras layout, into the padded flat buffer (zero everywhere else);
+        what: the complaint about a layer (name, shapes) that does not fit"""
+        flat.zero_()
+        for p, (w, b) in zip(self._public_plans(), arrays):
             s = p.spec
             w = self._front_to_gemm(p, w)
             if tuple(w.shape) != (s.kernel_size, s.cin, s.cout) or tuple(b.shape) != (s.cout,):
-                raise ValueError("weights of layer {} have shape {} / {}".format(s.name, w.shape, b.shape))
-            wv, bv = self.layer_param_views(self.params, p)
+                raise ValueError(what.format(s.name, w.shape, b.shape))
+            wv, bv = self.layer_param_views(flat, p)
             wv[:, :s.cin, :s.cout] = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32)).to(self.device)
             bv[:s.cout] = torch.as_tensor(np.ascontiguousarray(b, dtype=np.float32)).to(self.device)
-            if self._has_ones_output(p):
-                bv[p.cout_pad - 1] = 1.0  # relu(0 * x + 1) = elu(1) = 1: the ones channel (see self.ones_channel)
+
+    def set_weights(self, weights):
+        """weights: [(W (k,Cin,Cout), b (Cout,))] numpy, Keras layout."""
+        assert len(weights) == len(self.all_plans)
+        self._write_padded(self.params, weights, "weights of layer {} have shape {} / {}")
+        for p in self.all_plans:
+            if self._has_ones_output(p):  # relu(0 * x + 1) = elu(1) = 1: the ones channel (see self.ones_channel)
+                self.layer_param_views(self.params, p)[1][p.cout_pad - 1] = 1.0
         self._packed_dirty = True
         self._weights_set_count += 1
 
@@ -551,15 +518,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
 
     def set_optimizer_state(self, state):
         for name, flat in (("m", self.adam_m), ("v", self.adam_v)):
-            flat.zero_()
-            for p, (w, b) in zip(self._public_plans(), state[name]):
-                s = p.spec
-                w = self._front_to_gemm(p, w)
-                if tuple(w.shape) != (s.kernel_size, s.cin, s.cout) or tuple(b.shape) != (s.cout,):
-                    raise ValueError("optimizer state of layer {} has shape {} / {}".format(s.name, w.shape, b.shape))
-                wv, bv = self.layer_param_views(flat, p)
-                wv[:, :s.cin, :s.cout] = torch.as_tensor(np.ascontiguousarray(w, dtype=np.float32)).to(self.device)
-                bv[:s.cout] = torch.as_tensor(np.ascontiguousarray(b, dtype=np.float32)).to(self.device)
+            self._write_padded(flat, state[name], "optimizer state of layer {} has shape {} / {}")
         self.adam_iterations = int(state["iterations"])
         self._dropout_steps = int(state.get("dropout_steps", 0))
 
@@ -605,12 +564,10 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         if self.planes > 1:
             self._launch("pack_input", self._x3("sl_split3_pack_input"), src.data_ptr(), buf.x0.data_ptr(), batch, t_in, f, p0.cin_pad,
                          p0.pad_left, buf.rows0 * p0.cin_pad * self.planes, self._stream())
-            self.cur = buf
-            self._src_keepalive = src
-            return buf
-        self._launch("pack_input", "sl_pack_input_ones", src.data_ptr(), buf.x0.data_ptr(), batch, t_in, f, p0.pad_left,
-                     p0.cin_pad, buf.rows0 * p0.cin_pad, p0.cin_pad - 1 if self._has_ones_input() else -1, self.dtype_code,
-                     self._stream())
+        else:
+            self._launch("pack_input", "sl_pack_input_ones", src.data_ptr(), buf.x0.data_ptr(), batch, t_in, f, p0.pad_left,
+                         p0.cin_pad, buf.rows0 * p0.cin_pad, p0.cin_pad - 1 if self._has_ones_input() else -1, self.dtype_code,
+                         self._stream())
         self.cur = buf
         self._src_keepalive = src
         return buf
@@ -677,22 +634,9 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             # the part geometries (and the workspace they may re-allocate) exist BEFORE a list is looked up or recorded: a
             # launch of the lower layers already in the list being recorded would keep a freed nt_ws pointer
             self._presize_parts(buf, ("fwd", "dgrad") if buf.bwd_ready else ("fwd",), split_ctc[1])
-        ops = self._launch_list(buf, key) if key is not None else None
-        if ops is not None:
-            self._replay(ops)
+        if self._run_recorded(buf, key, lambda: self._forward_eager(buf, rate, fuse_out, st, split_ctc)):
             buf.split_pending = split_ctc[1] if split_ctc is not None else 0
-            return buf.probs
-        record = key is not None and self.use_launch_lists and self.timeline is None and \
-            self.kernel_timeline is None and self._rec is None
-        if not record:
-            return self._forward_eager(buf, rate, fuse_out, st, split_ctc)
-        self._rec = []
-        try:
-            probs = self._forward_eager(buf, rate, fuse_out, st, split_ctc)
-            buf.launch_lists[key] = self._rec
-            return probs
-        finally:
-            self._rec = None
+        return buf.probs
 
     def _forward_eager(self, buf, rate, fuse_out, st, split_ctc=None):
         if self.planes > 1:
@@ -832,21 +776,20 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         if grad_scale is None:
             grad_scale = 1.0 / buf.batch
         l_max = buf.labels.shape[1]
-        if self.planes > 1:  # fp32 dL/dlogits into the staging buffer, then into the planes of g[last]
-            cp = self.plans[last].cout_pad
+        cp = self.plans[last].cout_pad
+        x3 = self.planes > 1
+        if x3:  # fp32 dL/dlogits into the staging buffer, then into the planes of g[last]
             buf.stage32[:buf.batch * buf.tt_pad * cp].zero_()  # (padded classes: the CTC kernel writes the k real ones)
-            self._launch("ctc", "sl_ctc_loss_grad", buf.probs.data_ptr(), buf.logq.data_ptr(), buf.labels.data_ptr(),
-                         buf.label_len.data_ptr(), buf.input_len.data_ptr(), buf.loss.data_ptr(), buf.stage32.data_ptr(),
-                         buf.batch, buf.t_out, self.grapheme_set_size, l_max, 0, cp, buf.tt_pad * cp, _lib.SL_F32,
-                         self.ctc_epsilon, grad_scale * self.g_scale, buf.ctc_ws.data_ptr(), buf.ctc_ws.numel(), self._stream())
+            grad, halo, batch_stride, code, scale = buf.stage32, 0, buf.tt_pad * cp, _lib.SL_F32, grad_scale * self.g_scale
+        else:
+            grad, halo, batch_stride, code, scale = buf.g[last], HALO, buf.rows * cp, self.dtype_code, grad_scale
+        self._launch("ctc", "sl_ctc_loss_grad", buf.probs.data_ptr(), buf.logq.data_ptr(), buf.labels.data_ptr(),
+                     buf.label_len.data_ptr(), buf.input_len.data_ptr(), buf.loss.data_ptr(), grad.data_ptr(),
+                     buf.batch, buf.t_out, self.grapheme_set_size, l_max, halo, cp, batch_stride, code,
+                     self.ctc_epsilon, scale, buf.ctc_ws.data_ptr(), buf.ctc_ws.numel(), self._stream())
+        if x3:
             self._launch("split:ctc", self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[last].data_ptr(), None, buf.batch, buf.t_out,
                          cp, buf.tt_pad * cp, HALO, buf.rows * cp * self.planes, 0, self._stream())
-            return buf.loss
-        self._launch("ctc", "sl_ctc_loss_grad", buf.probs.data_ptr(), buf.logq.data_ptr(), buf.labels.data_ptr(),
-                      buf.label_len.data_ptr(), buf.input_len.data_ptr(), buf.loss.data_ptr(), buf.g[last].data_ptr(),
-                      buf.batch, buf.t_out, self.grapheme_set_size, l_max, HALO, self.plans[last].cout_pad,
-                      buf.rows * self.plans[last].cout_pad, self.dtype_code, self.ctc_epsilon, grad_scale,
-                      buf.ctc_ws.data_ptr(), buf.ctc_ws.numel(), self._stream())
         return buf.loss
 
     def ctc_align(self, label_batch, label_lengths, prediction_lengths):
@@ -905,21 +848,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                                         tuple(sorted(self.nt_cfg.items())),
                                         buf.t_out if self.planes > 1 else None)  # (bf16x3 helpers take it by value)
         try:
-            ops = self._launch_list(buf, key) if key is not None else None
-            if ops is not None:
-                self._replay(ops, on_bucket_ready)
-                return
-            record = key is not None and self.use_launch_lists and self.timeline is None and \
-                self.kernel_timeline is None and self._rec is None
-            if not record:
-                self._backward_eager(buf, main, side, on_bucket_ready)
-                return
-            self._rec = []
-            try:
-                self._backward_eager(buf, main, side, on_bucket_ready)
-                buf.launch_lists[key] = self._rec
-            finally:
-                self._rec = None
+            self._run_recorded(buf, key, lambda: self._backward_eager(buf, main, side, on_bucket_ready), on_bucket_ready)
         except BaseException:
             if on_bucket_ready is not None and self.comm_cus:
                 # raised between setting and clearing the CU hint: the library's setting is process-wide state shared by
@@ -1078,15 +1007,9 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         return layers
 
     def _wgrad_multi_workspace_need(self, table, n_jobs):
-        """workspace of a balanced weight-gradient launch under EVERY sl_set_available_cus setting this engine launches
-        under: its segment count is 2 * CUs / tiles, so a table first used under the data-parallel CU hint would otherwise
-        get a workspace too small for a later step without the hint"""
-        need = 0
-        for hint in self.cu_hints():
-            self.lib.call("sl_set_available_cus", hint)
-            need = max(need, self.lib.raw("sl_conv1d_wgrad_multi_workspace_bytes")(table, n_jobs, self.dtype_code))
-        self.lib.call("sl_set_available_cus", self._cu_hint_active)
-        return need
+        """workspace of a balanced weight-gradient launch: its segment count is 2 * CUs / tiles (_max_over_cu_hints)"""
+        return self._max_over_cu_hints(
+            lambda: self.lib.raw("sl_conv1d_wgrad_multi_workspace_bytes")(table, n_jobs, self.dtype_code))
 
     def _wgrad_multi_table(self, buf, layers):
         """job table of a balanced weight-gradient launch over `layers`, built once per buffer set; makes sure the shared
@@ -1100,14 +1023,9 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                 x = (buf.x0_dropped if buf.dropped else buf.x0) if i == 0 else buf.y[i - 1]
                 dw, _ = self.layer_param_views(self.grads, self.plans[i])
                 job.x, job.g, job.dw = x.data_ptr(), buf.g[i].data_ptr(), dw.data_ptr()
-                for name, _ in ConvGeom._fields_:
-                    setattr(job.geom, name, getattr(buf.wgrad_geom[i], name))
+                job.geom.copy_from(buf.wgrad_geom[i])
             buf.multi_tables[key] = table
-            need = self._wgrad_multi_workspace_need(table, len(layers))
-            if buf.wgrad_multi_ws is None or buf.wgrad_multi_ws.numel() < need:
-                if buf.wgrad_multi_ws is not None:
-                    buf.launch_lists = {}  # (a recorded list may hold the pointer that is freed here)
-                buf.wgrad_multi_ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
+            buf.grow("wgrad_multi_ws", self._wgrad_multi_workspace_need(table, len(layers)), 16, first_drops=False)
         return table
 
     def _launch_wgrad_multi(self, buf, layers, st):
@@ -1132,32 +1050,29 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         ones_in = self._ones_input_layers(first)
         ones_db = set() if buf.dropped else set(ones_in)
         # data parallel: bucket b is complete once the weight gradient of its LOWEST layer is enqueued
-        bucket_at = {}
-        if on_bucket_ready is not None:
-            for b, (layers, _) in enumerate(self.bucket_plan()):
-                bucket_at[layers[0]] = (b, layers)
+        plan = self.bucket_plan() if on_bucket_ready is not None else []
+        bucket_at = {layers[0]: (b, layers) for b, (layers, _) in enumerate(plan)}
         side_busy = [False]
 
         def flush_bias_passes(pending):
             """sl_bias_grad passes of the layers in `pending` (their g is complete at this point of MAIN) on SIDE -- a lone
             small pass (the first layer's 8 MB, the only one left beside the ones channel) on MAIN: two hand-overs cost the
             main stream 6.5 us each (rocprof timeline), the pass itself 9"""
-            if len(pending) == 1 and buf.g[pending[0]].numel() * buf.g[pending[0]].element_size() <= (32 << 20) \
-                    and self.small_bias_pass_on_main:
-                j = pending[0]
+            def bias_pass(j, stream):
                 _, db_j = self.layer_param_views(self.grads, self.plans[j])
                 self._launch("bgrad:" + self.plans[j].spec.name, "sl_bias_grad", buf.g[j].data_ptr(), db_j.data_ptr(),
                              ctypes.byref(buf.wgrad_geom[j]), self.dtype_code, buf.bias_ws.data_ptr(),
-                             buf.bias_ws.numel(), main.cuda_stream)
+                             buf.bias_ws.numel(), stream.cuda_stream)
+
+            if len(pending) == 1 and buf.g[pending[0]].numel() * buf.g[pending[0]].element_size() <= (32 << 20) \
+                    and self.small_bias_pass_on_main:
+                bias_pass(pending[0], main)
                 del pending[:]
                 return
             self._hand_over(main, side)
             with torch.cuda.stream(side):
                 for j in pending:
-                    _, db_j = self.layer_param_views(self.grads, self.plans[j])
-                    self._launch("bgrad:" + self.plans[j].spec.name, "sl_bias_grad", buf.g[j].data_ptr(),
-                                 db_j.data_ptr(), ctypes.byref(buf.wgrad_geom[j]), self.dtype_code,
-                                 buf.bias_ws.data_ptr(), buf.bias_ws.numel(), side.cuda_stream)
+                    bias_pass(j, side)
             side_busy[0] = True
             del pending[:]
 
@@ -1197,9 +1112,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                 if rows:
                     self._bias_grads_from_wgrad(rows, bool(ones_db), main)
                 join_side()
-                on_bucket_ready(b)
-                if self._rec is not None:
-                    self._rec.append((2, b))
+                self._bucket_ready(on_bucket_ready, b)
                 if hint and b == 0:  # from here on communication kernels may own CUs: the choosers plan for the rest
                     self._eager_op(self._set_cu_hint, 256 - self.comm_cus)
             if i in dchain:
@@ -1219,9 +1132,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             self._front_backward(buf, main.cuda_stream)
             if on_bucket_ready is not None:  # the front layer's parameters: the last bucket of bucket_plan()
                 b = len(self.bucket_plan()) - 1
-                on_bucket_ready(b)
-                if self._rec is not None:
-                    self._rec.append((2, b))
+                self._bucket_ready(on_bucket_ready, b)
         if hint:
             self._eager_op(self._set_cu_hint, 0)
 
@@ -1275,20 +1186,17 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             chunk = layers[lo:lo + 16]
             table = self._adam_table(chunk)
             tag = "adam:{}..{}".format(self.all_plans[chunk[0]].spec.name, self.all_plans[chunk[-1]].spec.name)
+            what = (self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), table,
+                    len(chunk))
+            how = (self.adam_iterations, self.lr, self.beta_1, self.beta_2, self.adam_epsilon)
             if self.planes == 3 and self.x3_f16:
-                self._launch(tag, "sl_splitf16_adam_pack_layers", self.params.data_ptr(), self.grads.data_ptr(),
-                             self.adam_m.data_ptr(), self.adam_v.data_ptr(), table, len(chunk), self.adam_iterations,
-                             self.lr, self.beta_1, self.beta_2, self.adam_epsilon, self.w_scale, st)
+                self._launch(tag, "sl_splitf16_adam_pack_layers", *what, *how, self.w_scale, st)
             elif self.planes == 3:  # bf16x3: the [w_hi | w_hi | w_lo] operand rows are rewritten in the same pass
-                self._launch(tag, "sl_split3_adam_pack_layers", self.params.data_ptr(), self.grads.data_ptr(),
-                             self.adam_m.data_ptr(), self.adam_v.data_ptr(), table, len(chunk), self.adam_iterations,
-                             self.lr, self.beta_1, self.beta_2, self.adam_epsilon, st)
+                self._launch(tag, "sl_split3_adam_pack_layers", *what, *how, st)
                 if 0 in chunk and self.w_dgrad[0] is not None:
                     self._pack_pair_dgrad_x3(st)
             else:
-                self._launch(tag, "sl_adam_pack_layers", self.params.data_ptr(), self.grads.data_ptr(),
-                             self.adam_m.data_ptr(), self.adam_v.data_ptr(), table, len(chunk), self.dtype_code,
-                             self.adam_iterations, self.lr, self.beta_1, self.beta_2, self.adam_epsilon, st)
+                self._launch(tag, "sl_adam_pack_layers", *what, self.dtype_code, *how, st)
 
     def train_step(self, input_batch, label_batch, label_lengths, prediction_lengths, reducer=None):
         """One full optimisation step (forward, CTC, backward, [gradient all-reduce], Adam, weight repack).

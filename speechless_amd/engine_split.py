@@ -5,7 +5,6 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import ConvGeom
 from .plan import HALO
 
 
@@ -74,20 +73,12 @@ class SplitTopMixin:
         g = buf.half_geoms.get((kind, i, count))
         if g is None:
             src = {"fwd": buf.fwd_geom, "dgrad": buf.dgrad_geom, "wgrad": buf.wgrad_geom}[kind][i]
-            g = ConvGeom()
-            for name, _ in ConvGeom._fields_:
-                setattr(g, name, getattr(src, name))
+            g = src.copy()
             g.batch = count
             buf.half_geoms[(kind, i, count)] = g
             if kind in ("fwd", "dgrad"):  # (a part of the batch may pick more K splits: make sure the workspace covers it)
-                need = 0
-                for hint in self.cu_hints():
-                    self.lib.call("sl_set_available_cus", hint)
-                    need = max(need, self.lib.raw("sl_conv1d_nt_workspace_bytes")(ctypes.byref(g), self.dtype_code, 0))
-                self.lib.call("sl_set_available_cus", self._cu_hint_active)
-                if buf.nt_ws is None or buf.nt_ws.numel() < need:
-                    buf.nt_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
-                    buf.launch_lists = {}
+                buf.grow("nt_ws", self._max_over_cu_hints(
+                    lambda: self.lib.raw("sl_conv1d_nt_workspace_bytes")(ctypes.byref(g), self.dtype_code, 0)))
         return g
 
     @staticmethod

@@ -5,7 +5,6 @@ import ctypes
 import torch
 
 from . import _lib
-from ._lib import ConvGeom
 from .plan import HALO
 
 
@@ -17,10 +16,7 @@ class X3Mixin:
     def _pack_weights_x3(self, tag, w_master, w_fwd, w_dgrad, k, cin, cout, st):
         """both operand copies [w_hi | w_hi | w_lo] of one layer from its fp32 master (f16x3: of w_scale * w)"""
         args = (w_master.data_ptr(), w_fwd.data_ptr(), w_dgrad.data_ptr() if w_dgrad is not None else None, k, cin, cout)
-        if self.x3_f16:
-            self._launch(tag, "sl_splitf16_pack_weights", *args, self.w_scale, st)
-        else:
-            self._launch(tag, "sl_split3_pack_weights", *args, st)
+        self._launch(tag, self._x3("sl_split3_pack_weights"), *args, *((self.w_scale,) if self.x3_f16 else ()), st)
 
     def _repack_weights_x3(self):
         """bf16x3 operand copies: rows [w_hi | w_hi | w_lo] in both operand layouts, w_hi = bf16(w), w_lo = bf16(w - w_hi),
@@ -56,9 +52,7 @@ class X3Mixin:
         g = buf.plane_geoms.get((kind, i))
         if g is None:
             src = (buf.fwd_geom if kind == "fwd" else buf.dgrad_geom)[i]
-            g = ConvGeom()
-            for name, _ in ConvGeom._fields_:
-                setattr(g, name, getattr(src, name))
+            g = src.copy()
             g.y_row0, g.y_row_stride, g.y_batch_stride = HALO, self.planes * channels, buf.rows * channels * self.planes
             buf.plane_geoms[(kind, i)] = g
         return g
@@ -133,10 +127,8 @@ class X3Mixin:
         ones_in = self._ones_input_layers(first)
         ones_db = set() if buf.dropped else set(ones_in)  # rows that hold a bias gradient (else: only to be zeroed)
         main = torch.cuda.current_stream(self.device)
-        bucket_at = {}
-        if on_bucket_ready is not None:
-            for b, (layers, _) in enumerate(self.bucket_plan()):
-                bucket_at[layers[0]] = (b, layers)
+        plan = self.bucket_plan() if on_bucket_ready is not None else []
+        bucket_at = {layers[0]: (b, layers) for b, (layers, _) in enumerate(plan)}
         # the runs of identical layers (inner_conv_1..7): their 2 x 7 partial weight gradients (x planes against g_hi, against
         # g_lo) in ONE balanced launch (sl_conv1d_wgrad_multi, a job per partial) at the lowest layer of the run -- they
         # were 14 launches of 31 us + their reductions, 0.6 ms of the 6.8 ms step
@@ -181,33 +173,20 @@ class X3Mixin:
                     self._x3_bias_ws = torch.empty((self.lib.raw("sl_split3_bias_grad_workspace_bytes")(
                         max(q.cout_pad for q in self.plans)),), dtype=torch.uint8, device=self.device)
                 args = (buf.g[i].data_ptr(), db.data_ptr(), buf.batch, buf.t_out, p.cout_pad, HALO, buf.rows * p.cout_pad * pl)
-                if self.x3_f16:
-                    self._launch("bgrad:" + p.spec.name, "sl_splitf16_bias_grad", *args, 1.0 / self.g_scale,
-                                 self._x3_bias_ws.data_ptr(), self._x3_bias_ws.numel(), st)
-                else:
-                    self._launch("bgrad:" + p.spec.name, "sl_split3_bias_grad", *args, self._x3_bias_ws.data_ptr(),
-                                 self._x3_bias_ws.numel(), st)
+                scale = (1.0 / self.g_scale,) if self.x3_f16 else ()  # (f16x3: the gradient planes are stored scaled)
+                self._launch("bgrad:" + p.spec.name, self._x3("sl_split3_bias_grad"), *args, *scale,
+                             self._x3_bias_ws.data_ptr(), self._x3_bias_ws.numel(), st)
             if i in bucket_at:
                 b, layers = bucket_at[i]
                 rows = [j for j in layers if j in ones_in]
                 if rows:
                     self._bias_grads_from_wgrad(rows, bool(ones_db), main)
-                on_bucket_ready(b)
-                if self._rec is not None:
-                    self._rec.append((2, b))
+                self._bucket_ready(on_bucket_ready, b)
             dropped_in = buf.dropped and i in self._dropout_layers()  # a Dropout sits between y[i - 1] and layer i
-            if i > first and self.specs[i - 1].activation == "elu" and dropped_in:
-                # a stored zero is ambiguous behind an ELU: plain input gradient, then both factors of the chain rule with the
-                # keep decisions recomputed from the step's seed (cf. sl_elu_dropout_backward)
-                self._launch("dgrad:" + p.spec.name, "sl_conv1d_nt", buf.g[i].data_ptr(), self.w_dgrad[i].data_ptr(), None,
-                             None, buf.stage32.data_ptr(), ctypes.byref(buf.dgrad_geom[i]), _lib.EPI_NONE, self.dtype_code, 1,
-                             self.nt_cfg.get(("dgrad", p.spec.name), 0), buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
-                self._launch("split:dgrad:" + p.spec.name, self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[i - 1].data_ptr(),
-                             None, buf.batch, buf.t_out, p.cin_pad, buf.tt_pad * p.cin_pad, HALO,
-                             buf.rows * p.cin_pad * pl, 0, st)
-                self._dropout_x3("dropout_elu_bwd:" + p.spec.name, buf.g[i - 1], buf.g[i - 1], buf.y[i - 1], p.cin_pad, 2,
-                                 buf.dropout_seed0 + i, st)
-                continue
+            elu = i > first and self.specs[i - 1].activation == "elu"
+            # a stored zero is ambiguous behind an ELU: plain input gradient (no mask), then both factors of the chain rule with
+            # the keep decisions recomputed from the step's seed (cf. sl_elu_dropout_backward)
+            elu_dropped = elu and dropped_in
             if i > first and self.specs[i - 1].activation == "relu" and self.x3_fused_epilogue:
                 # the ReLU mask (the hi plane of the stored activation) and the split into planes in the NT kernel's epilogue
                 self._launch("dgrad:" + p.spec.name, "sl_conv1d_nt", buf.g[i].data_ptr(), self.w_dgrad[i].data_ptr(), None,
@@ -219,9 +198,12 @@ class X3Mixin:
                              None, buf.stage32.data_ptr(), ctypes.byref(buf.dgrad_geom[i]), _lib.EPI_NONE, self.dtype_code, 1,
                              self.nt_cfg.get(("dgrad", p.spec.name), 0), buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
                 self._launch("split:dgrad:" + p.spec.name, self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[i - 1].data_ptr(),
-                             buf.y[i - 1].data_ptr(), buf.batch, buf.t_out, p.cin_pad, buf.tt_pad * p.cin_pad, HALO,
-                             buf.rows * p.cin_pad * pl, 4 if self.specs[i - 1].activation == "elu" else 3, st)
-            if i > first and dropped_in:
+                             None if elu_dropped else buf.y[i - 1].data_ptr(), buf.batch, buf.t_out, p.cin_pad,
+                             buf.tt_pad * p.cin_pad, HALO, buf.rows * p.cin_pad * pl, 0 if elu_dropped else (4 if elu else 3), st)
+            if elu_dropped:
+                self._dropout_x3("dropout_elu_bwd:" + p.spec.name, buf.g[i - 1], buf.g[i - 1], buf.y[i - 1], p.cin_pad, 2,
+                                 buf.dropout_seed0 + i, st)
+            elif i > first and dropped_in:
                 # the ReLU mask (stored activation > 0) already applied the keep mask: the stored activation is the
                 # post-dropout one; what is left of d dropout / dx is the factor 1 / (1 - rate)
                 self._dropout_x3("dropout_scale:" + p.spec.name, buf.g[i - 1], buf.g[i - 1], None, p.cin_pad, 1, 0, st)
@@ -231,9 +213,7 @@ class X3Mixin:
             self._front_backward(buf, st)
             if on_bucket_ready is not None:  # the front layer's parameters: the last bucket of bucket_plan()
                 b = len(self.bucket_plan()) - 1
-                on_bucket_ready(b)
-                if self._rec is not None:
-                    self._rec.append((2, b))
+                self._bucket_ready(on_bucket_ready, b)
 
     def _wgrad_multi_layers_x3(self, first):
         """bf16x3: no launch writes the weight gradients of the striding layer AND of a run (bucket_plan() merges nothing)"""
@@ -282,8 +262,7 @@ class X3Mixin:
                                                     (buf.g[i].data_ptr() + self.plans[i].cout_pad * 2, rb,
                                                      buf.wgrad_geom_b[i]))):
                     job.x, job.g, job.dw = x.data_ptr(), g_ptr, out.data_ptr()
-                    for name, _ in ConvGeom._fields_:
-                        setattr(job.geom, name, getattr(geom, name))
+                    job.geom.copy_from(geom)
             need = self._wgrad_multi_workspace_need(table, len(table))
             ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
             entry = buf.multi_tables[key] = (table, parts, scratch, ws)

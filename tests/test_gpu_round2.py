@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import w2l_oracle as o
+from speechless_amd.launch_list import entry_points
 from test_gpu_parity import (_report, layer_activation, make_case, make_engine, rel_l2, run_loss_and_grads,
                              synthetic_examples, weights64)
 
@@ -756,7 +757,7 @@ def test_fused_run_of_inner_layers_against_the_single_launches():
             eng = make_engine(case, "bf16")
             eng.use_chain = chain
             losses, grads = run_loss_and_grads(eng, case)
-            tags = [op[3] for ops in eng.cur.launch_lists.values() for op in ops if op[0] == 0]
+            tags = [name for ops in eng.cur.launch_lists.values() for name, _ in entry_points(ops)]
             assert (tags.count("sl_conv1d_chain") == 2) == chain and ("sl_conv1d_chain" in tags) == chain
             res[chain] = (eng, losses, grads)
         (ea, la, ga), (eb, lb, gb) = res[True], res[False]
@@ -809,7 +810,7 @@ def test_bias_gradients_from_the_ones_channel(dropout, dtype):
         eng.backward()
         torch.cuda.synchronize()
         grads = eng.get_gradients()
-        tags = [op[3] for ops in eng.cur.launch_lists.values() for op in ops if op[0] == 0] if not dropout else []
+        tags = [name for ops in eng.cur.launch_lists.values() for name, _ in entry_points(ops)] if not dropout else []
         if not dropout:
             assert tags.count("sl_bias_grad") == (1 if ones else len(eng.plans))
             assert tags.count("sl_bias_grad_from_wgrad") == (1 if ones else 0)
@@ -858,7 +859,7 @@ def test_fast_paths_against_the_plain_launches_over_odd_shapes(b, t, frozen):
     finally:
         _lib.lib().call("sl_ctc_select", 0)
     (la, ga, ea), (lb, gb, _) = res[True], res[False]
-    tags = [op[3] for ops in ea.cur.launch_lists.values() for op in ops if op[0] == 0]
+    tags = [name for ops in ea.cur.launch_lists.values() for name, _ in entry_points(ops)]
     assert "sl_conv1d_chain" in tags and "sl_bias_grad_from_wgrad" in tags
     np.testing.assert_allclose(la, lb, rtol=2e-3)  # (bf16 activations through two different accumulation orders)
     for i in range(frozen, len(ga)):

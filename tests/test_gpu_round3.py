@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from oracle import w2l_oracle as o
+from speechless_amd.launch_list import entry_points
 from test_gpu_parity import _report, make_case, make_engine, rel_l2, run_loss_and_grads
 
 pytestmark = pytest.mark.gpu
@@ -203,7 +204,7 @@ def test_fused_inner_layers_with_48_frame_tiles_are_bit_identical(hip_lib, b, t)
             hip_lib.call("sl_conv1d_chain_select", rows)
             eng = make_engine(case, "bf16")
             losses, grads = run_loss_and_grads(eng, case)
-            tags = [op[3] for ops in eng.cur.launch_lists.values() for op in ops if op[0] == 0]
+            tags = [name for ops in eng.cur.launch_lists.values() for name, _ in entry_points(ops)]
             assert tags.count("sl_conv1d_chain") == 2
             res[rows] = (losses, [y.clone() for y in eng.cur.y[:8]], [g.clone() for g in eng.cur.g[:8]], grads)
             torch.cuda.synchronize()

@@ -62,7 +62,7 @@ def main():
         for value in (True, False):
             setattr(eng, args.attr, value)
             for buf in eng._buffers.values():  # (attributes that change the launch sequence: lists and job tables are rebuilt)
-                buf.launch_lists, buf.multi_tables = {}, {}
+                buf.invalidate()
             res[value].append(timed())
     for value in (True, False):
         v = res[value]
