@@ -71,11 +71,6 @@ extern "C" int sl_conv1d_nt(const void* x, const void* w, const float* bias, con
     return SL_ERR_INVALID_ARGUMENT;
 }
 
-bool output_softmax_supported(const sl_conv_geom* g, int k);
-int output_softmax_bf16(const void* x, const void* w, const float* bias, float* probs, float* logq, float* logits,
-                        const sl_conv_geom* g, int k, int logit_stride, long logit_batch_stride, float eps, hipStream_t s);
-
-int output_softmax_select(int variant);
 extern "C" int sl_output_softmax_select(int variant) {
     SL_CHECK_ARG(variant >= 0 && variant <= 2, "sl_output_softmax_select: variant %d outside 0..2", variant);
     return output_softmax_select(variant);
@@ -98,7 +93,6 @@ extern "C" int sl_output_softmax(const void* x, const void* w, const float* bias
                                (hipStream_t)stream);
 }
 
-int conv_chain_select(int rows);
 extern "C" int sl_conv1d_chain_select(int tile_rows) {
     SL_CHECK_ARG(tile_rows == 0 || tile_rows == 48 || tile_rows == 64, "sl_conv1d_chain_select: tile_rows must be 0, 48 or 64");
     return conv_chain_select(tile_rows);

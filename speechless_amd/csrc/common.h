@@ -136,6 +136,11 @@ int conv_nt_f32(const void* x, const void* w, const float* bias, const void* mas
 bool conv_chain_bf16_supported(const sl_conv_geom* g, int n_layers);
 int conv_chain_bf16(const void* x, void* const* ys, const void* const* ws, const float* const* biases,
                     const void* const* masks, const sl_conv_geom* g, int n_layers, int epilogue, hipStream_t s);
+int conv_chain_select(int rows);
+bool output_softmax_supported(const sl_conv_geom* g, int k);
+int output_softmax_select(int variant);
+int output_softmax_bf16(const void* x, const void* w, const float* bias, float* probs, float* logq, float* logits,
+                        const sl_conv_geom* g, int k, int logit_stride, long logit_batch_stride, float eps, hipStream_t s);
 int wgrad_split_count(const sl_conv_geom* g, int tile);
 int wgrad_tn_bf16(const void* x, const void* gr, float* dw, const sl_conv_geom* g, int cfg, int groups, long x_gs,
                   long g_gs, long dw_gs, float* ws, size_t ws_bytes, hipStream_t s);

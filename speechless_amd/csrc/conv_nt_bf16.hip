@@ -34,7 +34,13 @@
 //   * conv_nt_slab_bf16_kernel (cfg bit 29) is the chunk-major variant that keeps the activation rows of all taps in LDS.
 //   * conv_nt_ks2_bf16_kernel (cfg it = 5) is the 128x128 tile with eight waves, the two waves of a SIMD splitting the k-halves.
 //   The library's measured table (auto_cfg) picks shape, flavour and kernel per launch; tools/tune_kernels.py sweeps them.
+//
+// Host side: NT_VARIANTS lists every compiled tile variant once, as (kernel kind, m32, it, wm, wn, ring slots, pipelined,
+// interleaved) plus its launcher; valid_cfg() looks a decoded cfg word up in that list and applies the geometry rules, and
+// conv_nt_bf16() launches what it found.  The LDS-DMA / fragment-read helpers live in lds_dma.h (shared with the fused output
+// layer, output_softmax_bf16.hip).  This file is compiled twice (build.py: -DSL_ELEM_F16 for the fp16 operands of f16x3).
 #include "common.h"
+#include "lds_dma.h"
 
 #include <type_traits>
 
@@ -66,53 +72,6 @@ struct NtArgs {
     int gm;  // tile raster: blocks of (all n_tiles) x gm m-tiles are numbered consecutively
 };
 
-__device__ __forceinline__ void glds16(const __bf16* gsrc, char* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((const SL_GLOBAL void*)gsrc, (SL_LDS void*)lds_wave_base, 16, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// LDS fragment reads the compiler does not track (it answers every LDS dependency in these kernels with lgkmcnt(0),
-// because the LDS-DMA loads leave a "flat access pending" mark): the hand-counted wait below releases the registers.
-template <int OFF>
-__device__ __forceinline__ void ds_read128(bf16x8& dst, unsigned addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF));
-}
-template <int I, int N, int STRIDE>
-struct DsReadRun {
-    static __device__ __forceinline__ void go(bf16x8 (&f)[N], unsigned addr) {
-        ds_read128<I * STRIDE>(f[I], addr);
-        DsReadRun<I + 1, N, STRIDE>::go(f, addr);
-    }
-};
-template <int N, int STRIDE>
-struct DsReadRun<N, N, STRIDE> {
-    static __device__ __forceinline__ void go(bf16x8 (&)[N], unsigned) {}
-};
-// s_waitcnt lgkmcnt(CNT) that the MFMAs consuming these fragments cannot be hoisted above
-template <int CNT>
-__device__ __forceinline__ void wait_frags(bf16x8 (&a)[4], bf16x8 (&b)[4]) {
-    asm volatile("s_waitcnt lgkmcnt(%8)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])
-                 : "n"(CNT));
-}
-template <int CNT>
-__device__ __forceinline__ void wait_frags(bf16x8 (&a)[4], bf16x8 (&b)[8]) {
-    asm volatile("s_waitcnt lgkmcnt(%12)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]),
-                   "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7])
-                 : "n"(CNT));
-}
-template <int CNT>
-__device__ __forceinline__ void wait_frags(bf16x8 (&a)[4], bf16x8 (&b)[2]) {
-    asm volatile("s_waitcnt lgkmcnt(%6)"
-                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1])
-                 : "n"(CNT));
-}
-
 // fp32 -> bf16 in the main epilogue: v_cvt_pk_bf16_f32 (round to nearest even like the software form, which costs five VALU
 // instructions per value: 640 of a wave's epilogue at the 256 x 256 tile)
 #if defined(SL_NT_SOFT_PACK)
@@ -122,8 +81,6 @@ __device__ __forceinline__ void wait_frags(bf16x8 (&a)[4], bf16x8 (&b)[2]) {
 #endif
 enum { MODE_PARTIAL = 100 };  // besides the SL_EPI_* values: raw fp32 accumulators to the split-K workspace
 
-__device__ __forceinline__ float bf16_lo(unsigned int u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float bf16_hi(unsigned int u) { return __uint_as_float(u & 0xFFFF0000u); }
 // ELU: y = z > 0 ? z : exp(z) - 1;   dy/dz expressed through the stored output: y > 0 ? 1 : y + 1
 __device__ __forceinline__ float elu_f(float z) { return z > 0.f ? z : expm1f(z); }
 __device__ __forceinline__ float elu_grad_from_y(float y) { return y > 0.f ? 1.f : y + 1.f; }
@@ -299,13 +256,10 @@ struct IlvPhase<IT, G, NQ, NQ, RPG> {
                                                bf16x8 (&)[IT], unsigned, unsigned, const Hook&) {}
 };
 
-// STAGES_P: low 3 bits = ring slots, bit 3 = register-pipelined main loop (fragments of the next tile's first half are
-// read from LDS while the MFMAs of the current tile's second half run, see the loop)
-template <bool M32, int IT, int WM, int WN, int STAGES_P, int MODE, bool OUT_F32>
+// STAGES = ring slots; PIPE = register-pipelined main loop (fragments of the next tile's first half are read from LDS while
+// the MFMAs of the current tile's second half run, see the loop); ILV = hand-interleaved variant of the pipelined loop
+template <bool M32, int IT, int WM, int WN, int STAGES, bool PIPE, bool ILV, int MODE, bool OUT_F32>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt_bf16_kernel(NtArgs a) {
-    constexpr int STAGES = STAGES_P & 7;
-    constexpr bool PIPE = (STAGES_P & 8) != 0;
-    constexpr bool ILV = (STAGES_P & 16) != 0;  // hand-interleaved variant of the pipelined loop
     static_assert(STAGES >= 2, "ring too shallow");
     static_assert(!ILV || (PIPE && !M32), "the interleaved schedule is a variant of the register-pipelined 16x16 loop");
     constexpr int NW = WM * WN;
@@ -737,10 +691,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
 //   vmcnt bookkeeping: the slab of chunk c+1 is issued in step (c, tap 0) BEFORE that step's weight tile, so it is older
 //   than every weight tile of chunk c+1 (needs taps >= STAGES) and only the steps with tap in [1, STAGES-2] see it among
 //   the instructions that may stay in flight.
-template <int IT, int WM, int WN, int STAGES_P, int MODE, bool OUT_F32, bool ILV>
+template <int IT, int WM, int WN, int STAGES, bool PIPE, bool ILV, int MODE, bool OUT_F32>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt_slab_bf16_kernel(NtArgs a) {
-    constexpr int STAGES = STAGES_P & 7;
-    constexpr bool PIPE = (STAGES_P & 8) != 0;
     static_assert(!ILV || PIPE, "the interleaved schedule is a variant of the register-pipelined loop");
     static_assert(STAGES >= 2, "ring too shallow");
     constexpr int NW = WM * WN;
@@ -1282,277 +1234,6 @@ __global__ __launch_bounds__(512, 2) void conv_nt_ks2_bf16_kernel(NtArgs a) {
     }
 }
 
-// Softmax tail shared by the two fused output-layer kernels.  Lane (g, i) holds, for time row t0 + wave * 16 + i, the logits
-// of classes tile * 16 + 4 g + r in acc[tile][r] (bias not yet added).
-__device__ __forceinline__ void output_softmax_finish(const f32x4 (&acc)[2], const float* __restrict__ bias,
-                                                      float* __restrict__ probs, float* __restrict__ logq,
-                                                      float* __restrict__ logits, int b, int t0, int wave, int lane, int g,
-                                                      int t_out, int k, int logit_stride, long logit_batch_stride,
-                                                      float eps) {
-    // ---- lane (g, i): time row t0 + wave*16 + i, classes tile*16 + 4g + r.  Softmax over the k valid classes of the row:
-    // 8 values here, the rest in the three lanes that differ in g (lane ^ 16, lane ^ 32).
-    const int t = t0 + wave * 16 + (lane & 15);
-    float z[8];
-    float m = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int cls = j * 16 + 4 * g + r;
-            z[j * 4 + r] = cls < k ? acc[j][r] + bias[cls] : -INFINITY;
-            m = fmaxf(m, z[j * 4 + r]);
-        }
-    m = fmaxf(m, __shfl_xor(m, 16));
-    m = fmaxf(m, __shfl_xor(m, 32));
-    float e[8], sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        e[i] = z[i] == -INFINITY ? 0.f : expf(z[i] - m);
-        sum += e[i];
-    }
-    sum += __shfl_xor(sum, 16);
-    sum += __shfl_xor(sum, 32);
-    // q = (p + eps) / sum_j (p_j + eps), computed the way TF does: log-softmax of u = log(p + eps)   (sl_softmax_logq)
-    float u[8], um = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        e[i] = e[i] / sum;
-        u[i] = z[i] == -INFINITY ? -INFINITY : logf(e[i] + eps);
-        um = fmaxf(um, u[i]);
-    }
-    um = fmaxf(um, __shfl_xor(um, 16));
-    um = fmaxf(um, __shfl_xor(um, 32));
-    float usum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) usum += u[i] == -INFINITY ? 0.f : expf(u[i] - um);
-    usum += __shfl_xor(usum, 16);
-    usum += __shfl_xor(usum, 32);
-    const float lz = um + logf(usum);
-    if (t < t_out) {
-        const long f = (long)b * t_out + t;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int cls = j * 16 + 4 * g + r;
-                if (cls < k) {
-                    probs[f * k + cls] = e[j * 4 + r];
-                    logq[f * k + cls] = u[j * 4 + r] - lz;
-                    if (logits) logits[(long)b * logit_batch_stride + (long)t * logit_stride + cls] = z[j * 4 + r];
-                }
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Output layer: 1x1 convolution onto k <= 32 classes fused with the softmax and the log(p + eps) re-normalisation that
-// sl_softmax_logq computes.  As an NT launch this layer is a 128x128 tile of which three quarters is channel padding
-// (34 us, and another launch for the softmax); what it really needs is to stream its input once.  Here a work-group owns
-// 64 time rows and ALL classes: the whole weight matrix (32 x cin bf16, 128 KiB at cin = 2048, rows padded by 16 B
-// against bank conflicts) sits in LDS, the activation rows come through a 3-slot LDS-DMA ring (8 KiB per 64-channel
-// step), each of the four waves multiplies its 16 rows by the 32 classes (2 MFMA tiles x 2 k-halves per step) and ends
-// with the 32 logits of a time row in four lanes -> softmax by two butterfly steps, no logits round trip through HBM.
-// Summation order over the input channels is the NT kernels' (64-channel steps, two 32-deep MFMAs each).
-template <int SLOTS>
-__global__ __launch_bounds__(256, 1) void output_softmax_kernel(const __bf16* __restrict__ x, const __bf16* __restrict__ w,
-                                                                const float* __restrict__ bias, float* __restrict__ probs,
-                                                                float* __restrict__ logq, float* __restrict__ logits,
-                                                                int batch, int t_out, int t_tiles, int cin, int w_rs,
-                                                                int x_row0, int x_rs, long x_bs, int k, int logit_stride,
-                                                                long logit_batch_stride, float eps) {
-    constexpr int BM = 64, SLOT_BYTES = BM * 128, XPW = 2;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wrow = cin * 2 + 16;  // LDS bytes per weight row
-    const int wrows = k < 32 ? k : 32;  // weight rows kept in LDS (the MFMA rows behind them read ring bytes: classes >= k are masked)
-    const int ring_off = (wrows * wrow + 127) & ~127;  // the k-half XOR of the fragment addresses needs a 128-byte base
-    char* ring = smem + ring_off;
-    const int b = blockIdx.x / t_tiles;
-    const int t0 = (blockIdx.x - b * t_tiles) * BM;
-    const int nsteps = cin / BK;
-
-    const __bf16* xbase = x + (long)b * x_bs + (long)(x_row0 + t0) * x_rs;
-    int xoff[XPW];
-#pragma unroll
-    for (int q = 0; q < XPW; ++q) {
-        const int row = (wave * XPW + q) * 8 + (lane >> 3);
-        xoff[q] = row * x_rs + (((lane & 7) ^ (lane >> 3)) << 3);
-    }
-    auto request = [&](int step, int slot) {
-#pragma unroll
-        for (int q = 0; q < XPW; ++q)
-            glds16(xbase + step * BK + xoff[q], ring + slot * SLOT_BYTES + (wave * XPW + q) * 1024);
-    };
-    const int g = lane >> 4;
-    const unsigned lds0 = (unsigned)(size_t)smem;
-    const unsigned boff = lds0 + ring_off + (wave * 16 + (lane & 15)) * 128 + ((g ^ (lane & 7)) << 4);
-    const unsigned aoff = lds0 + (lane & 15) * wrow + g * 16;  // + tile * 16 * wrow + step * 128 + k-half * 64
-
-    f32x4 acc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int i = 0; i < SLOTS - 1; ++i)
-        if (i < nsteps) request(i, i);
-    // ---- the weight matrix: 32 rows of cin bf16.  Rows of whole KiB go by LDS-DMA (one KiB per wave instruction, all
-    // in flight at once); other widths through registers, 16 bytes per thread and trip.
-    if ((cin & 511) == 0) {
-        const int chunks = cin / 512;  // KiB per row
-        for (int i = wave; i < wrows * chunks; i += 4) {
-            const int r = i / chunks, c = i - r * chunks;
-            glds16(w + (long)r * w_rs + c * 512 + lane * 8, smem + r * wrow + c * 1024);
-        }
-    } else {
-        const int per_row = cin / 8;  // 16-byte pieces per row
-        for (int i = tid; i < wrows * per_row; i += 256) {
-            const int r = i / per_row, c = i - r * per_row;
-            *(u32x4*)(smem + r * wrow + c * 16) = *(const u32x4*)(w + (long)r * w_rs + c * 8);
-        }
-    }
-    wait_vmcnt<0>();  // weights (and the first activation tiles): the counted waits below start from zero in flight
-    __syncthreads();
-    int slot = 0;
-    for (int c = 0; c < nsteps; ++c) {
-        if (c + SLOTS - 2 < nsteps)
-            wait_vmcnt<XPW*(SLOTS - 2)>();  // tile c has landed, the SLOTS-2 younger ones may still be in flight
-        else
-            wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();  // ... everybody's part of it, and everybody is done reading tile c-1
-        asm volatile("" ::: "memory");
-        if (c + SLOTS - 1 < nsteps) request(c + SLOTS - 1, slot == 0 ? SLOTS - 1 : slot - 1);
-        bf16x8 af[4], bfr[2];
-        const unsigned a_addr = aoff + c * 128;
-        ds_read128<0>(af[0], a_addr);
-        ds_read128<64>(af[1], a_addr);
-        ds_read128<0>(af[2], a_addr + 16 * wrow);
-        ds_read128<64>(af[3], a_addr + 16 * wrow);
-        const unsigned b_addr = boff + slot * SLOT_BYTES;
-        ds_read128<0>(bfr[0], b_addr);
-        ds_read128<0>(bfr[1], b_addr ^ 64);
-        wait_frags<0>(af, bfr);
-        acc[0] = SL_MFMA16(af[0], bfr[0], acc[0]);
-        acc[1] = SL_MFMA16(af[2], bfr[0], acc[1]);
-        acc[0] = SL_MFMA16(af[1], bfr[1], acc[0]);
-        acc[1] = SL_MFMA16(af[3], bfr[1], acc[1]);
-        slot = (slot + 1 == SLOTS) ? 0 : slot + 1;
-    }
-
-    output_softmax_finish(acc, bias, probs, logq, logits, b, t0, wave, lane, g, t_out, k, logit_stride, logit_batch_stride, eps);
-}
-
-// The same layer with the WEIGHTS IN REGISTERS (round 3).  With the weight matrix in LDS (119 KiB of 160) the ring above is
-// five 8 KiB slots -- 32 KiB in flight per CU, one barrier per 64-channel step: 22.7 us for the 67 MB of config 3 = 3 TB/s.
-// Here the contraction is split over the four waves of the work-group: wave w owns input channels [w cin/4, (w+1) cin/4) of
-// all 64 time rows, its slice of the weights (32 classes x cin/4 bf16 = 32 KiB at cin = 2048) sits in 128 VGPRs as MFMA
-// fragments for the whole launch, and the wave streams exactly the activation bytes it consumes itself through its own
-// ring of four 8 KiB slots (LDS-DMA, counted vmcnt): no barrier in the loop, 128 KiB in flight per CU.  The four partial
-// 64 x 32 logit tiles meet once, in LDS, summed in wave order (deterministic); wave w then finishes rows 16 w .. 16 w + 15.
-// NSTEP = cin / 256 (64-channel steps per wave).
-template <int NSTEP>
-__global__ __launch_bounds__(256, 1) void output_softmax_regw_kernel(const __bf16* __restrict__ x,
-                                                                     const __bf16* __restrict__ w,
-                                                                     const float* __restrict__ bias,
-                                                                     float* __restrict__ probs, float* __restrict__ logq,
-                                                                     float* __restrict__ logits, int batch, int t_out,
-                                                                     int t_tiles, int w_rs, int x_row0, int x_rs, long x_bs,
-                                                                     int k, int logit_stride, long logit_batch_stride,
-                                                                     float eps) {
-    constexpr int BM = 64, SLOT_BYTES = BM * 128, SLOTS = NSTEP < 4 ? NSTEP : 4, DPS = 8;  // DMA instructions per step
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = lane >> 4;
-    const int b = blockIdx.x / t_tiles;
-    const int t0 = (blockIdx.x - b * t_tiles) * BM;
-    const int ch0 = wave * (NSTEP * 64);  // this wave's channel slice
-    char* ring = smem + wave * (SLOTS * SLOT_BYTES);
-    const __bf16* xbase = x + (long)b * x_bs + (long)(x_row0 + t0) * x_rs + ch0;
-    // DMA: instruction q of a step moves rows 8 q .. 8 q + 7 (lane >> 3 = row, lane & 7 = 16-byte slot holding logical
-    // piece (lane & 7) ^ row: the fragment reads below find piece p of row r at slot p ^ (r & 7))
-    const int xoff0 = (lane >> 3) * x_rs + (((lane & 7) ^ (lane >> 3)) << 3);
-    auto request = [&](int step, int slot) {
-#pragma unroll
-        for (int q = 0; q < DPS; ++q)
-            glds16(xbase + step * 64 + q * 8 * x_rs + xoff0, ring + slot * SLOT_BYTES + q * 1024);
-    };
-#pragma unroll
-    for (int i = 0; i < SLOTS; ++i) request(i, i);
-    // weight fragments: class tile j, 32-channel piece q of the slice: lane holds w[16 j + (lane & 15)][ch0 + 32 q + 8 g ..+8]
-    bf16x8 wf[2][2 * NSTEP];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int cls = j * 16 + (lane & 15);
-        const __bf16* wr = w + (long)(cls < k ? cls : 0) * w_rs + ch0 + g * 8;
-#pragma unroll
-        for (int q = 0; q < 2 * NSTEP; ++q) {
-            const u32x4 v = *(const u32x4*)(wr + q * 32);
-            const u32x4 z = (u32x4){0u, 0u, 0u, 0u};
-            wf[j][q] = __builtin_bit_cast(bf16x8, cls < k ? v : z);
-        }
-    }
-    f32x4 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    const unsigned lds0 = (unsigned)(size_t)ring;
-    const unsigned boff = lds0 + (lane & 15) * 128 + ((g ^ (lane & 7)) << 4);  // + row tile * 2048, ^ 64 for the second k-half
-    // the weight loads are ordinary vector-memory loads in front of the younger DMA requests: vmcnt counts both in order,
-    // so waiting for a step's DMA also waits for them
-#if defined(SL_PROBE_SM_NOLOOP)  // timing probe (wrong results): prologue + exchange + softmax only
-    wait_vmcnt<0>();
-#else
-#pragma unroll
-    for (int c = 0; c < NSTEP; ++c) {
-        const int slot = c % SLOTS;
-        // requests issued so far: min(NSTEP, c + SLOTS) steps; step c has landed once at most (issued - c - 1) steps remain
-        const int after = (c + SLOTS < NSTEP ? c + SLOTS : NSTEP) - c - 1;
-        if (after == 3) wait_vmcnt<3 * DPS>();
-        else if (after == 2) wait_vmcnt<2 * DPS>();
-        else if (after == 1) wait_vmcnt<1 * DPS>();
-        else wait_vmcnt<0>();
-        bf16x8 bfr[8];
-        const unsigned b_addr = boff + slot * SLOT_BYTES;
-        ds_read128<0>(bfr[0], b_addr);
-        ds_read128<2048>(bfr[1], b_addr);
-        ds_read128<4096>(bfr[2], b_addr);
-        ds_read128<6144>(bfr[3], b_addr);
-        ds_read128<0>(bfr[4], b_addr ^ 64);
-        ds_read128<2048>(bfr[5], b_addr ^ 64);
-        ds_read128<4096>(bfr[6], b_addr ^ 64);
-        ds_read128<6144>(bfr[7], b_addr ^ 64);
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(bfr[0]), "+v"(bfr[1]), "+v"(bfr[2]), "+v"(bfr[3]), "+v"(bfr[4]), "+v"(bfr[5]), "+v"(bfr[6]),
-                       "+v"(bfr[7]));
-        if (c + SLOTS < NSTEP) request(c + SLOTS, slot);  // the slot's bytes are in registers now
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = SL_MFMA16(wf[j][2 * c + h], bfr[4 * h + i], acc[i][j]);
-    }
-#endif
-    // ---- the four waves' partial tiles meet in LDS (the rings are drained): part[wave][row tile][class tile][lane] f32x4
-    __syncthreads();
-    f32x4* part = (f32x4*)smem;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) part[((wave * 4 + i) * 2 + j) * 64 + lane] = acc[i][j];
-    __syncthreads();
-    f32x4 sum[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        sum[j] = part[((0 * 4 + wave) * 2 + j) * 64 + lane];
-#pragma unroll
-        for (int p = 1; p < 4; ++p) sum[j] += part[((p * 4 + wave) * 2 + j) * 64 + lane];
-    }
-    output_softmax_finish(sum, bias, probs, logq, logits, b, t0, wave, lane, g, t_out, k, logit_stride, logit_batch_stride, eps);
-}
-
 // split-K tail: out = epi(sum_split partial), 8 channels per thread, fixed summation order
 template <int MODE, bool OUT_F32>
 __global__ __launch_bounds__(256) void nt_splitk_epilogue_kernel(NtArgs a, int rows_per_batch) {
@@ -1654,45 +1335,37 @@ __global__ __launch_bounds__(256) void nt_splitk_epilogue_kernel(NtArgs a, int r
     }
 }
 
-template <bool M32, int IT, int WM, int WN, int STAGES, int MODE, bool OUT_F32>
+// which kernel a variant runs: conv_nt_bf16_kernel (tap-major), conv_nt_slab_bf16_kernel, conv_nt_ks2_bf16_kernel
+enum NtKind { TAP, SLAB, KS2 };
+
+template <auto KERNEL, int THREADS, int LDS_BYTES>
+int launch_kernel(const NtArgs& a, hipStream_t s, const char* what) {
+    static_assert(LDS_BYTES <= 160 * 1024, "LDS ring (and slabs) exceed the 160 KiB of a CU");
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        attr_set = true;
+    }
+    SL_LAUNCH_MAIN(KERNEL, dim3(xcd_grid(a.batch * a.t_tiles * a.n_tiles * a.ksplit)), dim3(THREADS), LDS_BYTES, s, a);
+    return sl_check_launch(what);
+}
+
+// One compiled tile variant: IT is the real number of 16-row MFMA tiles per wave (M32: unused, 4), SLOTS the ring depth, PIPE the
+// register-pipelined loop, ILV its hand-interleaved schedule.
+template <NtKind KIND, bool M32, int IT, int WM, int WN, int SLOTS, bool PIPE, bool ILV, int MODE, bool OUT_F32>
 int launch_main(const NtArgs& a, hipStream_t s) {
-    const int grid = xcd_grid(a.batch * a.t_tiles * a.n_tiles * a.ksplit);
-    if constexpr (!M32 && IT == 50) {  // 128x128 tile, eight waves in k-half pairs (conv_nt_ks2_bf16_kernel)
-        constexpr int LDS_BYTES = (STAGES & 7) * 256 * 128;
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)conv_nt_ks2_bf16_kernel<(STAGES & 7), MODE, OUT_F32>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            attr_set = true;
-        }
-        SL_LAUNCH_MAIN((conv_nt_ks2_bf16_kernel<(STAGES & 7), MODE, OUT_F32>), dim3(grid), dim3(512), LDS_BYTES, s, a);
-        return sl_check_launch("sl_conv1d_nt(bf16, k-half pairs)");
-    } else if constexpr (!M32 && IT >= 100) {  // slab variant: IT - 100 is the real IT (IT - 200: interleaved schedule)
-        constexpr bool ILV = IT >= 200;
-        constexpr int RIT = ILV ? IT - 200 : IT - 100;
-        constexpr int LDS_BYTES = 2 * (16 * RIT * WM / 8 + 4) * 1024 + (STAGES & 7) * 64 * WN * 128;
-        static_assert(LDS_BYTES <= 160 * 1024, "slabs + weight ring exceed the 160 KiB of a CU");
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)conv_nt_slab_bf16_kernel<RIT, WM, WN, STAGES, MODE, OUT_F32, ILV>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            attr_set = true;
-        }
-        SL_LAUNCH_MAIN((conv_nt_slab_bf16_kernel<RIT, WM, WN, STAGES, MODE, OUT_F32, ILV>), dim3(grid),
-                           dim3(64 * WM * WN), LDS_BYTES, s, a);
-        return sl_check_launch("sl_conv1d_nt(bf16, slab)");
+    constexpr int BM = (M32 ? 64 : 16 * IT) * WM, BN = 64 * WN;
+    if constexpr (KIND == KS2) {  // 128x128 tile, eight waves in k-half pairs
+        static_assert(!M32 && IT == 4 && WM == 2 && WN == 2 && PIPE && ILV, "the k-half-pair kernel has one tile shape and one loop");
+        return launch_kernel<conv_nt_ks2_bf16_kernel<SLOTS, MODE, OUT_F32>, 512, SLOTS * (BM + BN) * 128>(
+            a, s, "sl_conv1d_nt(bf16, k-half pairs)");
+    } else if constexpr (KIND == SLAB) {  // two slabs of BM + 32 rows and the weight ring
+        static_assert(!M32, "the slab kernel has the 16x16 MFMA shape only");
+        return launch_kernel<conv_nt_slab_bf16_kernel<IT, WM, WN, SLOTS, PIPE, ILV, MODE, OUT_F32>, 64 * WM * WN,
+                             2 * (BM / 8 + 4) * 1024 + SLOTS * BN * 128>(a, s, "sl_conv1d_nt(bf16, slab)");
     } else {
-        constexpr int LDS_BYTES = (STAGES & 7) * ((M32 ? 64 : 16 * IT) * WM + 64 * WN) * 128;
-        static_assert(LDS_BYTES <= 160 * 1024, "LDS ring exceeds the 160 KiB of a CU");
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)conv_nt_bf16_kernel<M32, IT, WM, WN, STAGES, MODE, OUT_F32>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-            attr_set = true;
-        }
-        SL_LAUNCH_MAIN((conv_nt_bf16_kernel<M32, IT, WM, WN, STAGES, MODE, OUT_F32>), dim3(grid), dim3(64 * WM * WN),
-                           LDS_BYTES, s, a);
-        return sl_check_launch("sl_conv1d_nt(bf16)");
+        return launch_kernel<conv_nt_bf16_kernel<M32, IT, WM, WN, SLOTS, PIPE, ILV, MODE, OUT_F32>, 64 * WM * WN,
+                             SLOTS * (BM + BN) * 128>(a, s, "sl_conv1d_nt(bf16)");
     }
 }
 
@@ -1704,13 +1377,14 @@ int launch_tail(const NtArgs& a, int rows_per_batch, hipStream_t s) {
     return sl_check_launch("sl_conv1d_nt(bf16 split-K epilogue)");
 }
 
-template <bool M32, int IT, int WM, int WN, int STAGES>
+template <NtKind KIND, bool M32, int IT, int WM, int WN, int SLOTS, bool PIPE, bool ILV>
 int launch_cfg(NtArgs& a, int epilogue, int out_f32, hipStream_t s) {
-    constexpr int BM = (M32 ? 64 : 16 * (IT >= 200 ? IT - 200 : IT >= 100 ? IT - 100 : IT == 50 ? 4 : IT)) * WM;
+#define SL_NT_MAIN(MODE_, F32_) launch_main<KIND, M32, IT, WM, WN, SLOTS, PIPE, ILV, MODE_, F32_>(a, s)
+    constexpr int BM = (M32 ? 64 : 16 * IT) * WM;
     a.t_tiles = (a.t_out + BM - 1) / BM;
     a.n_tiles = a.cout / (64 * WN);
     if (a.ksplit > 1) {
-        int rc = launch_main<M32, IT, WM, WN, STAGES, MODE_PARTIAL, true>(a, s);
+        int rc = SL_NT_MAIN(MODE_PARTIAL, true);
         if (rc != SL_OK) return rc;
         const int rows = a.t_tiles * BM;
         if (out_f32) {
@@ -1729,23 +1403,61 @@ int launch_cfg(NtArgs& a, int epilogue, int out_f32, hipStream_t s) {
 #endif
         }
     } else if (out_f32) {
-        if (epilogue == SL_EPI_BIAS) return launch_main<M32, IT, WM, WN, STAGES, SL_EPI_BIAS, true>(a, s);
-        if (epilogue == SL_EPI_NONE) return launch_main<M32, IT, WM, WN, STAGES, SL_EPI_NONE, true>(a, s);
+        if (epilogue == SL_EPI_BIAS) return SL_NT_MAIN(SL_EPI_BIAS, true);
+        if (epilogue == SL_EPI_NONE) return SL_NT_MAIN(SL_EPI_NONE, true);
     } else {
 #if !defined(SL_ELEM_F16)
         switch (epilogue) {
-            case SL_EPI_NONE: return launch_main<M32, IT, WM, WN, STAGES, SL_EPI_NONE, false>(a, s);
-            case SL_EPI_BIAS: return launch_main<M32, IT, WM, WN, STAGES, SL_EPI_BIAS, false>(a, s);
-            case SL_EPI_BIAS_RELU: return launch_main<M32, IT, WM, WN, STAGES, SL_EPI_BIAS_RELU, false>(a, s);
-            case SL_EPI_RELU_MASK: return launch_main<M32, IT, WM, WN, STAGES, SL_EPI_RELU_MASK, false>(a, s);
-            case SL_EPI_BIAS_ELU: return launch_main<M32, IT, WM, WN, STAGES, SL_EPI_BIAS_ELU, false>(a, s);
-            case SL_EPI_ELU_MASK: return launch_main<M32, IT, WM, WN, STAGES, SL_EPI_ELU_MASK, false>(a, s);
+            case SL_EPI_NONE: return SL_NT_MAIN(SL_EPI_NONE, false);
+            case SL_EPI_BIAS: return SL_NT_MAIN(SL_EPI_BIAS, false);
+            case SL_EPI_BIAS_RELU: return SL_NT_MAIN(SL_EPI_BIAS_RELU, false);
+            case SL_EPI_RELU_MASK: return SL_NT_MAIN(SL_EPI_RELU_MASK, false);
+            case SL_EPI_BIAS_ELU: return SL_NT_MAIN(SL_EPI_BIAS_ELU, false);
+            case SL_EPI_ELU_MASK: return SL_NT_MAIN(SL_EPI_ELU_MASK, false);
         }
 #endif
     }
+#undef SL_NT_MAIN
     sl_set_error("sl_conv1d_nt(bf16): unsupported epilogue %d with out_f32=%d", epilogue, out_f32);
     return SL_ERR_UNSUPPORTED;
 }
+
+// ---- every compiled tile variant, once: what valid configurations are and what conv_nt_bf16() launches
+struct NtVariant {
+    NtKind kind;
+    int m32, it, wm, wn, slots, pipe, ilv;
+    int (*launch)(NtArgs&, int epilogue, int out_f32, hipStream_t);
+};
+#define V(KIND, M32, IT, WM, WN, SLOTS, PIPE, ILV) \
+    {KIND, M32, IT, WM, WN, SLOTS, PIPE, ILV, launch_cfg<KIND, (M32 != 0), IT, WM, WN, SLOTS, (PIPE != 0), (ILV != 0)>}
+constexpr NtVariant NT_VARIANTS[] = {
+    //        m32 it wm wn slots pipe ilv
+    // 128x128 tile, eight waves in k-half pairs
+    V(KS2,  0, 4, 2, 2, 3, 1, 1), V(KS2,  0, 4, 2, 2, 4, 1, 1),
+    // slab, interleaved: the 256x256 tile of 8 waves and the 128x128 tile of 4
+    V(SLAB, 0, 8, 2, 4, 2, 1, 1), V(SLAB, 0, 4, 2, 2, 2, 1, 1), V(SLAB, 0, 4, 2, 2, 3, 1, 1), V(SLAB, 0, 4, 2, 2, 4, 1, 1),
+    // slab, plain and register-pipelined
+    V(SLAB, 0, 4, 4, 4, 2, 0, 0), V(SLAB, 0, 8, 2, 4, 2, 1, 0), V(SLAB, 0, 2, 4, 2, 3, 1, 0), V(SLAB, 0, 2, 4, 2, 3, 0, 0),
+    V(SLAB, 0, 4, 2, 2, 3, 1, 0), V(SLAB, 0, 4, 2, 2, 4, 1, 0),
+    // tap-major, interleaved
+    V(TAP,  0, 2, 4, 2, 2, 1, 1), V(TAP,  0, 2, 4, 2, 3, 1, 1), V(TAP,  0, 2, 4, 2, 4, 1, 1), V(TAP,  0, 4, 2, 2, 2, 1, 1),
+    V(TAP,  0, 4, 2, 2, 3, 1, 1), V(TAP,  0, 4, 2, 2, 4, 1, 1), V(TAP,  0, 8, 2, 4, 2, 1, 1),
+    // tap-major, register-pipelined (16x16 shape, up to 8 waves; the 256x128 tile exists in this flavour only)
+    V(TAP,  0, 4, 2, 2, 2, 1, 0), V(TAP,  0, 4, 2, 2, 3, 1, 0), V(TAP,  0, 4, 2, 2, 4, 1, 0), V(TAP,  0, 2, 4, 2, 2, 1, 0),
+    V(TAP,  0, 2, 4, 2, 3, 1, 0), V(TAP,  0, 2, 4, 2, 4, 1, 0), V(TAP,  0, 4, 4, 2, 2, 1, 0), V(TAP,  0, 4, 4, 2, 3, 1, 0),
+    V(TAP,  0, 4, 2, 4, 2, 1, 0), V(TAP,  0, 4, 2, 4, 3, 1, 0), V(TAP,  0, 8, 2, 4, 2, 1, 0), V(TAP,  0, 8, 2, 2, 2, 1, 0),
+    V(TAP,  0, 8, 2, 2, 3, 1, 0),
+    // tap-major, plain ring, 16x16 shape (8 2 4: the 256x256 tile, 8 waves of 128x64)
+    V(TAP,  0, 8, 2, 4, 2, 0, 0), V(TAP,  0, 4, 2, 2, 2, 0, 0), V(TAP,  0, 4, 2, 2, 3, 0, 0), V(TAP,  0, 4, 2, 2, 4, 0, 0),
+    V(TAP,  0, 4, 4, 2, 2, 0, 0), V(TAP,  0, 4, 4, 2, 3, 0, 0), V(TAP,  0, 4, 2, 4, 2, 0, 0), V(TAP,  0, 4, 2, 4, 3, 0, 0),
+    V(TAP,  0, 4, 4, 4, 2, 0, 0), V(TAP,  0, 2, 2, 2, 2, 0, 0), V(TAP,  0, 2, 2, 2, 3, 0, 0), V(TAP,  0, 2, 2, 2, 4, 0, 0),
+    V(TAP,  0, 2, 2, 4, 2, 0, 0), V(TAP,  0, 2, 2, 4, 3, 0, 0), V(TAP,  0, 2, 4, 2, 2, 0, 0), V(TAP,  0, 2, 4, 2, 3, 0, 0),
+    V(TAP,  0, 2, 4, 2, 4, 0, 0), V(TAP,  0, 2, 8, 2, 2, 0, 0), V(TAP,  0, 2, 8, 2, 3, 0, 0),
+    // tap-major, plain ring, 32x32 shape
+    V(TAP,  1, 4, 2, 2, 2, 0, 0), V(TAP,  1, 4, 2, 2, 3, 0, 0), V(TAP,  1, 4, 2, 2, 4, 0, 0), V(TAP,  1, 4, 4, 2, 2, 0, 0),
+    V(TAP,  1, 4, 4, 2, 3, 0, 0), V(TAP,  1, 4, 2, 4, 2, 0, 0), V(TAP,  1, 4, 2, 4, 3, 0, 0), V(TAP,  1, 4, 4, 4, 2, 0, 0),
+};
+#undef V
 
 struct Cfg {
     int wm, wn, stages, ksplit, it, m32;
@@ -1827,55 +1539,20 @@ Cfg auto_cfg(const sl_conv_geom* g) {
     return c;
 }
 
-bool valid_cfg(const Cfg& full, const sl_conv_geom* g) {
-    Cfg c = full;
-    c.stages = full.stages & 7;  // bit 3 selects the register-pipelined loop, instantiated for the shapes listed below
-    if (c.ks2) {  // instantiated: 2x2 patches, 3 or 4 slots, interleaved tap-major only
-        if (c.m32 || c.slab || !c.ilv || c.wm != 2 || c.wn != 2 || (full.stages != 11 && full.stages != 12)) return false;
-        if (g->cout % 128 || c.ksplit < 1) return false;
-        return c.ksplit <= (long)g->taps * (g->cin / BK);
+// the compiled variant a decoded configuration names, if there is one and the launch geometry fits it
+const NtVariant* valid_cfg(const Cfg& c, const sl_conv_geom* g) {
+    const NtKind kind = c.ks2 ? KS2 : c.slab ? SLAB : TAP;
+    const NtVariant* v = nullptr;
+    for (const NtVariant& e : NT_VARIANTS)  // cfg stages field: ring slots, bit 3 = register-pipelined
+        if (e.kind == kind && !(c.ks2 && c.slab) && e.m32 == c.m32 && e.it == c.it && e.wm == c.wm && e.wn == c.wn &&
+            e.slots == (c.stages & 7) && e.pipe == (c.stages >> 3) && e.ilv == c.ilv)
+            v = &e;
+    if (v == nullptr || c.ksplit < 1 || g->cout % (64 * c.wn)) return nullptr;
+    if (kind == SLAB) {  // the slab holds BM + 32 rows and its DMA must be older than the next chunk's tiles
+        if (g->taps > 33 || g->taps < v->slots) return nullptr;
+        return c.ksplit <= g->cin / BK ? v : nullptr;  // whole chunks per split
     }
-    if ((full.stages & 8) && (c.m32 || !((c.it == 4 && c.wm * c.wn >= 4 && c.wm * c.wn <= 8) || c.it == 8 ||
-                                         (c.it == 2 && c.wm == 4 && c.wn == 2))))
-        return false;
-    bool shape;
-    if (c.m32)
-        shape = (c.wm == 2 && c.wn == 2 && c.stages >= 2 && c.stages <= 4) || (c.wm == 4 && c.wn == 4 && c.stages == 2) ||
-                (c.wm == 4 && c.wn == 2 && (c.stages == 2 || c.stages == 3)) ||
-                (c.wm == 2 && c.wn == 4 && (c.stages == 2 || c.stages == 3));
-    else
-        shape = (c.it == 2 && c.wm == 2 && c.wn == 2 && c.stages >= 2 && c.stages <= 4) ||
-                (c.it == 2 && c.wm == 2 && c.wn == 4 && (c.stages == 2 || c.stages == 3)) ||
-                (c.it == 2 && c.wm == 4 && c.wn == 2 && c.stages >= 2 && c.stages <= 4) ||
-                (c.it == 2 && c.wm == 8 && c.wn == 2 && (c.stages == 2 || c.stages == 3)) ||
-                (c.it == 4 && c.wm == 2 && c.wn == 2 && (c.stages >= 2 && c.stages <= 4)) ||
-                (c.it == 4 && c.wm == 4 && c.wn == 2 && (c.stages == 2 || c.stages == 3)) ||
-                (c.it == 4 && c.wm == 2 && c.wn == 4 && (c.stages == 2 || c.stages == 3)) ||
-                (c.it == 4 && c.wm == 4 && c.wn == 4 && c.stages == 2) ||
-                (c.it == 8 && c.wm == 2 && c.wn == 4 && c.stages == 2) ||  // 256x256 tile, 8 waves of 128x64
-                (c.it == 8 && c.wm == 2 && c.wn == 2 && (full.stages == 10 || full.stages == 11));  // 256x128, pipelined only
-    if (!shape || c.ksplit < 1) return false;
-    if (g->cout % (64 * c.wn)) return false;
-    const long nsteps = (long)g->taps * (g->cin / BK);
-    if (c.ilv) {  // instantiated interleaved shapes: the slab 256x256 kernel and three tap-major pipelined tiles
-        const bool slab_ilv = c.slab && !c.m32 && ((c.it == 8 && c.wm == 2 && c.wn == 4 && full.stages == 10) ||
-                                                   (c.it == 4 && c.wm == 2 && c.wn == 2 && full.stages >= 10 && full.stages <= 12));
-        const bool tap_ilv = !c.slab && !c.m32 && (full.stages & 8) &&
-                             ((c.it == 2 && c.wm == 4 && c.wn == 2) || (c.it == 4 && c.wm == 2 && c.wn == 2) ||
-                              (c.it == 8 && c.wm == 2 && c.wn == 4 && full.stages == 10));
-        if (!slab_ilv && !tap_ilv) return false;
-    }
-    if (c.slab) {
-        // instantiated slab shapes; the slab holds BM + 32 rows and its DMA must be older than the next chunk's tiles
-        const bool inst = !c.m32 && ((c.it == 4 && c.wm == 4 && c.wn == 4 && full.stages == 2) ||
-                                     (c.it == 8 && c.wm == 2 && c.wn == 4 && full.stages == 10) ||
-                                     (c.it == 2 && c.wm == 4 && c.wn == 2 && (full.stages == 11 || full.stages == 3)) ||
-                                     (c.it == 4 && c.wm == 2 && c.wn == 2 && (full.stages == 11 || full.stages == 12)) ||
-                                     (c.ilv && c.it == 4 && c.wm == 2 && c.wn == 2 && full.stages == 10));
-        if (!inst || g->taps > 33 || g->taps < c.stages) return false;
-        return c.ksplit <= g->cin / BK;  // whole chunks per split
-    }
-    return c.ksplit <= nsteps;
+    return c.ksplit <= (long)g->taps * (g->cin / BK) ? v : nullptr;
 }
 
 }  // namespace
@@ -1895,7 +1572,8 @@ size_t conv_nt_bf16_workspace_bytes(const sl_conv_geom* g, int cfg) {
 int conv_nt_bf16(const void* x, const void* w, const float* bias, const void* mask, void* y, const sl_conv_geom* g,
                  int epilogue, int out_f32, int cfg, void* workspace, size_t workspace_bytes, hipStream_t s) {
     Cfg c = cfg ? decode_cfg(cfg) : auto_cfg(g);
-    if (!valid_cfg(c, g)) {
+    const NtVariant* v = valid_cfg(c, g);
+    if (v == nullptr) {
         sl_set_error(
             "sl_conv1d_nt(bf16): invalid tile configuration m32=%d it=%d wm=%d wn=%d stages=%d ksplit=%d for cout=%d",
             c.m32, c.it, c.wm, c.wn, c.stages, c.ksplit, g->cout);
@@ -1957,145 +1635,5 @@ int conv_nt_bf16(const void* x, const void* w, const float* bias, const void* ma
             return SL_ERR_WORKSPACE_TOO_SMALL;
         }
     }
-    if (c.ks2 && c.stages == 11) return launch_cfg<false, 50, 2, 2, 11>(a, epilogue, out_f32, s);
-    if (c.ks2 && c.stages == 12) return launch_cfg<false, 50, 2, 2, 12>(a, epilogue, out_f32, s);
-#define SL_NT_SLAB_CASE(IT_, WM_, WN_, ST_)                                      \
-    if (c.slab && c.it == IT_ && c.wm == WM_ && c.wn == WN_ && c.stages == ST_) \
-        return launch_cfg<false, 100 + IT_, WM_, WN_, ST_>(a, epilogue, out_f32, s);
-    if (c.slab && c.ilv && c.it == 8) return launch_cfg<false, 208, 2, 4, 10>(a, epilogue, out_f32, s);
-    if (c.slab && c.ilv && c.stages == 10) return launch_cfg<false, 204, 2, 2, 10>(a, epilogue, out_f32, s);
-    if (c.slab && c.ilv && c.stages == 11) return launch_cfg<false, 204, 2, 2, 11>(a, epilogue, out_f32, s);
-    if (c.slab && c.ilv && c.stages == 12) return launch_cfg<false, 204, 2, 2, 12>(a, epilogue, out_f32, s);
-    SL_NT_SLAB_CASE(4, 4, 4, 2)
-    SL_NT_SLAB_CASE(8, 2, 4, 10)
-    SL_NT_SLAB_CASE(2, 4, 2, 11)
-    SL_NT_SLAB_CASE(2, 4, 2, 3)
-    SL_NT_SLAB_CASE(4, 2, 2, 11)
-    SL_NT_SLAB_CASE(4, 2, 2, 12)
-#undef SL_NT_SLAB_CASE
-    if (c.slab) {
-        sl_set_error("sl_conv1d_nt(bf16): slab configuration not instantiated");
-        return SL_ERR_UNSUPPORTED;
-    }
-#define SL_NT_ILV_CASE(IT_, WM_, WN_, ST_)                                          \
-    if (!c.slab && c.ilv && c.it == IT_ && c.wm == WM_ && c.wn == WN_ && c.stages == ST_) \
-        return launch_cfg<false, IT_, WM_, WN_, (ST_ | 16)>(a, epilogue, out_f32, s);
-    SL_NT_ILV_CASE(2, 4, 2, 10)
-    SL_NT_ILV_CASE(2, 4, 2, 11)
-    SL_NT_ILV_CASE(2, 4, 2, 12)
-    SL_NT_ILV_CASE(4, 2, 2, 10)
-    SL_NT_ILV_CASE(4, 2, 2, 11)
-    SL_NT_ILV_CASE(4, 2, 2, 12)
-    SL_NT_ILV_CASE(8, 2, 4, 10)
-#undef SL_NT_ILV_CASE
-#define SL_NT_CASE(M32_, IT_, WM_, WN_, ST_)                                                \
-    if (c.m32 == M32_ && c.it == IT_ && c.wm == WM_ && c.wn == WN_ && c.stages == ST_) \
-        return launch_cfg<(M32_ != 0), IT_, WM_, WN_, ST_>(a, epilogue, out_f32, s);
-    SL_NT_CASE(0, 4, 2, 2, 10)
-    SL_NT_CASE(0, 4, 2, 2, 11)
-    SL_NT_CASE(0, 4, 2, 2, 12)
-    SL_NT_CASE(0, 2, 4, 2, 10)
-    SL_NT_CASE(0, 2, 4, 2, 11)
-    SL_NT_CASE(0, 2, 4, 2, 12)
-    SL_NT_CASE(0, 4, 4, 2, 10)
-    SL_NT_CASE(0, 4, 4, 2, 11)
-    SL_NT_CASE(0, 4, 2, 4, 10)
-    SL_NT_CASE(0, 4, 2, 4, 11)
-    SL_NT_CASE(0, 8, 2, 4, 10)
-    SL_NT_CASE(0, 8, 2, 4, 2)
-    SL_NT_CASE(0, 8, 2, 2, 10)
-    SL_NT_CASE(0, 8, 2, 2, 11)
-    SL_NT_CASE(0, 4, 2, 2, 2)
-    SL_NT_CASE(0, 4, 2, 2, 3)
-    SL_NT_CASE(0, 4, 2, 2, 4)
-    SL_NT_CASE(0, 4, 4, 2, 2)
-    SL_NT_CASE(0, 4, 4, 2, 3)
-    SL_NT_CASE(0, 4, 2, 4, 2)
-    SL_NT_CASE(0, 4, 2, 4, 3)
-    SL_NT_CASE(0, 4, 4, 4, 2)
-    SL_NT_CASE(0, 2, 2, 2, 2)
-    SL_NT_CASE(0, 2, 2, 2, 3)
-    SL_NT_CASE(0, 2, 2, 2, 4)
-    SL_NT_CASE(0, 2, 2, 4, 2)
-    SL_NT_CASE(0, 2, 2, 4, 3)
-    SL_NT_CASE(0, 2, 4, 2, 2)
-    SL_NT_CASE(0, 2, 4, 2, 3)
-    SL_NT_CASE(0, 2, 4, 2, 4)
-    SL_NT_CASE(0, 2, 8, 2, 2)
-    SL_NT_CASE(0, 2, 8, 2, 3)
-    SL_NT_CASE(1, 4, 2, 2, 2)
-    SL_NT_CASE(1, 4, 2, 2, 3)
-    SL_NT_CASE(1, 4, 2, 2, 4)
-    SL_NT_CASE(1, 4, 4, 2, 2)
-    SL_NT_CASE(1, 4, 4, 2, 3)
-    SL_NT_CASE(1, 4, 2, 4, 2)
-    SL_NT_CASE(1, 4, 2, 4, 3)
-    SL_NT_CASE(1, 4, 4, 4, 2)
-#undef SL_NT_CASE
-    sl_set_error("sl_conv1d_nt(bf16): configuration not instantiated");
-    return SL_ERR_UNSUPPORTED;
+    return v->launch(a, epilogue, out_f32, s);
 }
-
-#if !defined(SL_ELEM_F16)  // (the fused output layer belongs to the bf16 path: one definition, in the bf16 translation unit)
-// ---- fused output layer (declared in capi.hip's dispatch: sl_output_softmax)
-bool output_softmax_supported(const sl_conv_geom* g, int k) {
-    if (g->taps != 1 || k < 1 || k > 32 || g->cout < 32 || g->cin % BK) return false;
-    return ((k * (g->cin * 2 + 16) + 127) & ~127) + 3 * 64 * 128 <= 160 * 1024;
-}
-
-static int g_output_softmax_variant = 0;  // sl_output_softmax_select: 0 = automatic, 1 = weights in LDS, 2 = weights in registers
-int output_softmax_select(int variant) {
-    g_output_softmax_variant = variant;
-    return SL_OK;
-}
-
-template <int NSTEP>
-static int launch_output_softmax_regw(const void* x, const void* w, const float* bias, float* probs, float* logq,
-                                      float* logits, const sl_conv_geom* g, int k, int logit_stride,
-                                      long logit_batch_stride, float eps, hipStream_t s) {
-    constexpr int SLOTS = NSTEP < 4 ? NSTEP : 4;
-    constexpr int LDS = (4 * SLOTS * 64 * 128) > 32768 ? (4 * SLOTS * 64 * 128) : 32768;  // rings; at least the 32 KiB exchange
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)output_softmax_regw_kernel<NSTEP>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        attr_set = true;
-    }
-    const int t_tiles = (g->t_out + 63) / 64;
-    hipLaunchKernelGGL(output_softmax_regw_kernel<NSTEP>, dim3(g->batch * t_tiles), dim3(256), LDS, s, (const __bf16*)x,
-                       (const __bf16*)w, bias, probs, logq, logits, g->batch, g->t_out, t_tiles, g->taps * g->cin, g->x_row0,
-                       g->x_row_stride, (long)g->x_batch_stride, k, logit_stride, logit_batch_stride, eps);
-    return sl_check_launch("sl_output_softmax(register weights)");
-}
-
-int output_softmax_bf16(const void* x, const void* w, const float* bias, float* probs, float* logq, float* logits,
-                        const sl_conv_geom* g, int k, int logit_stride, long logit_batch_stride, float eps, hipStream_t s) {
-    // weights in registers (one wave per quarter of the input channels, its own ring): cin = 256, 512, 1024 or 2048
-    if (g_output_softmax_variant != 1 && g->taps == 1) {
-        if (g->cin == 2048) return launch_output_softmax_regw<8>(x, w, bias, probs, logq, logits, g, k, logit_stride, logit_batch_stride, eps, s);
-        if (g->cin == 1024) return launch_output_softmax_regw<4>(x, w, bias, probs, logq, logits, g, k, logit_stride, logit_batch_stride, eps, s);
-        if (g->cin == 512) return launch_output_softmax_regw<2>(x, w, bias, probs, logq, logits, g, k, logit_stride, logit_batch_stride, eps, s);
-        if (g->cin == 256) return launch_output_softmax_regw<1>(x, w, bias, probs, logq, logits, g, k, logit_stride, logit_batch_stride, eps, s);
-    }
-    const int wbytes = (k * (g->cin * 2 + 16) + 127) & ~127;
-    const int slots = wbytes + 5 * 64 * 128 <= 160 * 1024 ? 5 : 3;  // ring depth the rest of the LDS allows
-    const int lds = wbytes + slots * 64 * 128;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)output_softmax_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)output_softmax_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    const int t_tiles = (g->t_out + 63) / 64;
-    if (slots == 5)
-        hipLaunchKernelGGL(output_softmax_kernel<5>, dim3(g->batch * t_tiles), dim3(256), lds, s, (const __bf16*)x,
-                           (const __bf16*)w, bias, probs, logq, logits, g->batch, g->t_out, t_tiles, g->cin,
-                           g->taps * g->cin, g->x_row0, g->x_row_stride, (long)g->x_batch_stride, k, logit_stride,
-                           logit_batch_stride, eps);
-    else
-        hipLaunchKernelGGL(output_softmax_kernel<3>, dim3(g->batch * t_tiles), dim3(256), lds, s, (const __bf16*)x,
-                           (const __bf16*)w, bias, probs, logq, logits, g->batch, g->t_out, t_tiles, g->cin,
-                           g->taps * g->cin, g->x_row0, g->x_row_stride, (long)g->x_batch_stride, k, logit_stride,
-                           logit_batch_stride, eps);
-    return sl_check_launch("sl_output_softmax");
-}
-#endif  // !SL_ELEM_F16

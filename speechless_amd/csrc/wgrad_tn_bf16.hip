@@ -1013,12 +1013,24 @@ WCfg auto_wcfg(const sl_conv_geom* g, int groups) {
     return WCfg{2, 2, 2, splits};
 }
 
-bool valid_wcfg(const WCfg& c, const sl_conv_geom* g) {
-    const bool shape = (c.wm == 2 && c.wn == 2 && c.stages >= 2 && c.stages <= 4) ||
-                       (c.wm == 4 && c.wn == 2 && (c.stages == 2 || c.stages == 3)) ||
-                       (c.wm == 2 && c.wn == 4 && (c.stages == 2 || c.stages == 3)) ||
-                       (c.wm == 4 && c.wn == 4 && (c.stages == 2 || c.stages == 10 || c.stages == 11));  // 10: 8-wave interleaved kernel, 11: its 4-slot ring variant
-    return shape && g->cin % (64 * c.wm) == 0 && g->cout % (64 * c.wn) == 0 && c.splits >= 1 && c.splits <= g->batch;
+// ---- every compiled tile variant, once: (wm, wn, stages field of the cfg word) and its launcher
+struct TnVariant {
+    int wm, wn, stages;
+    int (*launch)(const TnArgs&, hipStream_t);
+};
+constexpr TnVariant TN_VARIANTS[] = {
+    {2, 2, 2, launch<2, 2, 2>}, {2, 2, 3, launch<2, 2, 3>}, {2, 2, 4, launch<2, 2, 4>}, {4, 2, 2, launch<4, 2, 2>},
+    {4, 2, 3, launch<4, 2, 3>}, {2, 4, 2, launch<2, 4, 2>}, {2, 4, 3, launch<2, 4, 3>}, {4, 4, 2, launch<4, 4, 2>},
+    {4, 4, 10, launch_ilv},    // 8-wave interleaved kernel
+    {4, 4, 11, launch_ilv32},  // its 4-slot ring variant
+};
+
+// the compiled variant a configuration names, if there is one and the launch geometry fits it
+const TnVariant* valid_wcfg(const WCfg& c, const sl_conv_geom* g) {
+    for (const TnVariant& v : TN_VARIANTS)
+        if (v.wm == c.wm && v.wn == c.wn && v.stages == c.stages)
+            return g->cin % (64 * c.wm) == 0 && g->cout % (64 * c.wn) == 0 && c.splits >= 1 && c.splits <= g->batch ? &v : nullptr;
+    return nullptr;
 }
 
 WCfg resolve_wcfg(const sl_conv_geom* g, int cfg, int groups) {
@@ -1086,7 +1098,8 @@ size_t wgrad_tn_bf16_workspace_bytes(const sl_conv_geom* g, int cfg, int groups)
 int wgrad_tn_bf16(const void* x, const void* gr, float* dw, const sl_conv_geom* g, int cfg, int groups, long x_gs,
                   long g_gs, long dw_gs, float* ws, size_t ws_bytes, hipStream_t s) {
     const WCfg c = resolve_wcfg(g, cfg, groups);
-    if (!valid_wcfg(c, g) || groups < 1) {
+    const TnVariant* v = valid_wcfg(c, g);
+    if (v == nullptr || groups < 1) {
         sl_set_error("sl_conv1d_wgrad(bf16): invalid tile configuration wm=%d wn=%d stages=%d splits=%d for cin=%d cout=%d",
                      c.wm, c.wn, c.stages, c.splits, g->cin, g->cout);
         return SL_ERR_INVALID_ARGUMENT;
@@ -1120,20 +1133,7 @@ int wgrad_tn_bf16(const void* x, const void* gr, float* dw, const sl_conv_geom* 
         return SL_ERR_WORKSPACE_TOO_SMALL;
     }
     a.out = a.splits > 1 ? ws : dw;
-    int rc = SL_ERR_UNSUPPORTED;
-#define SL_TN_CASE(WM_, WN_, ST_) \
-    if (c.wm == WM_ && c.wn == WN_ && c.stages == ST_) rc = launch<WM_, WN_, ST_>(a, s);
-    SL_TN_CASE(2, 2, 2)
-    SL_TN_CASE(2, 2, 3)
-    SL_TN_CASE(2, 2, 4)
-    SL_TN_CASE(4, 2, 2)
-    SL_TN_CASE(4, 2, 3)
-    SL_TN_CASE(2, 4, 2)
-    SL_TN_CASE(2, 4, 3)
-    SL_TN_CASE(4, 4, 2)
-#undef SL_TN_CASE
-    if (c.wm == 4 && c.wn == 4 && c.stages == 10) rc = launch_ilv(a, s);
-    if (c.wm == 4 && c.wn == 4 && c.stages == 11) rc = launch_ilv32(a, s);
+    const int rc = v->launch(a, s);
     if (rc != SL_OK) return rc;
     if (a.splits > 1) {
         const long n4 = a.split_stride / 4;

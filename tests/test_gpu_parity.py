@@ -802,7 +802,13 @@ NT_CONFIGS = (
      (4, 2, 10, 1, 2, 0, 0, 2), (4, 2, 11, 1, 2, 0, 0, 2), (4, 2, 12, 2, 2, 0, 0, 2), (2, 2, 10, 1, 4, 0, 0, 2),
      (2, 2, 11, 1, 4, 0, 0, 2), (2, 2, 12, 1, 4, 0, 0, 2), (2, 4, 10, 1, 8, 0, 0, 2)] +
     # split-K of the tap-major kernels
-    [(4, 4, 2, 3, 4, 0, 0, 0), (4, 2, 11, 2, 2, 0, 0, 0)])
+    [(4, 4, 2, 3, 4, 0, 0, 0), (4, 2, 11, 2, 2, 0, 0, 0)] +
+    # the remaining tap-major variants: with these every entry of NT_VARIANTS (conv_nt_bf16.hip) has at least one line here
+    [(wm, wn, st, 1, it, m32, 0, 0) for (wm, wn, st, it, m32) in
+     [(2, 2, 11, 4, 0), (4, 2, 10, 2, 0), (4, 2, 11, 4, 0), (2, 4, 10, 4, 0),
+      (2, 2, 3, 4, 0), (4, 2, 2, 4, 0), (2, 4, 3, 4, 0), (2, 2, 2, 2, 0), (2, 2, 4, 2, 0), (2, 4, 2, 2, 0), (2, 4, 3, 2, 0),
+      (4, 2, 2, 2, 0), (4, 2, 3, 2, 0), (8, 2, 3, 2, 0),
+      (2, 2, 2, 4, 1), (2, 2, 4, 4, 1), (4, 2, 2, 4, 1), (4, 2, 3, 4, 1), (2, 4, 2, 4, 1), (2, 4, 3, 4, 1)]])
 
 
 @pytest.mark.parametrize("taps,t_out,batch", [(7, 300, 3), (32, 140, 2), (5, 129, 5)])
