@@ -430,6 +430,45 @@ int sl_adam_pack_layer(float* param, const float* grad, float* m, float* v, void
                        int cin_pad, int cout_pad, int dtype, int step, float lr, float beta1, float beta2, float eps,
                        void* stream);
 
+/* ---- Gradient clipping on the device (Keras 2.0.x optimizers.py, Optimizer.get_gradients: every Keras optimizer takes
+ * clipnorm / clipvalue; restated from knowledge of Keras 2.0 like the Adam row above -- not checkable offline) ------------
+ *   n = sqrt(sum over the TRAINABLE tensors of sum(g * g));   g = g * clipnorm / n if n >= clipnorm else g
+ *   then g = clip(g, -clipvalue, +clipvalue)
+ * The optimisation step never waits for the host, so n is reduced on the device and the Adam kernels read the factor from
+ * device memory.  A NaN / Inf norm gets no special handling: the comparison is false and g passes through, as in Keras.
+ *
+ * Squared norm: *sqnorm = sum over the ranges [offset, offset + count) of grad (floats; any alignment of the ranges, grad
+ * itself 16-byte aligned) of g * g, accumulated in double.  The order of the additions is fixed by the ranges alone (a
+ * partial per 16384-float chunk, then the partials in index order; no floating-point atomics), so the same data gives the same
+ * bits on every call, whatever sl_set_available_cus says.  norm / scale (each may be NULL): sl_clip_scale's outputs for this
+ * one term, written by the same final launch. */
+#define SL_NORM_MAX_RANGES 16
+typedef struct {
+    int64_t offset; /* first float of the range in grad */
+    int64_t count;  /* floats (0 allowed) */
+} sl_norm_range;
+size_t sl_grad_sqnorm_workspace_bytes(const sl_norm_range* ranges, int n_ranges);
+int sl_grad_sqnorm(const float* grad, const sl_norm_range* ranges, int n_ranges, float clipnorm, double* sqnorm, float* norm,
+                   float* scale, void* workspace, size_t workspace_bytes, void* stream);
+/* n = sqrt(sqnorm[0] + ... + sqnorm[n_terms - 1]) (one term per range table, or the all-reduced sum of the ranks' terms);
+ * *norm = (float)n;  *scale = n >= clipnorm ? (float)(clipnorm / n) : exactly 1.0f  (clipnorm <= 0: 1.0f). */
+int sl_clip_scale(const double* sqnorm, int n_terms, float clipnorm, float* scale, float* norm, void* stream);
+
+/* Clipped twins of the four Adam entry points: the update sees clip(g * *grad_scale, -clipvalue, +clipvalue) in place of g
+ * (grad_scale: device pointer, NULL = 1; clipvalue 0 = off).  grad itself is not rewritten; the operand-repack half is the
+ * original's.  With NULL and 0 a twin IS its original (same kernel, same bits). */
+int sl_adam_step_clipped(float* param, const float* grad, float* m, float* v, size_t n, int step, float lr, float beta1,
+                         float beta2, float eps, const float* grad_scale, float clipvalue, void* stream);
+int sl_adam_pack_layers_clipped(float* param, const float* grad, float* m, float* v, const sl_adam_layer* layers, int n_layers,
+                                int dtype, int step, float lr, float beta1, float beta2, float eps, const float* grad_scale,
+                                float clipvalue, void* stream);
+int sl_split3_adam_pack_layers_clipped(float* param, const float* grad, float* m, float* v, const sl_adam_layer* layers,
+                                       int n_layers, int step, float lr, float beta1, float beta2, float eps,
+                                       const float* grad_scale, float clipvalue, void* stream);
+int sl_splitf16_adam_pack_layers_clipped(float* param, const float* grad, float* m, float* v, const sl_adam_layer* layers,
+                                         int n_layers, int step, float lr, float beta1, float beta2, float eps, float w_scale,
+                                         const float* grad_scale, float clipvalue, void* stream);
+
 /* ---- "bf16x3": the fast parity path ---------------------------------------------------------------------------------------
  * north_star: greedy-decoded indices bit-exact against the reference's fp32 CPU path (net.py:417-436 on Keras / TF float32),
  * gradients within 1e-3.  Every fp32 value is carried as two bf16 numbers (hi = bf16(v), lo = bf16(v - hi)) in THREE planes

@@ -40,6 +40,11 @@ class BgwLayer(ctypes.Structure):
                 ("tap", c_int32)]
 
 
+class NormRange(ctypes.Structure):
+    """Mirror of sl_norm_range (include/speechless_hip.h)."""
+    _fields_ = [("offset", c_int64), ("count", c_int64)]
+
+
 class ConvGeom(ctypes.Structure):
     """Mirror of sl_conv_geom (include/speechless_hip.h)."""
     _fields_ = [
@@ -170,6 +175,19 @@ SIGNATURES = {
     "sl_splitf16_bias_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_float, c_void_p, c_size_t,
                                       c_void_p]),
     "sl_splitf16_dropout": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, ctypes.c_uint64, c_void_p]),
+    "sl_grad_sqnorm_workspace_bytes": (c_size_t, [POINTER(NormRange), c_int]),
+    "sl_grad_sqnorm": (c_int, [c_void_p, POINTER(NormRange), c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                               c_void_p]),
+    "sl_clip_scale": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    # the clipped twins: the original's arguments, then grad_scale (device float*, NULL = 1) and clipvalue (0 = off)
+    "sl_adam_step_clipped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_float,
+                                     c_float, c_void_p, c_float, c_void_p]),
+    "sl_adam_pack_layers_clipped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamLayer), c_int, c_int, c_int,
+                                            c_float, c_float, c_float, c_float, c_void_p, c_float, c_void_p]),
+    "sl_split3_adam_pack_layers_clipped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamLayer), c_int, c_int,
+                                                   c_float, c_float, c_float, c_float, c_void_p, c_float, c_void_p]),
+    "sl_splitf16_adam_pack_layers_clipped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamLayer), c_int, c_int,
+                                                     c_float, c_float, c_float, c_float, c_float, c_void_p, c_float, c_void_p]),
 }
 
 

@@ -166,11 +166,28 @@ __device__ __forceinline__ void adam_element(float& p, const float g, float& m, 
     p = p - step;
 }
 
+// Gradient clipping (sl_*_clipped): what the update sees in place of g.  Comparisons, not fminf / fmaxf: a NaN gradient stays
+// a NaN, as through Keras' clip.  gs == 1 and cv == 0 leave g's bits alone.
+__device__ __forceinline__ float clipped_grad(const float g, const float gs, const float cv) {
+    const float s = g * gs;
+    if (cv > 0.f) return s > cv ? cv : (s < -cv ? -cv : s);
+    return s;
+}
+
+// CLIP: the gradient goes through clipped_grad first (*gscale read once per thread: NULL = 1); CLIP = false is the kernel
+// as it was -- the twins with no clipping asked for launch that instantiation
+template <bool CLIP = false>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                            float* __restrict__ v, long n4, float lr_t, float b1, float b2, float eps) {
+                            float* __restrict__ v, long n4, float lr_t, float b1, float b2, float eps,
+                            const float* __restrict__ gscale = nullptr, float cv = 0.f) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n4) return;
-    const f32x4 gv = ((const f32x4*)g)[i];
+    f32x4 gv = ((const f32x4*)g)[i];
+    if (CLIP) {
+        const float gs = gscale ? *gscale : 1.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gv[j] = clipped_grad(gv[j], gs, cv);
+    }
     f32x4 mv = ((f32x4*)m)[i];
     f32x4 vv = ((f32x4*)v)[i];
     f32x4 pv = ((f32x4*)p)[i];
@@ -206,11 +223,12 @@ __device__ __forceinline__ u32x2 pack_lo4(float a0, float a1, float a2, float a3
     auto lo = [](float v) { return v - bf16_bits_to_f32(f32_to_bf16_bits(v)); };
     return (u32x2){pack_bf16x2(lo(a0), lo(a1)), pack_bf16x2(lo(a2), lo(a3))};
 }
-template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0>
+template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0, bool CLIP = false>
 __device__ __forceinline__ void adam_pack_block(float (&tile)[32][65], float* __restrict__ p, const float* __restrict__ g,
                                                 float* __restrict__ m, float* __restrict__ v, T* __restrict__ wf,
                                                 T* __restrict__ wd, int k, int cin, int cout, float lr_t, float b1,
-                                                float b2, float eps, int bx, int by, int bz, float wscale = 1.f) {
+                                                float b2, float eps, int bx, int by, int bz, float wscale = 1.f,
+                                                float gs = 1.f, float cv = 0.f) {
     const int tap = bz;
     const int co0 = bx * 64;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
@@ -221,7 +239,7 @@ __device__ __forceinline__ void adam_pack_block(float (&tile)[32][65], float* __
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float pj = pv[j], mj = mv[j], vj = vv[j];
-            adam_element(pj, gv[j], mj, vj, lr_t, b1, b2, eps);
+            adam_element(pj, CLIP ? clipped_grad(gv[j], gs, cv) : gv[j], mj, vj, lr_t, b1, b2, eps);
             pv[j] = pj, mv[j] = mj, vv[j] = vj;
         }
         *(f32x4*)(m + idx) = mv;
@@ -297,10 +315,11 @@ struct AdamTable {
     int k[SL_ADAM_MAX_LAYERS], cin[SL_ADAM_MAX_LAYERS], cout[SL_ADAM_MAX_LAYERS];
 };
 
-template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0>
+template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0, bool CLIP = false>
 __global__ __launch_bounds__(256) void adam_pack_multi_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                               float* __restrict__ m, float* __restrict__ v, AdamTable t,
-                                                              float lr_t, float b1, float b2, float eps, float wscale = 1.f) {
+                                                              float lr_t, float b1, float b2, float eps, float wscale = 1.f,
+                                                              const float* __restrict__ gscale = nullptr, float cv = 0.f) {
     __shared__ float tile[32][65];
     int layer = 0;
     while (layer + 1 < t.n && (int)blockIdx.x >= t.block_begin[layer + 1]) ++layer;
@@ -310,9 +329,10 @@ __global__ __launch_bounds__(256) void adam_pack_multi_kernel(float* __restrict_
     const int bx = local % nx, by = (local / nx) % ny, bz = local / (nx * ny);
     const long off = t.offset[layer];
     if (!ADAM && bz == k) return;  // (the bias block has no operand copy)
-    adam_pack_block<T, ADAM, PLANES, FMT>(tile, p + off, ADAM ? g + off : nullptr, ADAM ? m + off : nullptr,
-                                          ADAM ? v + off : nullptr, (T*)t.wf[layer], (T*)t.wd[layer], k, cin, cout, lr_t, b1, b2,
-                                          eps, bx, by, bz, wscale);
+    const float gs = (CLIP && gscale) ? *gscale : 1.f;
+    adam_pack_block<T, ADAM, PLANES, FMT, CLIP>(tile, p + off, ADAM ? g + off : nullptr, ADAM ? m + off : nullptr,
+                                                ADAM ? v + off : nullptr, (T*)t.wf[layer], (T*)t.wd[layer], k, cin, cout, lr_t,
+                                                b1, b2, eps, bx, by, bz, wscale, gs, cv);
 }
 
 }  // namespace
@@ -339,56 +359,103 @@ static int adam_table_from(const sl_adam_layer* layers, int n_layers, const char
     return SL_OK;
 }
 
+// The three fused entry points and their clipped twins share one body each: `clip` picks the CLIP instantiation, and a twin
+// called with NULL / 0 launches the plain one -- the original's kernel, hence its bits.
+static int adam_pack_layers_impl(const char* who, float* param, const float* grad, float* m, float* v,
+                                 const sl_adam_layer* layers, int n_layers, int dtype, int step, float lr, float beta1,
+                                 float beta2, float eps, const float* grad_scale, float clipvalue, void* stream) {
+    SL_CHECK_ARG(param && grad && m && v && layers, "%s: null pointer", who);
+    SL_CHECK_ARG(n_layers >= 1 && n_layers <= SL_ADAM_MAX_LAYERS, "%s: 1..%d layers per call", who, SL_ADAM_MAX_LAYERS);
+    SL_CHECK_ARG(step >= 1 && (dtype == SL_BF16 || dtype == SL_F32), "%s: bad step or dtype", who);
+    SL_CHECK_ARG(clipvalue >= 0.f, "%s: clipvalue must be >= 0 (0 = off)", who);
+    AdamTable t;
+    int blocks = 0;
+    const int rc = adam_table_from(layers, n_layers, who, &t, &blocks);
+    if (rc != SL_OK) return rc;
+    const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step));
+    const bool clip = grad_scale != nullptr || clipvalue > 0.f;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == SL_BF16 && !clip)
+        hipLaunchKernelGGL((adam_pack_multi_kernel<unsigned short>), dim3(blocks), dim3(256), 0, s, param, grad, m, v, t,
+                           (float)lr_t, beta1, beta2, eps);
+    else if (dtype == SL_BF16)
+        hipLaunchKernelGGL((adam_pack_multi_kernel<unsigned short, true, 1, 0, true>), dim3(blocks), dim3(256), 0, s, param,
+                           grad, m, v, t, (float)lr_t, beta1, beta2, eps, 1.f, grad_scale, clipvalue);
+    else if (!clip)
+        hipLaunchKernelGGL((adam_pack_multi_kernel<float>), dim3(blocks), dim3(256), 0, s, param, grad, m, v, t, (float)lr_t,
+                           beta1, beta2, eps);
+    else
+        hipLaunchKernelGGL((adam_pack_multi_kernel<float, true, 1, 0, true>), dim3(blocks), dim3(256), 0, s, param, grad, m,
+                           v, t, (float)lr_t, beta1, beta2, eps, 1.f, grad_scale, clipvalue);
+    return sl_check_launch(who);
+}
+
 extern "C" int sl_adam_pack_layers(float* param, const float* grad, float* m, float* v, const sl_adam_layer* layers,
                                    int n_layers, int dtype, int step, float lr, float beta1, float beta2, float eps,
                                    void* stream) {
-    SL_CHECK_ARG(param && grad && m && v && layers, "sl_adam_pack_layers: null pointer");
-    SL_CHECK_ARG(n_layers >= 1 && n_layers <= SL_ADAM_MAX_LAYERS, "sl_adam_pack_layers: 1..%d layers per call",
+    return adam_pack_layers_impl("sl_adam_pack_layers", param, grad, m, v, layers, n_layers, dtype, step, lr, beta1, beta2, eps,
+                                 nullptr, 0.f, stream);
+}
+
+extern "C" int sl_adam_pack_layers_clipped(float* param, const float* grad, float* m, float* v, const sl_adam_layer* layers,
+                                           int n_layers, int dtype, int step, float lr, float beta1, float beta2, float eps,
+                                           const float* grad_scale, float clipvalue, void* stream) {
+    return adam_pack_layers_impl("sl_adam_pack_layers_clipped", param, grad, m, v, layers, n_layers, dtype, step, lr, beta1,
+                                 beta2, eps, grad_scale, clipvalue, stream);
+}
+
+// FMT 0: bf16x3 (w_scale 1), FMT 1: f16x3
+template <int FMT>
+static int split_adam_pack_layers_impl(const char* who, float* param, const float* grad, float* m, float* v,
+                                       const sl_adam_layer* layers, int n_layers, int step, float lr, float beta1,
+                                       float beta2, float eps, float w_scale, const float* grad_scale, float clipvalue,
+                                       void* stream) {
+    SL_CHECK_ARG(param && grad && m && v && layers && w_scale > 0.f, "%s: null pointer or bad scale", who);
+    SL_CHECK_ARG(n_layers >= 1 && n_layers <= SL_ADAM_MAX_LAYERS && step >= 1, "%s: 1..%d layers per call", who,
                  SL_ADAM_MAX_LAYERS);
-    SL_CHECK_ARG(step >= 1 && (dtype == SL_BF16 || dtype == SL_F32), "sl_adam_pack_layers: bad step or dtype");
+    SL_CHECK_ARG(clipvalue >= 0.f, "%s: clipvalue must be >= 0 (0 = off)", who);
     AdamTable t;
     int blocks = 0;
-    const int rc = adam_table_from(layers, n_layers, "sl_adam_pack_layers", &t, &blocks);
+    const int rc = adam_table_from(layers, n_layers, who, &t, &blocks);
     if (rc != SL_OK) return rc;
     const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step));
-    if (dtype == SL_BF16)
-        hipLaunchKernelGGL((adam_pack_multi_kernel<unsigned short>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, param,
-                           grad, m, v, t, (float)lr_t, beta1, beta2, eps);
+    if (grad_scale != nullptr || clipvalue > 0.f)
+        hipLaunchKernelGGL((adam_pack_multi_kernel<unsigned short, true, 3, FMT, true>), dim3(blocks), dim3(256), 0,
+                           (hipStream_t)stream, param, grad, m, v, t, (float)lr_t, beta1, beta2, eps, w_scale, grad_scale,
+                           clipvalue);
     else
-        hipLaunchKernelGGL((adam_pack_multi_kernel<float>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, param, grad, m,
-                           v, t, (float)lr_t, beta1, beta2, eps);
-    return sl_check_launch("sl_adam_pack_layers");
+        hipLaunchKernelGGL((adam_pack_multi_kernel<unsigned short, true, 3, FMT>), dim3(blocks), dim3(256), 0,
+                           (hipStream_t)stream, param, grad, m, v, t, (float)lr_t, beta1, beta2, eps, w_scale);
+    return sl_check_launch(who);
 }
 
 extern "C" int sl_split3_adam_pack_layers(float* param, const float* grad, float* m, float* v, const sl_adam_layer* layers,
                                           int n_layers, int step, float lr, float beta1, float beta2, float eps, void* stream) {
-    SL_CHECK_ARG(param && grad && m && v && layers, "sl_split3_adam_pack_layers: null pointer");
-    SL_CHECK_ARG(n_layers >= 1 && n_layers <= SL_ADAM_MAX_LAYERS && step >= 1, "sl_split3_adam_pack_layers: 1..%d layers per call",
-                 SL_ADAM_MAX_LAYERS);
-    AdamTable t;
-    int blocks = 0;
-    const int rc = adam_table_from(layers, n_layers, "sl_split3_adam_pack_layers", &t, &blocks);
-    if (rc != SL_OK) return rc;
-    const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step));
-    hipLaunchKernelGGL((adam_pack_multi_kernel<unsigned short, true, 3>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, param,
-                       grad, m, v, t, (float)lr_t, beta1, beta2, eps, 1.f);
-    return sl_check_launch("sl_split3_adam_pack_layers");
+    return split_adam_pack_layers_impl<0>("sl_split3_adam_pack_layers", param, grad, m, v, layers, n_layers, step, lr, beta1,
+                                          beta2, eps, 1.f, nullptr, 0.f, stream);
+}
+
+extern "C" int sl_split3_adam_pack_layers_clipped(float* param, const float* grad, float* m, float* v,
+                                                  const sl_adam_layer* layers, int n_layers, int step, float lr, float beta1,
+                                                  float beta2, float eps, const float* grad_scale, float clipvalue,
+                                                  void* stream) {
+    return split_adam_pack_layers_impl<0>("sl_split3_adam_pack_layers_clipped", param, grad, m, v, layers, n_layers, step, lr,
+                                          beta1, beta2, eps, 1.f, grad_scale, clipvalue, stream);
 }
 
 extern "C" int sl_splitf16_adam_pack_layers(float* param, const float* grad, float* m, float* v, const sl_adam_layer* layers,
                                             int n_layers, int step, float lr, float beta1, float beta2, float eps,
                                             float w_scale, void* stream) {
-    SL_CHECK_ARG(param && grad && m && v && layers && w_scale > 0.f, "sl_splitf16_adam_pack_layers: null pointer or bad scale");
-    SL_CHECK_ARG(n_layers >= 1 && n_layers <= SL_ADAM_MAX_LAYERS && step >= 1, "sl_splitf16_adam_pack_layers: 1..%d layers per call",
-                 SL_ADAM_MAX_LAYERS);
-    AdamTable t;
-    int blocks = 0;
-    const int rc = adam_table_from(layers, n_layers, "sl_splitf16_adam_pack_layers", &t, &blocks);
-    if (rc != SL_OK) return rc;
-    const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step));
-    hipLaunchKernelGGL((adam_pack_multi_kernel<unsigned short, true, 3, 1>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       param, grad, m, v, t, (float)lr_t, beta1, beta2, eps, w_scale);
-    return sl_check_launch("sl_splitf16_adam_pack_layers");
+    return split_adam_pack_layers_impl<1>("sl_splitf16_adam_pack_layers", param, grad, m, v, layers, n_layers, step, lr, beta1,
+                                          beta2, eps, w_scale, nullptr, 0.f, stream);
+}
+
+extern "C" int sl_splitf16_adam_pack_layers_clipped(float* param, const float* grad, float* m, float* v,
+                                                    const sl_adam_layer* layers, int n_layers, int step, float lr, float beta1,
+                                                    float beta2, float eps, float w_scale, const float* grad_scale,
+                                                    float clipvalue, void* stream) {
+    return split_adam_pack_layers_impl<1>("sl_splitf16_adam_pack_layers_clipped", param, grad, m, v, layers, n_layers, step, lr,
+                                          beta1, beta2, eps, w_scale, grad_scale, clipvalue, stream);
 }
 
 extern "C" int sl_pack_layers(const float* param, const sl_adam_layer* layers, int n_layers, int dtype, void* stream) {
@@ -664,13 +731,170 @@ extern "C" int sl_scale(void* x, size_t n, int dtype, float scale, void* stream)
     return sl_check_launch("sl_scale");
 }
 
-extern "C" int sl_adam_step(float* param, const float* grad, float* m, float* v, size_t n, int step, float lr,
-                            float beta1, float beta2, float eps, void* stream) {
-    SL_CHECK_ARG(param && grad && m && v, "sl_adam_step: null pointer");
-    SL_CHECK_ARG(n % 4 == 0 && step >= 1, "sl_adam_step: n must be a multiple of 4 and step >= 1");
+extern "C" int sl_adam_step_clipped(float* param, const float* grad, float* m, float* v, size_t n, int step, float lr,
+                                    float beta1, float beta2, float eps, const float* grad_scale, float clipvalue,
+                                    void* stream) {
+    const char* who = (grad_scale || clipvalue != 0.f) ? "sl_adam_step_clipped" : "sl_adam_step";
+    SL_CHECK_ARG(param && grad && m && v, "%s: null pointer", who);
+    SL_CHECK_ARG(n % 4 == 0 && step >= 1, "%s: n must be a multiple of 4 and step >= 1", who);
+    SL_CHECK_ARG(clipvalue >= 0.f, "%s: clipvalue must be >= 0 (0 = off)", who);
     const double lr_t = (double)lr * sqrt(1.0 - pow((double)beta2, step)) / (1.0 - pow((double)beta1, step));
     const long n4 = (long)(n / 4);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, param, grad,
-                       m, v, n4, (float)lr_t, beta1, beta2, eps);
-    return sl_check_launch("sl_adam_step");
+    if (n4 == 0) return SL_OK;
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    if (grad_scale || clipvalue > 0.f)
+        hipLaunchKernelGGL(adam_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, param, grad, m, v, n4, (float)lr_t,
+                           beta1, beta2, eps, grad_scale, clipvalue);
+    else
+        hipLaunchKernelGGL(adam_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, param, grad, m, v, n4, (float)lr_t,
+                           beta1, beta2, eps, (const float*)nullptr, 0.f);
+    return sl_check_launch(who);
+}
+
+extern "C" int sl_adam_step(float* param, const float* grad, float* m, float* v, size_t n, int step, float lr,
+                            float beta1, float beta2, float eps, void* stream) {
+    return sl_adam_step_clipped(param, grad, m, v, n, step, lr, beta1, beta2, eps, nullptr, 0.f, stream);
+}
+
+// ---- squared gradient norm + clip factor (include/speechless_hip.h: "Gradient clipping on the device") ----------------------
+namespace {
+
+constexpr int NORM_CHUNK = 16384;  // floats per partial: 16 x 16-byte loads per thread of a 256-thread work-group
+
+struct NormTable {
+    int n;
+    int chunk_begin[SL_NORM_MAX_RANGES + 1];  // first chunk of range i (chunks count from the range's 4-float-aligned start)
+    long offset[SL_NORM_MAX_RANGES], count[SL_NORM_MAX_RANGES];
+};
+
+// fixed-order sum of the 256 per-thread doubles of a work-group (tree over LDS); the result is valid in thread 0
+__device__ __forceinline__ double block_sum_256(double (&red)[256], double acc) {
+    red[threadIdx.x] = acc;
+    __syncthreads();
+#pragma unroll
+    for (int w = 128; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+// An HBM / L2-bound read: every work-group walks whole chunks (grid-stride; the grid is sized to the CUs, the chunking is
+// not, so the partials do not depend on the grid).  Per thread 16 x f32x4 of a chunk, four loads in flight, accumulated in
+// double in index order.  The first / last vector of a range may straddle its ends: those take guarded scalar loads (a 16-byte
+// load there could also leave the allocation).
+__global__ __launch_bounds__(256) void grad_sqnorm_partial_kernel(const float* __restrict__ g, NormTable t, int n_chunks,
+                                                                  double* __restrict__ partial) {
+    __shared__ double red[256];
+    for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
+        int r = 0;
+        while (r + 1 < t.n && c >= t.chunk_begin[r + 1]) ++r;
+        const long lo = t.offset[r], hi = lo + t.count[r];
+        const long q0 = (lo >> 2) + (long)(c - t.chunk_begin[r]) * (NORM_CHUNK / 4);  // first f32x4 (absolute) of this chunk
+        double acc = 0.0;
+#pragma unroll
+        for (int u0 = 0; u0 < 16; u0 += 4) {
+            f32x4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const long e = (q0 + (long)(u0 + u) * 256 + threadIdx.x) * 4;
+                if (e >= lo && e + 4 <= hi) {
+                    v[u] = *(const f32x4*)(g + e);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[u][j] = (e + j >= lo && e + j < hi) ? g[e + j] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = fma((double)v[u][j], (double)v[u][j], acc);
+        }
+        const double s = block_sum_256(red, acc);
+        if (threadIdx.x == 0) partial[c] = s;
+        __syncthreads();  // (red is reused by the next chunk)
+    }
+}
+
+__device__ __forceinline__ void write_clip_scale(double sq, float clipnorm, float* scale, float* norm) {
+    const double n = sqrt(sq);
+    if (norm) *norm = (float)n;
+    if (scale) *scale = (clipnorm > 0.f && n >= (double)clipnorm) ? (float)((double)clipnorm / n) : 1.0f;
+}
+
+// one work-group: thread i adds partials i, i + 256, ... in that order, then the tree
+__global__ __launch_bounds__(256) void grad_sqnorm_final_kernel(const double* __restrict__ partial, int n, float clipnorm,
+                                                                double* __restrict__ sqnorm, float* norm, float* scale) {
+    __shared__ double red[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+    const double s = block_sum_256(red, acc);
+    if (threadIdx.x == 0) {
+        *sqnorm = s;
+        write_clip_scale(s, clipnorm, scale, norm);
+    }
+}
+
+__global__ void clip_scale_kernel(const double* __restrict__ sqnorm, int n_terms, float clipnorm, float* scale, float* norm) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int i = 0; i < n_terms; ++i) s += sqnorm[i];
+    write_clip_scale(s, clipnorm, scale, norm);
+}
+
+int norm_table_from(const sl_norm_range* ranges, int n_ranges, NormTable* t) {
+    long chunks = 0;
+    t->n = n_ranges;
+    for (int i = 0; i < n_ranges; ++i) {
+        if (ranges[i].offset < 0 || ranges[i].count < 0) return -1;
+        t->chunk_begin[i] = (int)chunks;
+        t->offset[i] = ranges[i].offset;
+        t->count[i] = ranges[i].count;
+        const long span = ranges[i].count ? (ranges[i].offset & 3) + ranges[i].count : 0;  // from the aligned start
+        chunks += (span + NORM_CHUNK - 1) / NORM_CHUNK;
+        if (chunks > (1L << 30)) return -1;
+    }
+    t->chunk_begin[n_ranges] = (int)chunks;
+    return (int)chunks;
+}
+
+}  // namespace
+
+extern "C" size_t sl_grad_sqnorm_workspace_bytes(const sl_norm_range* ranges, int n_ranges) {
+    NormTable t;
+    if (!ranges || n_ranges < 1 || n_ranges > SL_NORM_MAX_RANGES) return 0;
+    const int chunks = norm_table_from(ranges, n_ranges, &t);
+    return chunks < 0 ? 0 : (size_t)(chunks > 0 ? chunks : 1) * sizeof(double);
+}
+
+extern "C" int sl_grad_sqnorm(const float* grad, const sl_norm_range* ranges, int n_ranges, float clipnorm, double* sqnorm,
+                              float* norm, float* scale, void* workspace, size_t workspace_bytes, void* stream) {
+    SL_CHECK_ARG(grad && ranges && sqnorm && workspace, "sl_grad_sqnorm: null pointer");
+    SL_CHECK_ARG(n_ranges >= 1 && n_ranges <= SL_NORM_MAX_RANGES, "sl_grad_sqnorm: 1..%d ranges per call", SL_NORM_MAX_RANGES);
+    SL_CHECK_ARG(((uintptr_t)grad & 15) == 0 && ((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sqnorm & 7) == 0,
+                 "sl_grad_sqnorm: grad must be 16-byte aligned, workspace and sqnorm 8-byte aligned");
+    NormTable t;
+    const int chunks = norm_table_from(ranges, n_ranges, &t);
+    SL_CHECK_ARG(chunks >= 0, "sl_grad_sqnorm: a range has a negative offset or count (or the table is too long)");
+    if (workspace_bytes < (size_t)(chunks > 0 ? chunks : 1) * sizeof(double)) {
+        sl_set_error("sl_grad_sqnorm: workspace too small");
+        return SL_ERR_WORKSPACE_TOO_SMALL;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (chunks > 0) {
+        const int grid = chunks < sl_cus() * 8 ? chunks : sl_cus() * 8;  // eight 4-wave work-groups per CU hide the HBM latency
+        hipLaunchKernelGGL(grad_sqnorm_partial_kernel, dim3(grid), dim3(256), 0, s, grad, t, chunks, (double*)workspace);
+        const int rc = sl_check_launch("sl_grad_sqnorm(partial)");
+        if (rc != SL_OK) return rc;
+    }
+    hipLaunchKernelGGL(grad_sqnorm_final_kernel, dim3(1), dim3(256), 0, s, (const double*)workspace, chunks, clipnorm, sqnorm,
+                       norm, scale);
+    return sl_check_launch("sl_grad_sqnorm(final)");
+}
+
+extern "C" int sl_clip_scale(const double* sqnorm, int n_terms, float clipnorm, float* scale, float* norm, void* stream) {
+    SL_CHECK_ARG(sqnorm && (scale || norm), "sl_clip_scale: null pointer");
+    SL_CHECK_ARG(n_terms >= 1 && n_terms <= 1024, "sl_clip_scale: 1..1024 terms");
+    hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, sqnorm, n_terms, clipnorm, scale, norm);
+    return sl_check_launch("sl_clip_scale");
 }

@@ -36,7 +36,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
     FRONT_DGRAD_EXTRA_ROWS = 17   # pair rows computed beyond the output frames: up to row T' + 23 = the last frame's
 
     def __init__(self, specs, grapheme_set_size, dtype="bf16", device="cuda:0", ctc_epsilon=1e-8,
-                 frozen_layer_count=0, lr=1e-4, beta_1=0.9, beta_2=0.999, adam_epsilon=1e-8, forward_only=False):
+                 frozen_layer_count=0, lr=1e-4, beta_1=0.9, beta_2=0.999, adam_epsilon=1e-8, forward_only=False,
+                 clipnorm=0.0, clipvalue=0.0, decay=0.0, track_grad_norm=False):
         if not torch.cuda.is_available():
             raise _lib.HipLibraryError("speechless_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                                        "there is no CPU fallback for the hot path")
@@ -87,6 +88,21 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.frozen_layer_count = frozen_layer_count
         self.lr, self.beta_1, self.beta_2, self.adam_epsilon = lr, beta_1, beta_2, adam_epsilon
         self.adam_iterations = 0
+        # What every Keras 2.0 optimizer takes besides its own hyper-parameters (optimizers.py: Optimizer.get_gradients, the
+        # `decay` of Adam.get_updates; include/speechless_hip.h "Gradient clipping on the device").  0 = off, and with all
+        # three off the step launches exactly what it launched before they existed.
+        #   clipnorm: the gradients of the trainable layers scaled by clipnorm / n when their global L2 norm n >= clipnorm --
+        #     n is reduced on the device behind the last gradient of backward (sl_grad_sqnorm), the Adam launches read the
+        #     factor from device memory: no host synchronisation, the recorded step replays it
+        #   clipvalue: each element clamped to [-clipvalue, clipvalue] afterwards, inside the Adam kernels
+        #   decay: lr = lr0 / (1 + decay * adam_iterations), on the host (adam_iterations is part of the optimizer state)
+        # track_grad_norm: reduce n even without clipnorm (grad_norm).  The gradient buffer is never rewritten.
+        self.clipnorm, self.clipvalue, self.decay = float(clipnorm or 0.0), float(clipvalue or 0.0), float(decay or 0.0)
+        if self.clipnorm < 0 or self.clipvalue < 0 or self.decay < 0:
+            raise ValueError("clipnorm, clipvalue and decay must be >= 0 (0 = off)")
+        self.track_grad_norm = bool(track_grad_norm)
+        self._norm_sq = self._norm_out = self._norm_ws = None  # device double; device floats (n, scale); partial sums
+        self._norm_tables = {}
         for i, s in enumerate(specs):
             if s.stride not in (1, 2) or (s.stride == 2 and i != 0):
                 raise NotImplementedError("only the first layer may stride (spectrogram-input stack, net.py:317)")
@@ -848,7 +864,16 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                                         tuple(sorted(self.nt_cfg.items())),
                                         buf.t_out if self.planes > 1 else None)  # (bf16x3 helpers take it by value)
         try:
-            self._run_recorded(buf, key, lambda: self._backward_eager(buf, main, side, on_bucket_ready), on_bucket_ready)
+            norm = self._norm_wanted() and on_bucket_ready is None  # (data parallel: behind the exchange, train_step_resident)
+            if norm:
+                key = key and key + ("norm", self.clipnorm)
+                self._norm_buffers(self._trainable_ranges())  # (allocated before a list keeps their pointers)
+
+            def eager():
+                self._backward_eager(buf, main, side, on_bucket_ready)
+                if norm:  # every gradient is complete on the main stream here
+                    self._launch_grad_norm(self._trainable_ranges(), main.cuda_stream)
+            self._run_recorded(buf, key, eager, on_bucket_ready)
         except BaseException:
             if on_bucket_ready is not None and self.comm_cus:
                 # raised between setting and clearing the CU hint: the library's setting is process-wide state shared by
@@ -1145,14 +1170,104 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.adam_iterations += 1
         st = self._stream()
         if not fused:
-            self._launch("adam", "sl_adam_step", self.params.data_ptr(), self.grads.data_ptr(),
-                         self.adam_m.data_ptr(), self.adam_v.data_ptr(), self.param_numel, self.adam_iterations,
-                         self.lr, self.beta_1, self.beta_2, self.adam_epsilon, st)
+            self._launch_adam_flat("adam", 0, self.param_numel, st)
             self._packed_dirty = True
             return
         if self._packed_dirty:
             self.repack_weights()  # frozen layers keep these copies; trainable ones are rewritten below
         self._adam_layers(self._trainable_layers(), st)
+
+    def _lr_now(self):
+        """the learning rate of the update being launched (self.adam_iterations already counts it): Keras 2.0 Adam's
+        lr * 1 / (1 + decay * iterations) with iterations = the updates completed before this one"""
+        if not self.decay:
+            return self.lr
+        return self.lr * (1.0 / (1.0 + self.decay * (self.adam_iterations - 1)))
+
+    def _clip_args(self):
+        """(grad_scale device pointer or None, clipvalue) of the clipped Adam twins, or None: launch the originals"""
+        if not (self.clipnorm > 0 or self.clipvalue > 0):
+            return None
+        return (self._norm_out[1:].data_ptr() if self.clipnorm > 0 else None, self.clipvalue)
+
+    def _launch_adam_flat(self, tag, lo, hi, st):
+        """plain elementwise Adam on [lo, hi) of the flat buffers (the unfused step; a rank's slice under the sharded optimizer)"""
+        what = (self.params[lo:hi].data_ptr(), self.grads[lo:hi].data_ptr(), self.adam_m[lo:hi].data_ptr(),
+                self.adam_v[lo:hi].data_ptr(), hi - lo, self.adam_iterations, self._lr_now(), self.beta_1, self.beta_2,
+                self.adam_epsilon)
+        clip = self._clip_args()
+        if clip is None:
+            self._launch(tag, "sl_adam_step", *what, st)
+        else:
+            self._launch(tag, "sl_adam_step_clipped", *what, *clip, st)
+
+    # ------------------------------------------------------------------ gradient norm (clipnorm, track_grad_norm)
+
+    def _norm_wanted(self):
+        return (self.clipnorm > 0 or self.track_grad_norm) and not self.forward_only
+
+    @property
+    def grad_norm(self):
+        """0-d device tensor (fp32, not synchronised): the global L2 norm of the trainable layers' gradients of the last
+        backward pass / step, before any clipping; None unless clipnorm > 0 or track_grad_norm"""
+        if not self._norm_wanted():
+            return None
+        self._norm_buffers(self._trainable_ranges())
+        return self._norm_out[0]
+
+    def _trainable_ranges(self):
+        """[lo, hi) ranges of the flat gradient buffer that hold the trainable layers (frozen layers contribute nothing).
+        Whole padded blocks: every padding element of the gradient buffer is zero once backward has run (padded channels
+        carry zeros through every GEMM; the ones-channel rows are zeroed by sl_bias_grad_from_wgrad) --
+        tests/test_gpu_optimizer_clip.py holds the norm over these ranges to the norm of the logical elements."""
+        out = []
+        for i in self._trainable_layers():
+            p = self.all_plans[i]
+            lo, hi = p.w_off, p.b_off + p.cout_pad
+            if out and out[-1][1] == lo:
+                out[-1] = (out[-1][0], hi)
+            else:
+                out.append((lo, hi))
+        return out
+
+    def _norm_table(self, ranges):
+        key = tuple(ranges)
+        table = self._norm_tables.get(key)
+        if table is None:
+            if not 1 <= len(key) <= 16:
+                raise ValueError("the gradient norm takes 1 .. 16 ranges per launch")
+            table = (_lib.NormRange * len(key))()
+            for entry, (lo, hi) in zip(table, key):
+                entry.offset, entry.count = lo, hi - lo
+            self._norm_tables[key] = table
+        return table
+
+    def _norm_buffers(self, ranges):
+        """the device scalars (allocated once: recorded launches keep their pointers) and a workspace that covers `ranges`"""
+        if self._norm_sq is None:
+            self._norm_sq = torch.zeros((1,), dtype=torch.float64, device=self.device)
+            self._norm_out = torch.zeros((2,), dtype=torch.float32, device=self.device)  # n, clip factor
+            self._norm_out[1] = 1.0
+        table = self._norm_table(ranges)
+        need = self.lib.raw("sl_grad_sqnorm_workspace_bytes")(table, len(table))
+        if self._norm_ws is None or self._norm_ws.numel() * 8 < need:
+            self._norm_ws = torch.empty(((need + 7) // 8,), dtype=torch.float64, device=self.device)
+            for buf in self._buffers.values():
+                buf.launch_lists.clear()  # (recorded backward lists hold the old workspace pointer)
+        return table
+
+    def _launch_grad_norm(self, ranges, st, finish=True):
+        """sum of g * g over `ranges` of the gradient buffer into the device double; finish: also n and the clip factor (one
+        process holds the whole gradient) -- else the caller all-reduces the double and calls _launch_clip_scale"""
+        table = self._norm_buffers(ranges)
+        out = self._norm_out
+        self._launch("grad_norm", "sl_grad_sqnorm", self.grads.data_ptr(), table, len(table), self.clipnorm,
+                     self._norm_sq.data_ptr(), out.data_ptr() if finish else None, out[1:].data_ptr() if finish else None,
+                     self._norm_ws.data_ptr(), self._norm_ws.numel() * 8, st)
+
+    def _launch_clip_scale(self, st):
+        self._launch("clip_scale", "sl_clip_scale", self._norm_sq.data_ptr(), 1, self.clipnorm, self._norm_out[1:].data_ptr(),
+                     self._norm_out.data_ptr(), st)
 
     def _trainable_layers(self):
         """internal indices of the layers the optimizer updates (the front layer, if any, has index len(plans))"""
@@ -1188,15 +1303,17 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             tag = "adam:{}..{}".format(self.all_plans[chunk[0]].spec.name, self.all_plans[chunk[-1]].spec.name)
             what = (self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), table,
                     len(chunk))
-            how = (self.adam_iterations, self.lr, self.beta_1, self.beta_2, self.adam_epsilon)
+            how = (self.adam_iterations, self._lr_now(), self.beta_1, self.beta_2, self.adam_epsilon)
+            clip = self._clip_args()  # None: the original entry points, with the arguments they always had
+            twin, clip = ("_clipped", clip) if clip is not None else ("", ())
             if self.planes == 3 and self.x3_f16:
-                self._launch(tag, "sl_splitf16_adam_pack_layers", *what, *how, self.w_scale, st)
+                self._launch(tag, "sl_splitf16_adam_pack_layers" + twin, *what, *how, self.w_scale, *clip, st)
             elif self.planes == 3:  # bf16x3: the [w_hi | w_hi | w_lo] operand rows are rewritten in the same pass
-                self._launch(tag, "sl_split3_adam_pack_layers", *what, *how, st)
+                self._launch(tag, "sl_split3_adam_pack_layers" + twin, *what, *how, *clip, st)
                 if 0 in chunk and self.w_dgrad[0] is not None:
                     self._pack_pair_dgrad_x3(st)
             else:
-                self._launch(tag, "sl_adam_pack_layers", *what, self.dtype_code, *how, st)
+                self._launch(tag, "sl_adam_pack_layers" + twin, *what, self.dtype_code, *how, *clip, st)
 
     def train_step(self, input_batch, label_batch, label_lengths, prediction_lengths, reducer=None):
         """One full optimisation step (forward, CTC, backward, [gradient all-reduce], Adam, weight repack).
@@ -1231,6 +1348,16 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.adam_iterations += 1
         st = self._stream()
         plan = self.bucket_plan()
+        if self._norm_wanted():
+            # the norm needs every reduced gradient before any layer is updated: wait for ALL buckets here (the bucket-by-bucket
+            # overlap of exchange and update below is given up; the waits below find nothing outstanding)
+            reducer.wait_all()
+            if not reducer.shard_optimizer:  # every rank reduces the same reduced buffer in the same order: the same bits
+                self._launch_grad_norm(self._trainable_ranges(), st)  # (= the buckets' layers, in the single process's order)
+            else:  # this rank's slices, then ONE scalar all-reduce (sum, double) through the reducer's process group
+                self._launch_grad_norm([reducer.shard_of(lo, hi) for _, (lo, hi) in plan], st, finish=False)
+                reducer.all_reduce_scalar(self._norm_sq)
+                self._launch_clip_scale(st)
         if not reducer.shard_optimizer:
             for layers, _ in plan:
                 reducer.wait_next()
@@ -1242,9 +1369,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         for b, (layers, (lo, hi)) in enumerate(plan):
             reducer.wait_next()
             slo, shi = reducer.shard_of(lo, hi)
-            self._launch("adam_shard:{}".format(b), "sl_adam_step", self.params[slo:shi].data_ptr(),
-                         self.grads[slo:shi].data_ptr(), self.adam_m[slo:shi].data_ptr(), self.adam_v[slo:shi].data_ptr(),
-                         shi - slo, self.adam_iterations, self.lr, self.beta_1, self.beta_2, self.adam_epsilon, st)
+            self._launch_adam_flat("adam_shard:{}".format(b), slo, shi, st)
             reducer.gather_bucket(b, self.params)
         for layers, _ in plan:
             reducer.wait_next()

@@ -50,10 +50,22 @@ def edit_distance(a, b):
 
 
 class Adam:
-    """Hyper-parameters of keras.optimizers.Adam as the reference constructs it (net.py:132: Adam(1e-4))."""
+    """Hyper-parameters of keras.optimizers.Adam as the reference constructs it (net.py:132: Adam(1e-4)), with what Keras
+    2.0 lets a user add: Adam's own `decay` (lr / (1 + decay * iterations)) and the `clipnorm` / `clipvalue` every Keras
+    optimizer accepts (global-norm scaling, then element clamp).  0 = off.  Restated from knowledge of Keras 2.0.x
+    (optimizers.py), like the update itself; not checkable offline."""
 
-    def __init__(self, lr=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-8):
+    def __init__(self, lr=1e-4, beta_1=0.9, beta_2=0.999, epsilon=1e-8, decay=0.0, clipnorm=0.0, clipvalue=0.0):
         self.lr, self.beta_1, self.beta_2, self.epsilon = lr, beta_1, beta_2, epsilon
+        self.decay, self.clipnorm, self.clipvalue = decay, clipnorm, clipvalue
+
+
+def optimizer_settings(optimizer):
+    """The Engine keyword arguments an optimizer object stands for: lr, beta_1, beta_2, epsilon as they always were read,
+    and decay / clipnorm / clipvalue where the object has them (a Keras optimizer carries clipnorm / clipvalue only when
+    they were given: absent = 0 = off)."""
+    extra = {name: float(getattr(optimizer, name, 0.0) or 0.0) for name in ("decay", "clipnorm", "clipvalue")}
+    return dict(lr=optimizer.lr, beta_1=optimizer.beta_1, beta_2=optimizer.beta_2, adam_epsilon=optimizer.epsilon, **extra)
 
 
 class LabeledSpectrogram:
@@ -245,7 +257,7 @@ class Wav2Letter:
                  asg_initial_probabilities=None, kenlm_directory=None,
                  # --- extensions of this implementation (keyword-only in spirit) ---
                  compute_dtype=None, device="cuda:0", seed=None, ctc_epsilon=1e-8, layer_sizes=None,
-                 load_optimizer_state=False, eval_dtype=None, beam_search_device="host"):
+                 load_optimizer_state=False, eval_dtype=None, beam_search_device="host", track_gradient_norm=False):
         if frozen_layer_count > 0 and load_model_from_directory is None:
             raise ValueError("Layers cannot be frozen if model is trained from scratch.")
         if use_asg:
@@ -286,9 +298,8 @@ class Wav2Letter:
                                        activation=activation, output_activation=output_activation,
                                        use_raw_wave_input=use_raw_wave_input, **self._layer_sizes)
         self.engine = Engine(specs, self.grapheme_encoding.grapheme_set_size, dtype=compute_dtype, device=device,
-                             ctc_epsilon=ctc_epsilon, frozen_layer_count=frozen_layer_count, lr=self.optimizer.lr,
-                             beta_1=self.optimizer.beta_1, beta_2=self.optimizer.beta_2,
-                             adam_epsilon=self.optimizer.epsilon)
+                             ctc_epsilon=ctc_epsilon, frozen_layer_count=frozen_layer_count,
+                             track_grad_norm=track_gradient_norm, **optimizer_settings(self.optimizer))
         self.engine.dropout_rate = dropout if dropout else None  # applied by training steps only (learning phase 1)
         # the reference signature has no seed: a plain Wav2Letter(..., dropout=0.1) draws one (Keras does the same)
         self.engine.dropout_seed = int(seed) if seed is not None else \
@@ -596,6 +607,12 @@ class Wav2Letter:
                                         reducer=reducer)
         mean = losses.mean()  # new tensor: safe against the next step overwriting the loss buffer
         return mean if lazy else float(mean.item())
+
+    def last_gradient_norm(self):
+        """Global L2 norm of the gradients of the last training step, before clipping (a float: synchronises), or None when
+        it is not tracked -- it is with an optimizer that has clipnorm > 0, or track_gradient_norm=True."""
+        norm = self.engine.grad_norm
+        return None if norm is None else float(norm.item())
 
     def _pack_for_staging(self, labeled_spectrogram_batch):
         """The host half of train_on_batch for pipeline.BatchStager: everything but the padded input array."""

@@ -124,6 +124,14 @@ class GradBucketReducer:
         else:
             dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group)
 
+    def all_reduce_scalar(self, tensor):
+        """Sum all-reduce of a small tensor over the reducer's process group, in place, ordered on the CURRENT stream behind
+        what is enqueued there and in front of what follows (the sharded optimizer's squared gradient norm: one double per
+        rank, each the sum over that rank's slices -- Engine.train_step_resident).  A world of one rank keeps its value."""
+        if self.world_size == 1 or self.skip_collective:
+            return
+        dist.all_reduce(tensor, op=dist.ReduceOp.SUM, group=self.group)
+
     def wait_next(self):
         """Makes the current stream (or the host, on CPU) wait for the OLDEST outstanding bucket only."""
         if not self._pending:
