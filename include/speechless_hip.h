@@ -129,6 +129,10 @@ int sl_conv1d_chain_supported(const sl_conv_geom* geom, int n_layers, int dtype)
 /* Measurement / test hook: output frames per work-group of sl_conv1d_chain.  0 (default) = chosen per launch (64, or 48 where
  * that fills the chip's rounds of 256 work-groups better: long utterances in small batches), 48 / 64 = forced.  Process-wide. */
 int sl_conv1d_chain_select(int tile_rows);
+/* Measurement / test hook: the output frames per work-group (48 or 64) that sl_conv1d_chain would choose for this geometry
+ * on the calling thread right now (sl_conv1d_chain_select, sl_set_available_cus); 0 when the run does not fit the kernel.
+ * Launches nothing. */
+int sl_conv1d_chain_plan(const sl_conv_geom* geom, int n_layers, int dtype);
 int sl_conv1d_chain(const void* x, void* const* ys, const void* const* ws, const float* const* biases,
                     const void* const* masks, const sl_conv_geom* geom, int n_layers, int epilogue, int dtype,
                     void* stream);
@@ -211,6 +215,11 @@ typedef struct sl_wgrad_job {
 size_t sl_conv1d_wgrad_multi_workspace_bytes(const sl_wgrad_job* jobs, int n_jobs, int dtype);
 int sl_conv1d_wgrad_multi(const sl_wgrad_job* jobs, int n_jobs, int dtype, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* Measurement / test hook: the plan sl_conv1d_wgrad_multi would launch for these jobs on the calling thread right now
+ * (sl_set_available_cus): *segs = segments per tile (2 * CUs / tiles, at most batch * ceil(t_out / 64), at least 1), *workers
+ * = work-groups of the main kernel (tiles * (segs / 2), plus ceil(tiles / 2) when segs is odd).  Either pointer may be NULL;
+ * the jobs' pointers are not read.  Launches nothing. */
+int sl_conv1d_wgrad_multi_plan(const sl_wgrad_job* jobs, int n_jobs, int dtype, int* segs, int* workers);
 
 /* bias gradient db[co] = sum_{b,t} g[b][g_row0+t][co] (fp32 out, deterministic two-stage).  Same autodiff site. */
 size_t sl_bias_grad_workspace_bytes(const sl_conv_geom* geom);

@@ -99,6 +99,7 @@ SIGNATURES = {
                              c_int, c_void_p, c_size_t, c_void_p]),
     "sl_conv1d_chain_supported": (c_int, [POINTER(ConvGeom), c_int, c_int]),
     "sl_conv1d_chain_select": (c_int, [c_int]),
+    "sl_conv1d_chain_plan": (c_int, [POINTER(ConvGeom), c_int, c_int]),
     "sl_conv1d_chain": (c_int, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                 POINTER(ConvGeom), c_int, c_int, c_int, c_void_p]),
     "sl_conv1d_wgrad_workspace_bytes": (c_size_t, [POINTER(ConvGeom), c_int, c_int]),
@@ -164,6 +165,7 @@ SIGNATURES = {
     "sl_split3_bias_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_size_t, c_void_p]),
     "sl_conv1d_wgrad_multi_workspace_bytes": (c_size_t, [POINTER(WgradJob), c_int, c_int]),
     "sl_conv1d_wgrad_multi": (c_int, [POINTER(WgradJob), c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "sl_conv1d_wgrad_multi_plan": (c_int, [POINTER(WgradJob), c_int, c_int, POINTER(c_int), POINTER(c_int)]),
     "sl_pack_layers": (c_int, [c_void_p, POINTER(AdamLayer), c_int, c_int, c_void_p]),
     "sl_splitf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int64, c_int, c_void_p]),
     "sl_splitf16_pack_input": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),

@@ -312,12 +312,14 @@ class _Buffers:
         bias_ws = eng._max_over_cu_hints(lambda: max(
             [0] + [L.raw("sl_bias_grad_workspace_bytes")(ctypes.byref(self.wgrad_geom[p.index])) for p in eng.plans[first:]]))
         self.size_nt_workspace(eng, self.dgrad_geom, "dgrad")
-        if eng.front_plan is not None:
+        if eng.front_plan is not None:  # (the front layer's launches run under the CU hint too: every setting in use)
             for g in (self.front_geom, self.front_stage_geom, self.front_dgrad_geom):
                 if g is not None:
-                    self.grow("nt_ws", L.raw("sl_conv1d_nt_workspace_bytes")(ctypes.byref(g), eng.dtype_code, 0))
+                    self.grow("nt_ws", eng._max_over_cu_hints(
+                        lambda: L.raw("sl_conv1d_nt_workspace_bytes")(ctypes.byref(g), eng.dtype_code, 0)))
             for g in ((self.front_wgrad_geom_a, self.front_wgrad_geom_b) if eng.planes > 1 else (self.front_geom,)):
-                ws_bytes = max(ws_bytes, L.raw("sl_conv1d_wgrad_workspace_bytes")(ctypes.byref(g), eng.dtype_code, 0))
+                ws_bytes = max(ws_bytes, eng._max_over_cu_hints(
+                    lambda: L.raw("sl_conv1d_wgrad_workspace_bytes")(ctypes.byref(g), eng.dtype_code, 0)))
             bias_ws = max(bias_ws, L.raw("sl_bias_grad_workspace_bytes")(ctypes.byref(self.front_geom)))
         if eng.planes > 1:
             need = max(p.taps_view * (self.wgrad_geom[p.index].cin + self.wgrad_geom_b[p.index].cin) * p.cout_pad
@@ -326,15 +328,16 @@ class _Buffers:
                 need = max(need, 3 * eng.front_plan.cin_pad * eng.front_plan.cout_pad)
             if self.wgrad_r is None or self.wgrad_r.numel() < need:
                 self.wgrad_r = torch.empty((need,), dtype=torch.float32, device=eng.device)
-            for p in eng.plans[first:]:
-                ws_bytes = max(ws_bytes, L.raw("sl_conv1d_wgrad_workspace_bytes")(
-                    ctypes.byref(self.wgrad_geom_b[p.index]), eng.dtype_code, 0))
+            # (the second launch of a layer and the grouped launch split by the same chooser: every CU setting in use)
+            ws_bytes = max(ws_bytes, eng._max_over_cu_hints(lambda: max(
+                [0] + [L.raw("sl_conv1d_wgrad_workspace_bytes")(ctypes.byref(self.wgrad_geom_b[p.index]), eng.dtype_code, 0)
+                       for p in eng.plans[first:]])))
         if eng.dtype == "bf16":
             for (s0, e0) in eng.runs:
                 lo = max(s0, first)
                 if e0 > lo:
-                    ws_bytes = max(ws_bytes, L.raw("sl_conv1d_wgrad_grouped_workspace_bytes")(
-                        ctypes.byref(self.wgrad_geom[lo]), e0 - lo + 1, 0))
+                    ws_bytes = max(ws_bytes, eng._max_over_cu_hints(lambda: L.raw("sl_conv1d_wgrad_grouped_workspace_bytes")(
+                        ctypes.byref(self.wgrad_geom[lo]), e0 - lo + 1, 0)))
         self.grow("wgrad_ws", ws_bytes, 16)
         self.grow("bias_ws", bias_ws, 16)
         last = len(eng.plans) - 1

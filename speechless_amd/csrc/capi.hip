@@ -102,6 +102,11 @@ extern "C" int sl_conv1d_chain_supported(const sl_conv_geom* geom, int n_layers,
     return geom != nullptr && dtype == SL_BF16 && geom->batch > 0 && geom->t_out > 0 && conv_chain_bf16_supported(geom, n_layers);
 }
 
+extern "C" int sl_conv1d_chain_plan(const sl_conv_geom* geom, int n_layers, int dtype) {
+    if (!sl_conv1d_chain_supported(geom, n_layers, dtype)) return 0;
+    return conv_chain_plan_tile_rows(geom, n_layers);
+}
+
 extern "C" int sl_conv1d_chain(const void* x, void* const* ys, const void* const* ws, const float* const* biases,
                                const void* const* masks, const sl_conv_geom* geom, int n_layers, int epilogue, int dtype,
                                void* stream) {
@@ -156,6 +161,15 @@ extern "C" int sl_conv1d_wgrad(const void* x, const void* g, float* dw, const sl
 extern "C" size_t sl_conv1d_wgrad_multi_workspace_bytes(const sl_wgrad_job* jobs, int n_jobs, int dtype) {
     if (!jobs || (dtype != SL_BF16 && dtype != SL_F16)) return 0;
     return dtype == SL_F16 ? wgrad_multi_f16_workspace_bytes(jobs, n_jobs) : wgrad_multi_bf16_workspace_bytes(jobs, n_jobs);
+}
+
+extern "C" int sl_conv1d_wgrad_multi_plan(const sl_wgrad_job* jobs, int n_jobs, int dtype, int* segs, int* workers) {
+    SL_CHECK_ARG(jobs != nullptr, "sl_conv1d_wgrad_multi_plan: jobs is null");
+    if (dtype != SL_BF16 && dtype != SL_F16) {
+        sl_set_error("sl_conv1d_wgrad_multi_plan: bf16 / f16 only");
+        return SL_ERR_UNSUPPORTED;
+    }
+    return wgrad_multi_plan(jobs, n_jobs, segs, workers);
 }
 
 extern "C" int sl_conv1d_wgrad_multi(const sl_wgrad_job* jobs, int n_jobs, int dtype, void* workspace,

@@ -137,6 +137,7 @@ bool conv_chain_bf16_supported(const sl_conv_geom* g, int n_layers);
 int conv_chain_bf16(const void* x, void* const* ys, const void* const* ws, const float* const* biases,
                     const void* const* masks, const sl_conv_geom* g, int n_layers, int epilogue, hipStream_t s);
 int conv_chain_select(int rows);
+int conv_chain_plan_tile_rows(const sl_conv_geom* g, int n_layers);  // what the next launch would choose (launches nothing)
 bool output_softmax_supported(const sl_conv_geom* g, int k);
 int output_softmax_select(int variant);
 int output_softmax_bf16(const void* x, const void* w, const float* bias, float* probs, float* logq, float* logits,
@@ -154,6 +155,7 @@ int conv1x1_bwd_bf16(const void* x, const void* gr, const void* w_dgrad, void* d
                      int epilogue, int cfg, int accumulate, void* ws, size_t ws_bytes, hipStream_t s);
 size_t wgrad_multi_bf16_workspace_bytes(const sl_wgrad_job* jobs, int n_jobs);
 int wgrad_multi_bf16(const sl_wgrad_job* jobs, int n_jobs, void* ws, size_t ws_bytes, hipStream_t s);
+int wgrad_multi_plan(const sl_wgrad_job* jobs, int n_jobs, int* segs, int* workers);  // segments per tile / work-groups (launches nothing)
 // the same entry points of the -DSL_ELEM_F16 translation units (fp16 operands: SL_F16)
 int conv_nt_f16(const void* x, const void* w, const float* bias, const void* mask, void* y, const sl_conv_geom* g,
                 int epilogue, int out_f32, int cfg, void* workspace, size_t workspace_bytes, hipStream_t s);

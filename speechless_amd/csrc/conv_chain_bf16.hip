@@ -481,6 +481,10 @@ static int chain_tile_rows(int batch, int t_out, int taps, int n_layers) {
     return best;
 }
 
+int conv_chain_plan_tile_rows(const sl_conv_geom* g, int n_layers) {
+    return chain_tile_rows(g->batch, g->t_out, g->taps, n_layers);
+}
+
 int conv_chain_bf16(const void* x, void* const* ys, const void* const* ws, const float* const* biases,
                     const void* const* masks, const sl_conv_geom* g, int n_layers, int epilogue, hipStream_t s) {
     ChainArgs a;

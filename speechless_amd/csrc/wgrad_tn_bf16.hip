@@ -1202,6 +1202,17 @@ size_t wgrad_multi_bf16_workspace_bytes(const sl_wgrad_job* jobs, int n_jobs) {
     return (size_t)(256 + a.total_tiles) * 2 * 256 * 256 * sizeof(float);
 }
 
+#if !defined(SL_ELEM_F16)  // (the plan is the same for both element types: one copy)
+int wgrad_multi_plan(const sl_wgrad_job* jobs, int n_jobs, int* segs, int* workers) {
+    MultiArgs a;
+    const int rc = multi_fill(jobs, n_jobs, &a);
+    if (rc != SL_OK) return rc;
+    if (segs) *segs = a.segs;
+    if (workers) *workers = a.workers;
+    return SL_OK;
+}
+#endif
+
 int wgrad_multi_bf16(const sl_wgrad_job* jobs, int n_jobs, void* ws, size_t ws_bytes, hipStream_t s) {
     MultiArgs a;
     int rc = multi_fill(jobs, n_jobs, &a);

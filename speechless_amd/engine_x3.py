@@ -129,6 +129,7 @@ class X3Mixin:
         main = torch.cuda.current_stream(self.device)
         plan = self.bucket_plan() if on_bucket_ready is not None else []
         bucket_at = {layers[0]: (b, layers) for b, (layers, _) in enumerate(plan)}
+        hint = on_bucket_ready is not None and self.comm_cus  # (as _backward_eager: the choosers plan for 256 - comm_cus)
         # the runs of identical layers (inner_conv_1..7): their 2 x 7 partial weight gradients (x planes against g_hi, against
         # g_lo) in ONE balanced launch (sl_conv1d_wgrad_multi, a job per partial) at the lowest layer of the run -- they
         # were 14 launches of 31 us + their reductions, 0.6 ms of the 6.8 ms step
@@ -182,6 +183,8 @@ class X3Mixin:
                 if rows:
                     self._bias_grads_from_wgrad(rows, bool(ones_db), main)
                 self._bucket_ready(on_bucket_ready, b)
+                if hint and b == 0:  # from here on communication kernels may own CUs
+                    self._eager_op(self._set_cu_hint, 256 - self.comm_cus)
             dropped_in = buf.dropped and i in self._dropout_layers()  # a Dropout sits between y[i - 1] and layer i
             elu = i > first and self.specs[i - 1].activation == "elu"
             # a stored zero is ambiguous behind an ELU: plain input gradient (no mask), then both factors of the chain rule with
@@ -214,6 +217,8 @@ class X3Mixin:
             if on_bucket_ready is not None:  # the front layer's parameters: the last bucket of bucket_plan()
                 b = len(self.bucket_plan()) - 1
                 self._bucket_ready(on_bucket_ready, b)
+        if hint:
+            self._eager_op(self._set_cu_hint, 0)
 
     def _wgrad_multi_layers_x3(self, first):
         """bf16x3: no launch writes the weight gradients of the striding layer AND of a run (bucket_plan() merges nothing)"""
