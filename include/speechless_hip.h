@@ -379,6 +379,32 @@ int sl_ctc_beam_search(const float* probs, const int32_t* lengths, int batch, in
                        int merge_repeated, float eps, const sl_beam_lm* lm, int32_t* out, int32_t* out_len,
                        float* log_prob, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- letter and word error counts: the two editdistance.eval calls of the reference's result object (speechless/net.py:
+ *      31-37, over the characters and over the .split() of expected / predicted), on index rows that are in HBM already. ----
+ * a: int32[batch] rows a_stride apart, the expected indices (the labels of sl_ctc_loss_grad); b: likewise b_stride apart,
+ * the predicted indices (`out` of sl_greedy_decode); a_len, b_len: int32[batch].  Entries at or past a row's length are
+ * never read, whatever they hold.
+ *   letter_errors[i] = Levenshtein distance (unit costs) between a[i][:a_len[i]] and b[i][:b_len[i]];
+ *   word_errors[i]   = the same between their word sequences.  A word is a maximal run of indices != space -- str.split() for
+ *     an alphabet whose only whitespace character sits at index `space`: leading, trailing and repeated separators yield no
+ *     empty words.  Two words are equal iff they have the same length and the same indices (compared index by index: exact).
+ *     space < 0: no separator, every non-empty row is one word;
+ *   a_word_count[i]  = number of words of a[i] (the denominator of the word error rate); may be NULL.
+ * Integers only; any index values (the symbols are only compared, so the grapheme set size does not enter).
+ * Errors.  What the host can see is refused before anything is launched: SL_ERR_INVALID_ARGUMENT for batch <= 0, a negative
+ * maximum, a null pointer, or a maximum above its row stride (a length up to it would leave the row).  The lengths themselves
+ * are in HBM and the call does not synchronise: a row whose a_len / b_len lies outside [0, a_max] / [0, b_max] reads nothing
+ * and reports -1 in all three outputs of that row -- a code per utterance, no fault; the other rows are unaffected.
+ * Limits: a_max <= 1024 (64 lanes x 16 columns of the DP row in registers), and both rows with their word spans in 64 KiB of
+ * LDS, 8 (a_max + b_max) + 16 bytes at most. The engine's shapes (labels <= 200, predictions <= T' = 500..4000) are far
+ * inside; anything larger is REJECTED with SL_ERR_UNSUPPORTED, and sl_edit_distance_supported(a_max, b_max) tells in advance
+ * (1 / 0) -- the Python layer counts such a batch on the host.  No workspace.  One work-group of two waves per utterance: the
+ * letter pass and the word pass run side by side. */
+int sl_edit_distance_supported(int a_max, int b_max);
+int sl_edit_distance(const int32_t* a, const int32_t* a_len, int a_stride, const int32_t* b, const int32_t* b_len,
+                     int b_stride, int batch, int a_max, int b_max, int space, int32_t* letter_errors,
+                     int32_t* word_errors, int32_t* a_word_count, void* stream);
+
 /* The same fused update for SEVERAL layers in one launch (the small layers' launches are pure latency): layer i's
  * block starts `offset` floats into param / grad / m / v (weights [k][cin_pad][cout_pad] followed by cout_pad biases). */
 #define SL_ADAM_MAX_LAYERS 16

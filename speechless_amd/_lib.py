@@ -129,6 +129,9 @@ SIGNATURES = {
     "sl_ctc_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sl_ctc_align": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_void_p, c_size_t, c_void_p]),
+    "sl_edit_distance_supported": (c_int, [c_int, c_int]),
+    "sl_edit_distance": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                 c_void_p, c_void_p, c_void_p]),
     "sl_ctc_beam_search_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "sl_ctc_beam_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, POINTER(BeamLm),
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

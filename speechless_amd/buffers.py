@@ -52,6 +52,7 @@ class _Buffers:
         self._argmax_flat = torch.zeros((batch * self.tt_pad,), dtype=torch.int32, device=dev)
         self.g = [None] * n  # allocated lazily by ensure_backward()
         self.align_labels = self.align_ws = None  # allocated lazily by ensure_align()
+        self.error_counts = self.edit_rows = None  # allocated lazily by ensure_error_counts() / ensure_edit_rows()
         self.decoded_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
         self.input_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
         self.loss = torch.zeros((batch,), dtype=torch.float32, device=dev)
@@ -378,3 +379,17 @@ class _Buffers:
         need = lib().raw("sl_ctc_align_workspace_bytes")(self.batch, self.tt_pad, l_max)  # covers every length
         if self.align_ws is None or self.align_ws.numel() < need:
             self.align_ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=eng.device)
+
+    def ensure_error_counts(self, eng, batch):
+        """Results of sl_edit_distance for up to `batch` utterances: int32 (3, batch) -- letter errors, word errors, words of
+        the expected row.  (The kernel needs no workspace: include/speechless_hip.h.)"""
+        if self.error_counts is None or self.error_counts.shape[1] < batch:
+            self.error_counts = torch.zeros((3, batch), dtype=torch.int32, device=eng.device)
+        return self.error_counts[:, :batch]
+
+    def ensure_edit_rows(self, eng, count):
+        """Staging for Engine.edit_distance_batch: `count` int32 in HBM holding the padded rows and lengths of index lists
+        that come from the host, grown only."""
+        if self.edit_rows is None or self.edit_rows.numel() < count:
+            self.edit_rows = torch.zeros((count,), dtype=torch.int32, device=eng.device)
+        return self.edit_rows[:count]

@@ -23,6 +23,7 @@ from .buffers import _Buffers
 from .engine_front import FrontLayerMixin
 from .engine_split import SplitTopMixin
 from .engine_x3 import X3Mixin
+from .error_counts import host_counts, pack_rows
 from ._hipevents import TimingEvent
 from .plan import HALO, TIME_TILE, LayerPlan, LayerSpec, _round_up, same_padding, wav2letter_layer_specs  # noqa: F401
 
@@ -837,6 +838,46 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                      buf.input_len.data_ptr(), path.data_ptr(), buf.align_score.data_ptr(), buf.batch, buf.t_out, k,
                      buf.align_labels.shape[1], buf.align_ws.data_ptr(), buf.align_ws.numel(), self._stream())
         return path.view(buf.batch, buf.t_out).cpu().numpy(), buf.align_score.cpu().numpy()
+
+    def error_counts(self, space_index):
+        """Letter and word error counts of the greedy transcriptions against the labels, after forward() + set_labels() +
+        greedy_decode(): one sl_edit_distance launch on buf.labels / label_len and buf.decoded / decoded_len where they lie.
+        space_index: the word separator's index, < 0 for an alphabet without one.  Returns (letter_errors, word_errors),
+        int32 (B,) numpy -- net.edit_distance of the decoded strings and of their .split()."""
+        buf = self.cur
+        return self._edit_distance(buf, buf.labels, buf.label_len, buf.decoded, buf.decoded_len, space_index)
+
+    def edit_distance_batch(self, expected_rows, predicted_rows, space_index):
+        """error_counts for index lists that live on the host, as the beam decoders return them: pads both sides, uploads
+        them in one copy and makes the same launch.  Returns the same tuple.  Any number of rows; the staging and result
+        tensors belong to the current buffer set, so a forward pass (or load_input) comes first."""
+        if len(expected_rows) != len(predicted_rows) or len(expected_rows) == 0:
+            raise ValueError("need as many expected as predicted rows, and at least one")
+        buf = self.cur
+        a, a_len = pack_rows(expected_rows)
+        b, b_len = pack_rows(predicted_rows)
+        n = len(a_len)
+        staged = buf.ensure_edit_rows(self, a.size + b.size + 2 * n)
+        staged.copy_(torch.from_numpy(np.concatenate([a.ravel(), b.ravel(), a_len, b_len])))
+        a_dev, b_dev, a_len_dev, b_len_dev = staged.split([a.size, b.size, n, n])
+        return self._edit_distance(buf, a_dev.view(a.shape), a_len_dev, b_dev.view(b.shape), b_len_dev, space_index)
+
+    def _edit_distance(self, buf, a, a_len, b, b_len, space_index):
+        n, a_max, b_max = int(a.shape[0]), int(a.shape[1]), int(b.shape[1])
+        if not self.lib.raw("sl_edit_distance_supported")(a_max, b_max):
+            # rows beyond what the kernel keeps in LDS (include/speechless_hip.h): the host function counts this batch
+            a, a_len, b, b_len = (t.cpu().numpy() for t in (a, a_len, b, b_len))
+            return host_counts([a[i, :a_len[i]].tolist() for i in range(n)], [b[i, :b_len[i]].tolist() for i in range(n)],
+                               space_index)
+        out = buf.ensure_error_counts(self, n)
+        self._launch("edit_distance", "sl_edit_distance", a.data_ptr(), a_len.data_ptr(), a.stride(0), b.data_ptr(),
+                     b_len.data_ptr(), b.stride(0), n, a_max, b_max, int(space_index), out[0].data_ptr(), out[1].data_ptr(),
+                     out[2].data_ptr(), self._stream())
+        counts = out.cpu().numpy()
+        if (counts[:2] < 0).any():
+            raise ValueError("utterance {}: a length outside its row (expected rows hold {}, predicted rows {})".format(
+                int(np.argmax((counts[:2] < 0).any(axis=0))), a_max, b_max))
+        return counts[0].copy(), counts[1].copy()
 
     def backward(self, on_bucket_ready=None):
         """wgrad / bias-grad / dgrad for every trainable layer, output layer first.

@@ -17,6 +17,7 @@ from pathlib import Path
 import numpy as np
 
 from .engine import Engine, wav2letter_layer_specs
+from .error_counts import edit_distance, space_index_of
 from .grapheme_encoding import CtcGraphemeEncoding
 
 logger = logging.getLogger("results")
@@ -33,20 +34,6 @@ def log(obj):
 
 def _average_or_nan(numbers):
     return sum(numbers) / len(numbers) if len(numbers) else float("nan")
-
-
-def edit_distance(a, b):
-    """Levenshtein distance between two sequences (the reference uses the `editdistance` package, net.py:31-37)."""
-    a, b = list(a), list(b)
-    if len(a) < len(b):
-        a, b = b, a
-    previous = list(range(len(b) + 1))
-    for i, x in enumerate(a, 1):
-        current = [i]
-        for j, y in enumerate(b, 1):
-            current.append(min(previous[j] + 1, current[j - 1] + 1, previous[j - 1] + (x != y)))
-        previous = current
-    return previous[-1]
 
 
 class Adam:
@@ -81,15 +68,19 @@ class LabeledSpectrogram:
 
 
 class ExpectationVsPrediction:
-    def __init__(self, expected, predicted, loss):
+    def __init__(self, expected, predicted, loss, letter_error_count=None, word_error_count=None):
+        """letter_error_count / word_error_count (extension): counts that were taken elsewhere -- on the GPU,
+        Wav2Letter(error_count_device="gpu") -- stored as they are; None computes them here as the reference does."""
         self.expected = expected
         self.predicted = predicted
         self.loss = loss
         self.expected_letter_count = len(expected)
         self.expected_words = expected.split()
         self.expected_word_count = len(self.expected_words)
-        self.letter_error_count = edit_distance(expected, predicted)
-        self.word_error_count = edit_distance(self.expected_words, predicted.split())
+        self.letter_error_count = edit_distance(expected, predicted) if letter_error_count is None \
+            else letter_error_count
+        self.word_error_count = edit_distance(self.expected_words, predicted.split()) if word_error_count is None \
+            else word_error_count
 
     @property
     def letter_error_rate(self):
@@ -257,7 +248,8 @@ class Wav2Letter:
                  asg_initial_probabilities=None, kenlm_directory=None,
                  # --- extensions of this implementation (keyword-only in spirit) ---
                  compute_dtype=None, device="cuda:0", seed=None, ctc_epsilon=1e-8, layer_sizes=None,
-                 load_optimizer_state=False, eval_dtype=None, beam_search_device="host", track_gradient_norm=False):
+                 load_optimizer_state=False, eval_dtype=None, beam_search_device="host", track_gradient_norm=False,
+                 error_count_device="host"):
         if frozen_layer_count > 0 and load_model_from_directory is None:
             raise ValueError("Layers cannot be frozen if model is trained from scratch.")
         if use_asg:
@@ -268,6 +260,11 @@ class Wav2Letter:
         if beam_search_device not in ("host", "gpu"):
             raise ValueError("beam_search_device must be 'host' or 'gpu', not {!r}".format(beam_search_device))
         self.beam_search_device = beam_search_device
+        if error_count_device not in ("host", "gpu"):
+            raise ValueError("error_count_device must be 'host' or 'gpu', not {!r}".format(error_count_device))
+        self.error_count_device = error_count_device
+        # extension: "gpu" takes the letter / word error counts of test_and_predict_batch from csrc/edit_distance.hip
+        self._space_index = space_index_of(allowed_characters) if error_count_device == "gpu" else None
         self.grapheme_encoding = CtcGraphemeEncoding(allowed_characters=allowed_characters)
         self.use_asg = use_asg
         self.frozen_layer_count = frozen_layer_count
@@ -529,9 +526,17 @@ class Wav2Letter:
         else:
             decoded, _ = engine.greedy_decode()
         predictions = [self.grapheme_encoding.decode_graphemes(d, merge_repeated=False) for d in decoded]
+        n = len(predictions)
+        letter_errors = word_errors = [None] * n  # None: ExpectationVsPrediction counts on the host (net.py:31-37)
+        if self.error_count_device == "gpu" and self._beam_decoder is None:  # labels and `decoded` are in HBM already
+            letter_errors, word_errors = (c.tolist() for c in engine.error_counts(self._space_index))
+        elif self.error_count_device == "gpu":
+            label_lengths = inputs[names.label_lengths].reshape(-1)
+            expected = [row[:m].tolist() for row, m in zip(inputs[names.label_batch], label_lengths)]
+            letter_errors, word_errors = (c.tolist() for c in engine.edit_distance_batch(expected, decoded, self._space_index))
         return ExpectationsVsPredictions(
-            [ExpectationVsPrediction(predicted=p, expected=x.label, loss=float(l))
-             for p, x, l in zip(predictions, labeled_spectrogram_batch, losses)])
+            [ExpectationVsPrediction(predicted=p, expected=x.label, loss=float(l), letter_error_count=le, word_error_count=we)
+             for p, x, l, le, we in zip(predictions, labeled_spectrogram_batch, losses, letter_errors, word_errors)])
 
     def alignment_batch(self, labeled_spectrogram_batch):
         """Extension (no reference counterpart): CTC forced alignment of every example's label, one forward pass on the
