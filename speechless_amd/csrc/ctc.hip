@@ -235,10 +235,6 @@ __device__ __forceinline__ float log2_of_double(double x) {
     return (float)e + __builtin_amdgcn_logf((float)m);
 }
 
-// one wave per frame; work-group = 4 waves x FRAMES_PER_WAVE frames.  NJ = SP / 64 lattice columns per lane: all of a
-// frame's alpha / beta loads are issued before the first one is used (one HBM/L2 round trip per frame instead of NJ).
-// LIN: the lattice comes from ctc_lattice_wave_kernel (doubles in linear units with one exponent per frame, emissions
-// u = p + eps instead of q) and is brought to log2 units on the fly; the sum of a frame's state posteriors must then be
 // ---- repair of one utterance inside the gradient kernel (see ctc_grad_kernel) ------------------------------------------
 // Log-domain alpha and beta lattices of utterance b by ONE work-group of 256 threads (S <= 512): the
 // recursion of ctc_lattice_kernel without its tuning, IN DOUBLES since round 6 (the fp32 log values of a 500-frame utterance
@@ -332,8 +328,10 @@ __device__ void repair_lattices(const float* __restrict__ lq_b, const int* s_lab
 // LIN: the lattice comes from ctc_lattice_wave_kernel (doubles in linear units with one exponent per frame, emissions
 // u = p + eps instead of q) and is brought to log2 units on the fly; the sum of a frame's state posteriors must then be
 // 1 -- if the linear lattice lost mass to underflow it is not, and the utterance is flagged for the log-domain repair.
-template <int NJ, int LIN>  // LIN: 0 = log-domain rows; 1 = linear rows in doubles (exponent blocks of 16); 2 = in floats (of 8);
-                            // 3 = doubles from the wave-PAIR lattice (one exponent per FOUR states: 128 per block of 16)
+// LIN is exactly one of: 0 = log-domain rows in floats (ctc_lattice_kernel); 1 = linear rows, the high words of doubles with one
+// exponent per lattice lane and block of 16 frames (wave_lattice_run<., double>); 2 = linear rows in floats with one per block
+// of 8 frames (wave_lattice_run<., float>); 4 = log-domain rows in doubles (repair_lattices)
+template <int NJ, int LIN>
 __device__ __forceinline__ void ctc_grad_frames(
     const float* __restrict__ probs, const float* __restrict__ logq, const void* __restrict__ alpha_v,
     const void* __restrict__ beta_v, const int32_t* __restrict__ ea, const int32_t* __restrict__ eb,
@@ -341,6 +339,7 @@ __device__ __forceinline__ void ctc_grad_frames(
     const int* s_lab, const int* s_pos, const int* s_start, float* s_lq, float* s_gam, int b, int S, int T, int t_out,
     int k, int l_max, int sp, int blank, int t_begin, int frames_per_wg, int g_row0, int g_rs, long g_bs, int out_f32,
     float eps, float grad_scale, int32_t* __restrict__ flags) {
+    static_assert(LIN == 0 || LIN == 1 || LIN == 2 || LIN == 4, "LIN is 0, 1, 2 or 4");
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = tid >> 6;
@@ -386,7 +385,7 @@ __device__ __forceinline__ void ctc_grad_frames(
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {  // only the live part of the row was written: s < S rounded up to 8
                         const bool in = lane + 64 * j < ((S + 7) & ~7);
-                        if (LIN == 1 || LIN == 3) {  // the high words of the doubles (wave_lattice_run / pair_lattice_run)
+                        if (LIN == 1) {  // the high words of the doubles (wave_lattice_run)
                             ad[j] = in ? (RT)__hiloint2double(((const int*)alpha_v)[fidx * sp + lane + 64 * j], 0) : (RT)0;
                             bd[j] = in ? (RT)__hiloint2double(((const int*)beta_v)[fidx * sp + lane + 64 * j], 0) : (RT)0;
                         } else {
@@ -400,8 +399,8 @@ __device__ __forceinline__ void ctc_grad_frames(
                     // summed exactly, only the mantissa logarithms go through fp32.
                     // (one exponent per lattice lane = 8 states and block of 16 steps of the respective direction)
                     constexpr int RBS = LIN == 2 ? 3 : 4;  // log2 of the frames per exponent block
-                    constexpr int ELANES = LIN == 3 ? 128 : 64;  // exponents per block
-                    constexpr int WSH = LIN == 3 ? 2 : 3;        // log2 of the states that share one
+                    constexpr int ELANES = 64;  // exponents per block
+                    constexpr int WSH = 3;      // log2 of the states that share one
                     const int32_t* eap = ea + ((long)b * ((t_out >> RBS) + 1) + (t >> RBS)) * ELANES;
                     const int32_t* ebp = eb + ((long)b * ((t_out >> RBS) + 1) + ((T - 1 - t) >> RBS)) * ELANES;
                     const int zi = zint[b];
@@ -785,7 +784,8 @@ __device__ __forceinline__ void wave_lattice_run(const float* __restrict__ pr, c
     fetch_chunk(0, e4);
     stage_chunk(0, e4);
     // HELP: hand-over with the helper wave per chunk of 8 frames (plain LDS accesses in program order, relaxed work-group
-    // atomics on the counters: see pair_lattice_run)
+    // atomics on the counters: `volatile` or acquire / release accesses make the memory legaliser put s_waitcnt lgkmcnt(0) -- or
+    // vmcnt(0): the row stores' round trip -- behind every one of them, per frame)
     int chunks_done = 0;
     auto await_chunk = [&]() {  // the helper has published chunk `chunks_done`
         if (HELP) {
@@ -1032,345 +1032,6 @@ __device__ __forceinline__ void wave_lattice_run(const float* __restrict__ pr, c
     *e_final = E;
 }
 
-// ---- the same lattice on a PAIR of waves per (utterance, direction) (round 6) -----------------------------------------------
-// The lone wave is latency-bound: 265 cycles per frame, of which the 20 dependent double operations of a lane's eight states
-// are 125 and the two 1 KB row stores 68 (0.10 ms of the config-3 step, 0.39 ms at config 5, nothing
-// beside it).  Here a lane owns FOUR states (lane gl of 128 owns states 4 gl .. 4 gl + 3, label positions 2 gl, 2 gl + 1): half
-// the arithmetic, one row store and three emission reads per wave and frame.  The recursion moves mass in ONE direction across
-// the wave boundary (alpha: from wave 0's lane 63 up into wave 1's lane 0; beta: from wave 1's lane 0 down into wave 0's lane
-// 63), so the upstream wave never waits: it writes its boundary state(s) of every row into an LDS mailbox (one slot per row)
-// and raises a progress counter three times per block of 16 frames -- after the block's rescale (with the boundary lane's
-// new exponent and its empty flag) and after each half of 8 frames -- and the downstream wave, which needs row t - 1 for row t,
-// runs half a block behind: it polls the counter once per half block, fetches the half block's eight boundary values in one
-// go and otherwise executes exactly the single-wave recursion.  A wave's LDS operations execute in order and LDS has no
-// caches, so "data written before the counter, counter read before the data" needs no fence.  Block floating point as in
-// wave_lattice_run; the boundary lane of the downstream wave sees the upstream boundary lane's FINAL exponent of the block in
-// every adoption round (a valid assignment like any other: exponents only re-express the values).
-constexpr int PNS = 4;            // states per lane
-constexpr int PLANES = 128;       // lanes per direction
-constexpr int PAIR_EMIS = 8 * 64 + 64;
-
-struct PairShared {
-    double* mbox;     // [T + 1][2]: boundary state(s) of row r at slot r + 1 (slot 0 = the zeros in front of row 0)
-    double* mdump;    // [128][2]: where the lanes that are not at the wave boundary put their (unused) copy -- unconditional stores
-    int* ebox;        // [blocks + 1][2]: exponent and empty flag of the upstream boundary lane after the block's rescale
-    int* progress;    // events the upstream wave has completed (3 per block)
-    double* emis;     // [2 waves][2][PAIR_EMIS]
-};
-
-// The hand-over is built from PLAIN LDS accesses in program order, a compiler barrier and relaxed work-group atomics on the
-// counter: `volatile` (or acquire / release) accesses make the memory legaliser put s_waitcnt lgkmcnt(0) -- or vmcnt(0): the
-// row stores' round trip -- behind every one of them, per frame (the first version of this kernel: 730 cycles per frame).
-template <int DIR>
-__device__ __forceinline__ void pair_lattice_run(const float* __restrict__ pr, const int32_t* __restrict__ lab,
-                                                 uint32_t* __restrict__ rows, uint32_t* __restrict__ dump,
-                                                 int32_t* __restrict__ eout, const PairShared sh, int wv, int lane, int L,
-                                                 int S, int T, int k, int blank, float eps, double* a, int* e_final) {
-    typedef double R;
-    constexpr int RB = 16;
-    constexpr int ZERO_SLOT = 63;
-    constexpr int FLOOR = WaveReal<double>::FLOOR, SHIFT_MAX = WaveReal<double>::SHIFT_MAX, TARGET = WaveReal<double>::TARGET;
-    const int gl = wv * 64 + lane;                 // lane of the direction: states 4 gl .. 4 gl + 3
-    const bool upstream = DIR == 0 ? wv == 0 : wv == 1;
-    // the lane whose neighbour lives in the other wave (downstream side) / the lane the other wave reads (upstream side)
-    const bool edge_lane = DIR == 0 ? (upstream ? lane == 63 : lane == 0) : (upstream ? lane == 0 : lane == 63);
-    const bool from_other = !upstream && edge_lane;
-    int col[2];
-    R sk[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int pos = 2 * gl + i;
-        const bool slot_live = pos < L;
-        const int me = slot_live ? lab[pos] : blank;
-        col[i] = slot_live ? me : ZERO_SLOT;
-        bool skip;
-        if (DIR == 0)
-            skip = slot_live && pos >= 1 && lab[pos - 1] != me;
-        else
-            skip = pos + 1 < L && lab[pos + 1] != me;
-        sk[i] = skip ? (R)1 : (R)0;
-    }
-    const int tstart = DIR == 0 ? 0 : T - 1;
-    const int tstep = DIR == 0 ? 1 : -1;
-    const bool lane_live = PNS * gl < S;
-    uint32_t* rowp = lane_live ? rows + (long)tstart * 512 + PNS * gl : dump + PNS * gl;
-    const long row_inc = lane_live ? (long)tstep * 512 : 0;
-    // mailbox store address of this lane: the real slot for the upstream boundary lane (advancing by a row per frame), a
-    // private dump slot (stride 0) for everybody else -- every lane stores, no exec mask, no branch
-    const bool poster = upstream && edge_lane;
-    double* mslot = poster ? sh.mbox : sh.mdump + 2 * gl;   // slot of row -1
-    const int mslot_inc = poster ? 2 : 0;
-
-    R* emis0 = sh.emis + (wv * 2 + 0) * PAIR_EMIS;
-    R* emis1 = sh.emis + (wv * 2 + 1) * PAIR_EMIS;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        emis0[j * 64 + lane] = (R)0;
-        emis1[j * 64 + lane] = (R)0;
-    }
-    int st_idx[4], ld_jf[4], ld_c[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int idx = lane + 64 * r;
-        const int jf = idx / k;
-        ld_c[r] = idx - jf * k;
-        ld_jf[r] = jf < 8 ? jf : 7;
-        st_idx[r] = jf < 8 ? jf * 64 + ld_c[r] : 8 * 64 + lane;
-    }
-    const float* chunk0 = pr + (long)tstart * k;
-    const int kstep = tstep * k;
-    auto fetch_chunk = [&](int base, float* e4) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) e4[r] = chunk0[min(base + ld_jf[r], T - 1) * kstep + ld_c[r]];
-    };
-    auto stage_chunk = [&](R* buf, const float* e4) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) buf[st_idx[r]] = (R)(e4[r] + eps);
-    };
-    float e4[4];
-    fetch_chunk(0, e4);
-    stage_chunk(emis0, e4);
-#pragma unroll
-    for (int j = 0; j < PNS; ++j) a[j] = (R)0;
-    int E = 0;
-    bool lane_zero = true;
-    R fscale = (R)1;
-    int events = 0;  // upstream: events published; downstream: events consumed
-    int mbase = 0;   // (partial last block: first mailbox slot of the half being run)
-
-    auto publish = [&]() {  // upstream: everything this wave wrote to the mailbox so far precedes this store in LDS order
-        if (upstream) {
-            ++events;
-            asm volatile("" ::: "memory");
-            if (lane == 0) __hip_atomic_store(sh.progress, events, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    };
-    auto await = [&]() {    // downstream: the upstream wave has completed the event of the same number
-        if (!upstream) {
-            ++events;
-            // (bounded: the upstream wave never waits, so this ends within a block's time; should that ever fail the wave goes
-            // on with what the mailbox holds instead of hanging -- the gradient kernel's sum check then flags the utterance)
-            for (int spins = 0; spins < (1 << 22); ++spins) {
-                if (__hip_atomic_load(sh.progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= events) break;
-                __builtin_amdgcn_s_sleep(1);
-            }
-            asm volatile("" ::: "memory");
-        }
-    };
-    // boundary values of the row this wave's registers hold, into the slot `mslot` points at (then on to the next row's)
-    auto post_row = [&]() {
-        mslot += mslot_inc;
-        if (DIR == 0) {
-            mslot[0] = a[PNS - 1];
-        } else {
-            *(double2*)mslot = make_double2(a[0], a[1]);
-        }
-    };
-
-    auto rescale = [&](int base) {
-        const int tp = tstart + tstep * (base - 1);
-        const int lo_edge = DIR == 0 ? S - 2 * (T - tp) : 0;
-        const int hi_edge = DIR == 0 ? S : 2 * tp + 1;
-        eout[max(base / RB - 1, 0) * PLANES + gl] = E;
-        R m = (R)0;
-#pragma unroll
-        for (int j = 0; j < PNS; ++j) {
-            const int st = PNS * gl + j;
-            a[j] = (st < lo_edge || st > hi_edge) ? (R)0 : a[j];
-            m = wave_max2(m, a[j]);
-        }
-        lane_zero = !(m > (R)0);
-        const int shift = lane_zero ? 0 : TARGET - wave_frexp_exp(m);
-#pragma unroll
-        for (int j = 0; j < PNS; ++j) a[j] = wave_ldexp(a[j], shift);
-        E -= shift;
-        // the neighbour's values of the lane at the wave boundary: from the other wave (downstream side)
-        int x_e = E, x_zero = 1;
-        if (!upstream) {
-            x_e = sh.ebox[2 * (base / RB)];
-            x_zero = sh.ebox[2 * (base / RB) + 1];
-        }
-        const int e_own = E;
-        int zsrc = DIR == 0 ? dpp_int_from_lower_lane(lane_zero ? 1 : 0, 1) : dpp_int_from_upper_lane(lane_zero ? 1 : 0, 1);
-        zsrc = from_other ? x_zero : zsrc;
-        // in 16 frames mass moves at most 32 states = 8 lanes of four: nine rounds of "empty lane <- neighbour"
-#pragma unroll
-        for (int round = 0; round < RB / 2 + 1; ++round) {
-            int en = DIR == 0 ? dpp_int_from_lower_lane(E, E) : dpp_int_from_upper_lane(E, E);
-            en = from_other ? x_e : en;
-            E = lane_zero ? en : (zsrc ? E : max(E, en - FLOOR));
-        }
-        {   // (the rule of wave_lattice_run's rescale: a lane more than 2^SHIFT_MAX below a source neighbour still in play)
-            int en_r = DIR == 0 ? dpp_int_from_lower_lane(E, E) : dpp_int_from_upper_lane(E, E);
-            en_r = from_other ? x_e : en_r;
-            const bool src_gone = DIR == 0 ? (PNS * gl - 1 < lo_edge) : (PNS * (gl + 1) > min(hi_edge, S - 1));
-            E = (!lane_zero && !src_gone && en_r - E > SHIFT_MAX) ? en_r - FLOOR : E;
-        }
-        const int lift = lane_zero ? 0 : E - e_own;
-#pragma unroll
-        for (int j = 0; j < PNS; ++j) a[j] = wave_ldexp(a[j], -lift);
-        int en = DIR == 0 ? dpp_int_from_lower_lane(E, E) : dpp_int_from_upper_lane(E, E);
-        en = from_other ? x_e : en;
-        fscale = wave_ldexp((R)1, max(min(en - E, SHIFT_MAX), -4 * SHIFT_MAX));
-        // upstream: the boundary lane's exponent and empty flag of this block, and row base - 1 AS RESCALED (the row the
-        // downstream wave's first frame of the block reads): the slot written last is written again
-        if (poster) {
-            sh.ebox[2 * (base / RB)] = E;
-            sh.ebox[2 * (base / RB) + 1] = lane_zero ? 1 : 0;
-        }
-        mslot -= mslot_inc;
-        post_row();
-    };
-    // x0 / x1: the boundary value(s) of the previous row from the other wave (used by the downstream edge lane only)
-    auto frame_core = [&](const bool first, const R ub, const R (&uq)[2], const R x0, const R x1) {
-        R n[PNS];
-        if (DIR == 0) {
-            R below = dpp_from_lower_lane(a[PNS - 1]);
-            below = (from_other ? x0 : below) * fscale;
-            n[0] = a[0] + below;
-#pragma unroll
-            for (int i = 1; i < PNS; ++i) n[i] = a[i] + a[i - 1];
-            asm volatile("" : "+v"(n[0]), "+v"(n[1]), "+v"(n[2]), "+v"(n[3]));
-            n[1] = fma(sk[0], below, n[1]);
-            n[3] = fma(sk[1], a[1], n[3]);
-        } else {
-            R up0 = dpp_from_upper_lane(a[0]);
-            R up1 = dpp_from_upper_lane(a[1]);
-            up0 = (from_other ? x0 : up0) * fscale;
-            up1 = (from_other ? x1 : up1) * fscale;
-            n[PNS - 1] = a[PNS - 1] + up0;
-#pragma unroll
-            for (int i = 0; i < PNS - 1; ++i) n[i] = a[i] + a[i + 1];
-            asm volatile("" : "+v"(n[0]), "+v"(n[1]), "+v"(n[2]), "+v"(n[3]));
-            n[3] = fma(sk[1], up1, n[3]);
-            n[1] = fma(sk[0], a[3], n[1]);
-        }
-        asm volatile("" : "+v"(n[0]), "+v"(n[1]), "+v"(n[2]), "+v"(n[3]));
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            n[2 * i] *= ub;
-            n[2 * i + 1] *= uq[i];
-        }
-        // step 0 (branch-free: selects; `first` is false at compile time for every frame but the first of a half block): the
-        // recursion above ran on zeros, only the entry states are set
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            bool blank_entry, label_entry;
-            if (DIR == 0) {
-                blank_entry = gl == 0 && i == 0;
-                label_entry = gl == 0 && i == 0;
-            } else {
-                blank_entry = PNS * gl + 2 * i == S - 1;
-                label_entry = L > 0 && PNS * gl + 2 * i + 1 == S - 2;
-            }
-            n[2 * i] = first ? (blank_entry ? ub : (R)0) : n[2 * i];
-            n[2 * i + 1] = first ? (label_entry ? uq[i] : (R)0) : n[2 * i + 1];
-        }
-#pragma unroll
-        for (int i = 0; i < PNS; ++i) a[i] = n[i];
-        *(ulonglong2*)rowp = make_ulonglong2(pk_high_words(a[0], a[1]), pk_high_words(a[2], a[3]));
-        rowp += row_inc;
-    };
-    // the boundary values of rows base - 1 .. base + 6 for a half block (downstream; everything else gets zeros it never uses)
-    R x0[8], x1[8];
-    auto preload = [&](int base, int count) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            x0[j] = (R)0;
-            x1[j] = (R)0;
-        }
-        if (!upstream) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                if (j < count) {
-                    if (DIR == 0) {
-                        x0[j] = sh.mbox[2 * (base + j)];  // slot of row base + j - 1
-                    } else {
-                        const double2 v = *(const double2*)(sh.mbox + 2 * (base + j));
-                        x0[j] = v.x;
-                        x1[j] = v.y;
-                    }
-                }
-            }
-        }
-    };
-    // eight frames, straight-line (no branch between a chunk's prefetch loads and their use: the waitcnt pass counts the
-    // row stores in between exactly -- see wave_lattice_run)
-    auto frames8 = [&](const bool entry, const R* erow0) {
-        // a frame's three emission reads are issued ONE FRAME AHEAD: a frame of four states per lane is ~35 instructions, and
-        // an LDS read issued inside it was what it waited for (lgkmcnt in front of the products: 106 us per call at 32 x 500)
-        R ub = erow0[blank];
-        R uq[2] = {erow0[col[0]], erow0[col[1]]};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            R nub = ub, nuq[2] = {uq[0], uq[1]};
-            if (j < 7) {
-                const R* erow = erow0 + (j + 1) * 64;
-                nub = erow[blank];
-                nuq[0] = erow[col[0]];
-                nuq[1] = erow[col[1]];
-            }
-            frame_core(j == 0 && entry, ub, uq, x0[j], x1[j]);
-            post_row();
-            ub = nub;
-            uq[0] = nuq[0];
-            uq[1] = nuq[1];
-        }
-    };
-    auto frames_some = [&](int count, const bool entry, const R* erow0) {  // (the last, partial block)
-        for (int j = 0; j < count; ++j) {
-            const R* erow = erow0 + j * 64;
-            const R ub = erow[blank];
-            R uq[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) uq[i] = erow[col[i]];
-            R xa = (R)0, xb = (R)0;
-            if (!upstream) {
-                xa = sh.mbox[2 * (mbase + j)];
-                xb = sh.mbox[2 * (mbase + j) + 1];
-            }
-            frame_core(j == 0 && entry, ub, uq, xa, xb);
-            post_row();
-        }
-    };
-
-    int base = 0;
-    for (; base + RB <= T; base += RB) {
-        await();  // (downstream: the upstream rescale of this block)
-        rescale(base);
-        publish();
-        await();  // (downstream: the upstream wave's first half of this block)
-        preload(base, 8);
-        fetch_chunk(base + 8, e4);
-        frames8(base == 0, emis0);
-        stage_chunk(emis1, e4);
-        publish();
-        await();
-        preload(base + 8, 8);
-        fetch_chunk(base + 16, e4);
-        frames8(false, emis1);
-        stage_chunk(emis0, e4);
-        publish();
-    }
-    if (base < T) {  // fewer than 16 steps left: the same three events
-        await();
-        rescale(base);
-        publish();
-        await();
-        fetch_chunk(base + 8, e4);
-        mbase = base;
-        frames_some(min(8, T - base), base == 0, emis0);
-        stage_chunk(emis1, e4);
-        publish();
-        await();
-        mbase = base + 8;
-        frames_some(max(0, min(8, T - base - 8)), false, emis1);
-        publish();
-    }
-    eout[((T - 1) / RB) * PLANES + gl] = E;
-    *e_final = E;
-}
-
 // workspace: alpha, beta R[B][T][512] (+ one dump row per utterance and direction); ea, eb int32[B][T/RB+1][64], RB =
 // WaveReal<R>::RESCALE; logz2 float[B]; cls as for the log-domain kernel
 template <typename R>
@@ -1559,7 +1220,7 @@ __device__ __forceinline__ void lattice_helper(const float* __restrict__ pr, con
     }
 }
 
-// per-class position lists for the gradient kernel, by ONE wave (the y = 2 work-groups of the pair / helped lattice kernels)
+// per-class position lists for the gradient kernel, by ONE wave (the y = 2 work-groups of ctc_lattice_helped_kernel)
 __device__ __forceinline__ void build_class_lists_wave(int* s_lab, int lane, const int32_t* __restrict__ labels,
                                                        int32_t* __restrict__ cls, int32_t* __restrict__ tickets, int b, int L,
                                                        int grad_wgs, int k, int l_max) {
@@ -1714,111 +1375,6 @@ __global__ __launch_bounds__(128) void ctc_lattice_helped_kernel(const float* __
     }
 }
 
-// dynamic LDS of ctc_lattice_pair_kernel (bytes): fin 32 | progress 32 | ebox | mbox | emis   (dir 2: the list builder's ints)
-__host__ __device__ inline size_t pair_lds_ebox(int t_out) { return (size_t)2 * (t_out / 16 + 2) * sizeof(int); }
-__host__ __device__ inline size_t pair_lds_mbox(int t_out) { return (size_t)2 * (t_out + 2) * sizeof(double); }
-__host__ inline size_t pair_lds_bytes(int t_out, int l_max, int k) {
-    size_t lattice = 64 + ((pair_lds_ebox(t_out) + 15) / 16) * 16 + pair_lds_mbox(t_out) + (size_t)2 * PLANES * sizeof(double) +
-                     (size_t)4 * PAIR_EMIS * sizeof(double);
-    const size_t lists = (size_t)(l_max + k + 1) * sizeof(int);
-    return lattice > lists ? lattice : lists;
-}
-
-// grid (B, 3), 128 threads: y = 0 alpha, 1 beta (two waves each, pair_lattice_run), 2 the per-class position lists (wave 0)
-__global__ __launch_bounds__(128) void ctc_lattice_pair_kernel(const float* __restrict__ probs, const float* __restrict__ logq,
-                                                               const int32_t* __restrict__ labels,
-                                                               const int32_t* __restrict__ label_len,
-                                                               const int32_t* __restrict__ input_len,
-                                                               uint32_t* __restrict__ alpha, uint32_t* __restrict__ beta,
-                                                               uint32_t* __restrict__ dump, int32_t* __restrict__ ea,
-                                                               int32_t* __restrict__ eb, float* __restrict__ logz2,
-                                                               int32_t* __restrict__ zint, float* __restrict__ loss,
-                                                               int32_t* __restrict__ cls, int32_t* __restrict__ flags,
-                                                               int32_t* __restrict__ tickets, int grad_wgs, int t_out, int k,
-                                                               int l_max, int blank, float eps) {
-    extern __shared__ __attribute__((aligned(16))) char pl_lds[];
-    const int b = blockIdx.x;
-    const int dir = blockIdx.y;
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int L = label_len[b];
-    if (dir == 2) {
-        if (wv == 0) build_class_lists_wave((int*)pl_lds, lane, labels, cls, tickets, b, L, grad_wgs, k, l_max);
-        return;
-    }
-    const int S = 2 * L + 1;
-    int T = input_len[b];
-    if (T > t_out) T = t_out;
-    if (T <= 0) {
-        if (dir == 0 && threadIdx.x == 0) {
-            loss[b] = INFINITY;
-            logz2[b] = 0.f;
-            zint[b] = 0;
-            flags[b] = 0;
-        }
-        return;
-    }
-    double* fin = (double*)pl_lds;
-    int* fin_e = (int*)(fin + 2);
-    PairShared sh;
-    sh.progress = (int*)(pl_lds + 32);
-    sh.ebox = (int*)(pl_lds + 64);
-    sh.mbox = (double*)(pl_lds + 64 + ((pair_lds_ebox(t_out) + 15) / 16) * 16);
-    sh.mdump = (double*)((char*)sh.mbox + pair_lds_mbox(t_out));
-    sh.emis = sh.mdump + 2 * PLANES;
-    if (threadIdx.x == 0) *sh.progress = 0;
-    __syncthreads();
-    const int32_t* lab = labels + (long)b * l_max;
-    const float* pr = probs + (long)b * t_out * k;
-    double a[PNS];
-    int E;
-    const int gl = wv * 64 + lane;
-    if (dir == 0) {
-        // sum over the scored frames of ln c_t and the repeat count (see ctc_lattice_wave_kernel): by the DOWNSTREAM wave, which
-        // has half a block to wait for its first boundary values anyway
-        float csum = 0.f;
-        int repeats = 0;
-        if (wv == 1) {
-            for (int t = lane; t < T; t += 64)
-                csum += logq[((long)b * t_out + t) * k + blank] - logf(pr[(long)t * k + blank] + eps);
-            csum = wave_sum(csum);
-            float repeats_f = 0.f;
-            for (int i = lane + 1; i < L; i += 64) repeats_f += lab[i] == lab[i - 1] ? 1.f : 0.f;
-            repeats = (int)wave_sum(repeats_f);
-        }
-        pair_lattice_run<0>(pr, lab, alpha + (long)b * t_out * 512, dump + (long)(2 * b) * 512,
-                            ea + (long)b * (t_out / 16 + 1) * PLANES, sh, wv, lane, L, S, T, k, blank, eps, a, &E);
-#pragma unroll
-        for (int i = 0; i < PNS; ++i) {
-            if (PNS * gl + i == S - 1) {
-                fin[0] = a[i];
-                fin_e[0] = E;
-            }
-            if (PNS * gl + i == S - 2) {
-                fin[1] = a[i];
-                fin_e[1] = E;
-            }
-        }
-        __syncthreads();
-        if (wv == 1 && lane == 0) {
-            const double z1 = fin[0], z2 = S >= 2 ? fin[1] : 0.0;
-            const int e1 = fin_e[0], e2 = S >= 2 ? fin_e[1] : e1;
-            const int ez = (z2 > 0.0 && (z1 == 0.0 || e2 > e1)) ? e2 : e1;
-            const double z = ldexp(z1, max(e1 - ez, -2000)) + ldexp(z2, max(e2 - ez, -2000));
-            int xz = 0;
-            const double mz = frexp(z > 0.0 ? z : 1.0, &xz);
-            const float frac = __builtin_amdgcn_logf((float)mz);
-            logz2[b] = frac;
-            zint[b] = xz + ez;
-            loss[b] = z > 0.0 ? (float)(-((double)(xz + ez) + (double)frac) * 0.6931471805599453 - (double)csum) : INFINITY;
-            flags[b] = (z > 0.0 && z < INFINITY) ? 0 : (z == 0.0 && L + repeats > T ? 0 : 1);
-        }
-    } else {
-        pair_lattice_run<1>(pr, lab, beta + (long)b * t_out * 512, dump + (long)(2 * b + 1) * 512,
-                            eb + (long)b * (t_out / 16 + 1) * PLANES, sh, wv, lane, L, S, T, k, blank, eps, a, &E);
-    }
-}
-
 __global__ __launch_bounds__(256) void greedy_decode_kernel(const float* __restrict__ probs,
                                                             const int32_t* __restrict__ input_len,
                                                             int32_t* __restrict__ out, int32_t* __restrict__ out_len,
@@ -1883,18 +1439,40 @@ __global__ __launch_bounds__(256) void greedy_decode_kernel(const float* __restr
 
 __host__ int lattice_sp(int l_max) { return ((2 * l_max + 1) + 63) / 64 * 64; }
 
-// which lattice sl_ctc_loss_grad runs (sl_ctc_select): 0 = automatic -- when the labels fit (2 * l_max + 1 <= 512, k <= 63)
-// the probability-domain wave lattice in doubles with the log-domain repair pass behind it, otherwise the log-domain
-// lattice (per call at 32 x 500 frames: 108 vs 132 us; at 8 x 4000 frames 556 vs 912); 1 = log-domain lattice only; 2 =
-// double wave lattice without the repair pass (measurement); 3 = double wave lattice, then every utterance redone by
-// the repair pass (tests); 4 = double wave lattice + repair; 5 / 6 / 7 = the FLOAT wave lattice with repair / without /
-// with forced repair (measurement: 87 / 463 us, but see WaveReal)
-int g_ctc_variant = 0;
+// which lattice sl_ctc_loss_grad runs (sl_ctc_select), and what the repair pass behind it redoes: the utterances the lattice
+// or the gradient kernel flagged, all of them (tests), or none (measurement).  The probability-domain lattices take labels
+// with 2 * l_max + 1 <= 512 and k <= 63; beyond that every variant runs the log-domain lattice (per call at 32 x 500 frames:
+// 108 vs 132 us; at 8 x 4000 frames 556 vs 912).  The numbers are fixed: profiles, HISTORY.md and tools refer to them, and
+// 8 / 9 (the lattice on a pair of waves: DESIGN.md section 6) stay retired.
 #ifndef SL_CTC_DEFAULT_WAVE
 // sl_ctc_select(0): 10 = the lattice wave with its helper wave (round 6: 92.4 -> 88.0 us per call at 32 x 500, 502 -> 471 us at
-// 8 x 4000, bit-identical results), 4 = the lone wave, 8 = the wave pair (A/B builds: -DSL_CTC_DEFAULT_WAVE=4)
+// 8 x 4000, bit-identical results), 4 = the lone wave (A/B builds: -DSL_CTC_DEFAULT_WAVE=4)
 #define SL_CTC_DEFAULT_WAVE 10
 #endif
+static_assert(SL_CTC_DEFAULT_WAVE == 10 || SL_CTC_DEFAULT_WAVE == 4, "SL_CTC_DEFAULT_WAVE is 10 (helper wave) or 4 (lone wave)");
+enum { LAT_LOG, LAT_LONE, LAT_LONE_F32, LAT_HELPED };
+enum { REP_NONE, REP_FLAGGED, REP_ALL };
+struct CtcVariant {
+    int variant, lattice, repair;
+};
+constexpr CtcVariant CTC_VARIANTS[] = {
+    {0, SL_CTC_DEFAULT_WAVE == 10 ? LAT_HELPED : LAT_LONE, REP_FLAGGED},  // automatic: the default wave lattice
+    {1, LAT_LOG, REP_NONE},         // the log-domain lattice only
+    {2, LAT_LONE, REP_NONE},        // the lone lattice wave without the repair pass (measurement)
+    {3, LAT_LONE, REP_ALL},         // ... then every utterance redone by the repair pass (tests)
+    {4, LAT_LONE, REP_FLAGGED},     // ... with the repair pass
+    {5, LAT_LONE_F32, REP_FLAGGED},  // the lone wave in FLOATS with the repair pass (measurement: see WaveReal)
+    {6, LAT_LONE_F32, REP_NONE},     // ... without
+    {7, LAT_LONE_F32, REP_ALL},      // ... every utterance redone
+    {10, LAT_HELPED, REP_FLAGGED},  // the lattice wave with its helper wave and the repair pass
+    {11, LAT_HELPED, REP_NONE},     // ... without the repair pass (measurement)
+};
+__host__ const CtcVariant* ctc_variant_row(int variant) {
+    for (const CtcVariant& r : CTC_VARIANTS)
+        if (r.variant == variant) return &r;
+    return nullptr;
+}
+int g_ctc_variant = 0;  // always a row of the table (sl_ctc_select)
 
 struct CtcLayout {
     size_t log_alpha, log_beta, cls, lin_alpha, lin_beta, dump, ea, eb, logz2, zint, flags, tickets, total;
@@ -1916,7 +1494,8 @@ __host__ CtcLayout ctc_layout(int batch, int t_out, int l_max) {
     w.lin_alpha = take(wave ? rows * 64 * WNS * sizeof(uint32_t) : 0);  // a float, or the high word of a double, per state
     w.lin_beta = take(wave ? rows * 64 * WNS * sizeof(uint32_t) : 0);
     w.dump = take(wave ? (size_t)2 * batch * 64 * WNS * sizeof(uint32_t) : 0);
-    // one exponent per lane and block of 16 (double) / 8 (float) steps; the pair lattice: 128 per block of 16
+    // one exponent per lane and block of 16 (double) / 8 (float) steps: (t_out / 16 + 1) * 64 resp. (t_out / 8 + 1) * 64 per
+    // utterance are read and written.  (The retired wave-pair lattice kept 128 per block of 16, the same size.)
     const size_t eblocks = (size_t)batch * (t_out / 8 + 2) * 64;
     w.ea = take(wave ? eblocks * sizeof(int32_t) : 0);
     w.eb = take(wave ? eblocks * sizeof(int32_t) : 0);
@@ -1931,7 +1510,8 @@ __host__ CtcLayout ctc_layout(int batch, int t_out, int l_max) {
 }  // namespace
 
 extern "C" int sl_ctc_select(int variant) {
-    SL_CHECK_ARG(variant >= 0 && variant <= 11, "sl_ctc_select: variant %d outside 0..11", variant);
+    SL_CHECK_ARG(variant != 8 && variant != 9, "sl_ctc_select: variant %d (the wave-pair lattice) is retired", variant);
+    SL_CHECK_ARG(ctc_variant_row(variant) != nullptr, "sl_ctc_select: variant %d is none of 0..7, 10, 11", variant);
     g_ctc_variant = variant;
     return SL_OK;
 }
@@ -1985,28 +1565,15 @@ extern "C" int sl_ctc_loss_grad(const float* probs, const float* logq, const int
     int32_t* cls = (int32_t*)(base + w.cls);
     int32_t* flags = (int32_t*)(base + w.flags);
     // which lattice: see sl_ctc_select
+    const CtcVariant* row = ctc_variant_row(g_ctc_variant);
     const bool fits = 2 * l_max + 1 <= 64 * WNS && k <= 63;
-    int v = g_ctc_variant;
-    // 8 (round 6): the double lattice on a PAIR of waves per direction (pair_lattice_run); its LDS mailbox holds a slot per
-    // frame, so very long utterances (T' > 8000) stay on the single wave
-    const bool pair_fits = fits && pair_lds_bytes(t_out, l_max, k) <= 150 * 1024;
-    if (v == 0) v = fits ? ((SL_CTC_DEFAULT_WAVE != 8 || pair_fits) ? SL_CTC_DEFAULT_WAVE : 4) : 1;
-    if (v != 1 && !fits) v = 1;
-    if (v == 8 && !pair_fits) v = 4;
-    if (v == 9 && !pair_fits) v = 2;
-    if ((v == 10 || v == 11) && !fits) v = 1;
-    const bool wave = v != 1;
-    const bool pair = v == 8 || v == 9;
-    const bool helped = v == 10 || v == 11;  // 10 / 11 (round 6): the lone lattice wave + a helper wave that gathers its emissions
-    const bool wave_f32 = v >= 5 && v <= 7;
-    const bool repair = wave && v != 2 && v != 6 && v != 9 && v != 11;
-    const bool force_repair = v == 3 || v == 7;
+    const int lattice = fits ? row->lattice : LAT_LOG;
     const int frames_per_wg = 8;  // two frames per wave: 16000 frames -> 8000 waves in flight
     const size_t lds2 = (size_t)(2 * l_max + (k + 1)) * sizeof(int) + (size_t)(4 * 64 + 4 * l_max) * sizeof(float);
     const dim3 grid((t_out + frames_per_wg - 1) / frames_per_wg, batch);
     const int out_f32 = dtype == SL_F32 ? 1 : 0;
     int rc;
-    if (wave) {
+    if (lattice != LAT_LOG) {
         void* la = base + w.lin_alpha;
         void* lb = base + w.lin_beta;
         int32_t* ea = (int32_t*)(base + w.ea);
@@ -2016,7 +1583,7 @@ extern "C" int sl_ctc_loss_grad(const float* probs, const float* logq, const int
         int32_t* tickets = (int32_t*)(base + w.tickets);
         size_t lds = (size_t)(l_max + k + 1) * sizeof(int);
         if (lds < 2 * sizeof(double) + 2 * sizeof(int)) lds = 2 * sizeof(double) + 2 * sizeof(int);
-        if (helped) {
+        if (lattice == LAT_HELPED) {
             const size_t hlds = helped_lds_bytes(l_max, k);
             static bool attr_set_h = false;
             if (!attr_set_h) {
@@ -2027,18 +1594,7 @@ extern "C" int sl_ctc_loss_grad(const float* probs, const float* logq, const int
             hipLaunchKernelGGL(ctc_lattice_helped_kernel, dim3(batch, 3), dim3(128), hlds, s, probs, logq, labels, label_len,
                                input_len, (uint32_t*)la, (uint32_t*)lb, (uint32_t*)(base + w.dump), ea, eb, logz2, zint, loss,
                                cls, flags, tickets, (int)grid.x, t_out, k, l_max, k - 1, eps);
-        } else if (pair) {
-            const size_t plds = pair_lds_bytes(t_out, l_max, k);
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void*)ctc_lattice_pair_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          160 * 1024);
-                attr_set = true;
-            }
-            hipLaunchKernelGGL(ctc_lattice_pair_kernel, dim3(batch, 3), dim3(128), plds, s, probs, logq, labels, label_len,
-                               input_len, (uint32_t*)la, (uint32_t*)lb, (uint32_t*)(base + w.dump), ea, eb, logz2, zint, loss,
-                               cls, flags, tickets, (int)grid.x, t_out, k, l_max, k - 1, eps);
-        } else if (wave_f32)
+        } else if (lattice == LAT_LONE_F32)
             hipLaunchKernelGGL(ctc_lattice_wave_kernel<float>, dim3(batch, 3), dim3(64), lds, s, probs, logq, labels,
                                label_len, input_len, (uint32_t*)la, (uint32_t*)lb, (uint32_t*)(base + w.dump), ea, eb, logz2, zint,
                                loss, cls, flags, tickets, (int)grid.x, t_out, k, l_max, k - 1, eps);
@@ -2048,19 +1604,14 @@ extern "C" int sl_ctc_loss_grad(const float* probs, const float* logq, const int
                                loss, cls, flags, tickets, (int)grid.x, t_out, k, l_max, k - 1, eps);
         rc = sl_check_launch("sl_ctc_loss_grad(wave lattice)");
         if (rc != SL_OK) return rc;
-        if (force_repair) {  // tests: every utterance is redone by the repair pass inside the gradient kernel
+        if (row->repair == REP_ALL) {  // tests: every utterance is redone by the repair pass inside the gradient kernel
             rc = (int)hipMemsetAsync(flags, 1, (size_t)batch * sizeof(int32_t), s);
             if (rc != 0) return SL_ERR_LAUNCH_FAILED;
         }
         // rows are 512 values wide; the kernel reads 8 columns per lane.  The repair pass is the tail of this launch
         // (ctc_grad_kernel: the work-group that finishes an utterance last redoes it if it was flagged).
-        int32_t* rep_tickets = repair ? tickets : nullptr;
-        if (pair)
-            hipLaunchKernelGGL((ctc_grad_kernel<8, 3>), grid, dim3(256), lds2, s, probs, logq, labels, label_len,
-                               input_len, (const void*)la, (const void*)lb, ea, eb, logz2, zint, loss, cls, dlogits, t_out, k,
-                               l_max, 64 * WNS, k - 1, frames_per_wg, g_row0, g_row_stride, (long)g_batch_stride, out_f32,
-                               eps, grad_scale, flags, rep_tickets, (double*)alpha, (double*)beta, sp);
-        else if (wave_f32)
+        int32_t* rep_tickets = row->repair != REP_NONE ? tickets : nullptr;
+        if (lattice == LAT_LONE_F32)
             hipLaunchKernelGGL((ctc_grad_kernel<8, 2>), grid, dim3(256), lds2, s, probs, logq, labels, label_len,
                                input_len, (const void*)la, (const void*)lb, ea, eb, logz2, zint, loss, cls, dlogits, t_out, k,
                                l_max, 64 * WNS, k - 1, frames_per_wg, g_row0, g_row_stride, (long)g_batch_stride, out_f32,

@@ -601,10 +601,11 @@ def _ctc_variant(hip_lib, variant):
     hip_lib.call("sl_ctc_select", variant)
 
 
-@pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11])
+@pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5, 6, 7, 10, 11])
 def test_ctc_lattice_variants_against_the_oracle(hip_lib, variant):
     """sl_ctc_loss_grad's lattices -- probability domain, one wave per utterance and direction, in doubles with an exponent
-    per lane and 16 frames (variants 2, 3, 4 and the default) or in floats with one per 8 frames (5, 6, 7) -- and log domain (variant 1; also the repair pass that variants 3 and 7 force for every utterance) -- on the
+    per lane and 16 frames, alone (variants 2, 3, 4) or with a helper wave (10, 11 and the default), or in floats with one per 8
+    frames (5, 6, 7) -- and log domain (variant 1; also the repair pass that variants 3 and 7 force for every utterance) -- on the
     edge cases of round 1 (repeats, empty label, input_len < T', no valid alignment), on labels of 200 graphemes over 500
     frames and on TensorFlow's known answers: same tolerances for all of them."""
     import json
@@ -706,6 +707,29 @@ def test_ctc_probability_domain_lattice_in_the_blank_collapse_regime(hip_lib):
         _report("ctc_float_lattice_alone_in_the_collapse_regime", {
             "loss_rel_err": [float(abs(loss[0] - ref_loss[0]) / ref_loss[0]), float(abs(loss2[0] - ref_loss2[0]) / ref_loss2[0])],
             "gradient_rel_l2": [float(rel_l2(dl, o.softmax_backward(ref_p, ref_dp))), float(rel_l2(dl2, ref_dl2))]})
+    finally:
+        _ctc_variant(hip_lib, 0)
+
+
+def test_ctc_select_refuses_retired_and_unknown_variants(hip_lib):
+    """8 and 9 (the lattice on a pair of waves) are retired: sl_ctc_select refuses them -- and -1 and 12 -- with
+    SL_ERR_INVALID_ARGUMENT, says "retired" for 8 and 9, and leaves the setting as it was: after the refusals a call gives bit
+    for bit what variant 4 gave before them."""
+    from test_gpu_parity import run_ctc_kernel
+    select = hip_lib.raw("sl_ctc_select")
+    rng = np.random.RandomState(11)
+    k, t = 7, 40
+    logits = (rng.randn(2, t, k) * 2).astype(np.float32)
+    labels = o.pack_label_batch([[0, 1, 2, 3], list(rng.randint(0, 6, size=19))])
+    try:
+        assert select(4) == 0
+        _, loss, dl = run_ctc_kernel(hip_lib, logits, labels, [4, 19], [t, t])
+        for bad in (8, 9, -1, 12):
+            assert select(bad) == -1, bad  # SL_ERR_INVALID_ARGUMENT
+            assert ("retired" in hip_lib.last_error()) == (bad in (8, 9)), (bad, hip_lib.last_error())
+        _, loss2, dl2 = run_ctc_kernel(hip_lib, logits, labels, [4, 19], [t, t])
+        assert np.isfinite(loss).all() and dl.any()
+        assert np.array_equal(loss, loss2) and np.array_equal(dl, dl2)
     finally:
         _ctc_variant(hip_lib, 0)
 

@@ -30,7 +30,7 @@ ref_p = o.softmax(logits.astype(np.float64))
 ref_loss, ref_dp = o.ctc_batch_cost(ref_p, labels, input_len, lab_len)
 ref_dl = o.softmax_backward(ref_p, ref_dp)
 print("ref loss", ref_loss)
-for v in (0, 10, 11, 4, 2, 3, 1, 8):
+for v in (0, 10, 11, 4, 2, 3, 1):
     lib.call("sl_ctc_select", v)
     _, loss, dl = run_ctc_kernel(lib, logits, labels, lab_len, input_len)
     errs = [float(np.abs(dl[i] - ref_dl[i]).max()) if np.isfinite(ref_loss[i]) else -1 for i in range(b)]
