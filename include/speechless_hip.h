@@ -341,6 +341,46 @@ int sl_ctc_align(const float* logq, const int32_t* labels, const int32_t* label_
                  int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- ASG criterion (auto segmentation criterion of the wav2letter paper, arXiv:1609.03193).  No reference counterpart:
+ *      the reference raises NotImplementedError where its ASG loss would be (speechless/net.py:397-399). ----------------------
+ * K = k letters and NO blank.  trans: float[k][k], trans[i*k + j] = g(i, j) = the score of moving from letter i to letter
+ * j; init: float[k], g0.  labels, label_len, input_len: as for the CTC loss (L = label_len clamped to [0, l_max], T_b =
+ * input_len clamped to [0, t_out], label values clamped to [0, k)).  Emissions e_t(j) = log(probs_t(j) + eps).
+ *   numerator    a_0(0) = g0(l_0) + e_0(l_0), a_0(s > 0) = -inf;
+ *                a_t(s) = e_t(l_s) + LSE(a_{t-1}(s) + g(l_s, l_s), a_{t-1}(s-1) + g(l_{s-1}, l_s));   N = a_{T_b-1}(L-1)
+ *   denominator  d_0(j) = g0(j) + e_0(j);   d_t(j) = e_t(j) + LSE_i(d_{t-1}(i) + g(i, j));   Z = LSE_j d_{T_b-1}(j)
+ *   loss[b] = Z - N >= 0.  Adjacent equal labels need no special rule.
+ * Gradients of grad_scale * sum_b loss[b], with G_t(j) = (denominator posterior - numerator posterior) of letter j at frame
+ * t, xi the posteriors of a pair of letters at frames t-1, t, p = probs and r = p / (p + eps):
+ *   dlogits_t(j) = grad_scale * (G_t(j) r_t(j) - p_t(j) sum_i G_t(i) r_t(i)), w.r.t. the PRE-softmax logits, written like
+ *                  the CTC gradient (g_row0, g_row_stride, g_batch_stride, dtype; zeros for t >= T_b; may be NULL)
+ *   dtrans[i][j] = grad_scale * sum_b sum_{1 <= t < T_b} (xi_den_t(i, j) - xi_num_t(i, j));  dinit[j] = grad_scale * sum_b G_0(j)
+ * dtrans / dinit (both or neither NULL) are OVERWRITTEN and bitwise reproducible: per-utterance partial sums, reduced over
+ * b = 0 .. B-1 in that order, no float atomics.  An utterance with L = 0, T_b = 0 or L > T_b is infeasible: loss +inf, its
+ * rows of dlogits zero, nothing added to dtrans / dinit.  logq is not read (log(p + eps) is taken from probs in doubles; logq
+ * differs from it by a per-frame constant, which cancels in Z - N) and may be NULL.
+ * Limits: 2 <= k <= 64, 0 <= l_max <= 511, SL_ERR_UNSUPPORTED otherwise (nothing is written).
+ * workspace: sl_asg_workspace_bytes(batch, t_out, k, l_max) bytes (the four lattices in doubles; 0 = unsupported shape). */
+size_t sl_asg_workspace_bytes(int batch, int t_out, int k, int l_max);
+int sl_asg_loss_grad(const float* probs, const float* logq, const float* trans, const float* init, const int32_t* labels,
+                     const int32_t* label_len, const int32_t* input_len, float* loss, void* dlogits, float* dtrans,
+                     float* dinit, int batch, int t_out, int k, int l_max, int g_row0, int g_row_stride,
+                     int64_t g_batch_stride, int dtype, float eps, float grad_scale, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* ---- ASG Viterbi decode over the full graph: the best letter per frame under emissions + transition scores.
+ * logq: float[B][t_out][k], the emissions e_t(j) used AS THEY ARE (sl_softmax_logq's logq: log(p + eps) re-normalised per
+ * frame -- the path is that of log(p + eps), the score differs by the per-frame constants).  fp32:
+ *   v_0(j) = g0(j) + e_0(j);   v_t(j) = (max_i (v_{t-1}(i) + g(i, j))) + e_t(j), strict > in ascending i (the lowest index
+ *   wins a tie); end state = the first maximal j.  Every operation is a max or ONE fp32 add in the order written, so a
+ *   float32 restatement reproduces path and score bit for bit.
+ * path: int32[B][t_out], the letter of the best path per frame, -1 for t >= T_b; score: float[B].  T_b = 0: row -1, score
+ * -inf.  Limits: 2 <= k <= 64.  workspace: sl_asg_viterbi_workspace_bytes(batch, t_out, k), 0 when the backpointers (t_out *
+ * k bytes) fit the work-group's LDS.  One wave per utterance. */
+size_t sl_asg_viterbi_workspace_bytes(int batch, int t_out, int k);
+int sl_asg_viterbi(const float* logq, const float* trans, const float* init, const int32_t* input_len, int32_t* path,
+                   float* score, int batch, int t_out, int k, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CTC beam search, optionally scored by an n-gram language model: the device twin of sl_host_ctc_beam_search
  *      (include/speechless_host.h; speechless/net.py:444-451).  The host decoder is the specification: for the same
  *      inputs the result is the same search, step for step --

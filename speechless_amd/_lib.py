@@ -129,6 +129,14 @@ SIGNATURES = {
     "sl_ctc_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sl_ctc_align": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_void_p, c_size_t, c_void_p]),
+    "sl_asg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    # probs, logq, trans, init, labels, label_len, input_len, loss, dlogits, dtrans, dinit; then sl_ctc_loss_grad's tail
+    "sl_asg_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, c_float, c_float,
+                                 c_void_p, c_size_t, c_void_p]),
+    "sl_asg_viterbi_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sl_asg_viterbi": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                               c_size_t, c_void_p]),
     "sl_edit_distance_supported": (c_int, [c_int, c_int]),
     "sl_edit_distance": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),

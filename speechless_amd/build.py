@@ -13,7 +13,7 @@ HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csr
 CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "misc.hip", "spectrogram.hip", "conv_chain_bf16.hip",
            "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip",
-           "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip"]
+           "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
 # f16x3 parity path (csrc/common.h: SL_MFMA16; only the fp32 / plane-output instantiations, about a third of the bf16 build)
 F16_VARIANTS = {"conv_nt_f16": "conv_nt_bf16.hip", "wgrad_tn_f16": "wgrad_tn_bf16.hip"}
@@ -35,8 +35,10 @@ def _newest_source_mtime():
 # indexed local array crept in)
 # (edit_distance.hip: a lane keeps up to 16 columns of the DP row and their symbols in registers, indexed by unrolled
 # constants; scratch there means an index stopped being a constant and every row of the matrix would go through memory)
+# (asg.hip: a lane's label states, prefetched frames and letter-pair sums are register arrays indexed by unrolled constants;
+# scratch there puts memory traffic on the T'-long sequential path of a lone wave)
 NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
-              "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip"}
+              "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip"}
 
 
 def _scratch_users(remarks):

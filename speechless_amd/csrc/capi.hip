@@ -243,3 +243,63 @@ extern "C" int sl_conv1d_wgrad_grouped(const void* x, const void* g, float* dw, 
     return wgrad_tn_bf16(x, g, dw, geom, cfg, groups, (long)x_group_stride, (long)g_group_stride,
                          (long)dw_group_stride, (float*)workspace, workspace_bytes, (hipStream_t)stream);
 }
+
+// ---- ASG criterion (asg.hip)
+static int asg_limits(const char* who, int k, int l_max) {
+    if (k < 2 || k > 64) {
+        sl_set_error("%s: k = %d outside 2 <= k <= 64 (one lane per letter)", who, k);
+        return SL_ERR_UNSUPPORTED;
+    }
+    if (l_max > 511) {
+        sl_set_error("%s: label length %d > 511 unsupported (at most eight label states per lane)", who, l_max);
+        return SL_ERR_UNSUPPORTED;
+    }
+    return SL_OK;
+}
+
+extern "C" size_t sl_asg_workspace_bytes(int batch, int t_out, int k, int l_max) {
+    if (batch <= 0 || t_out <= 0 || k < 2 || k > 64 || l_max < 0 || l_max > 511) return 0;
+    return asg_workspace_bytes(batch, t_out, k, l_max);
+}
+
+extern "C" int sl_asg_loss_grad(const float* probs, const float* logq, const float* trans, const float* init,
+                                const int32_t* labels, const int32_t* label_len, const int32_t* input_len, float* loss,
+                                void* dlogits, float* dtrans, float* dinit, int batch, int t_out, int k, int l_max, int g_row0,
+                                int g_row_stride, int64_t g_batch_stride, int dtype, float eps, float grad_scale, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    (void)logq;  // the kernels take log(p + eps) from probs in doubles; logq differs from it by a per-frame constant
+    SL_CHECK_ARG(batch > 0 && t_out > 0 && l_max >= 0, "sl_asg_loss_grad: need batch, t_out > 0 and l_max >= 0");
+    const int rc = asg_limits("sl_asg_loss_grad", k, l_max);
+    if (rc != SL_OK) return rc;
+    SL_CHECK_ARG(probs && trans && init && label_len && input_len && loss && (labels || l_max == 0),
+                 "sl_asg_loss_grad: null pointer");
+    SL_CHECK_ARG((dtrans == nullptr) == (dinit == nullptr), "sl_asg_loss_grad: dtrans and dinit go together");
+    SL_CHECK_ARG(dlogits == nullptr || (g_row0 >= 0 && g_row_stride >= k), "sl_asg_loss_grad: bad gradient geometry");
+    SL_CHECK_ARG(eps >= 0.f, "sl_asg_loss_grad: eps must be >= 0");
+    const size_t need = asg_workspace_bytes(batch, t_out, k, l_max);
+    if (workspace == nullptr || workspace_bytes < need) {
+        sl_set_error("sl_asg_loss_grad: workspace too small (%zu < %zu)", workspace_bytes, need);
+        return SL_ERR_WORKSPACE_TOO_SMALL;
+    }
+    return asg_loss_grad(probs, trans, init, labels, label_len, input_len, loss, dlogits, dtrans, dinit, batch, t_out, k, l_max,
+                         g_row0, g_row_stride, (long)g_batch_stride, dtype, eps, grad_scale, workspace, (hipStream_t)stream);
+}
+
+extern "C" size_t sl_asg_viterbi_workspace_bytes(int batch, int t_out, int k) {
+    if (batch <= 0 || t_out <= 0 || k < 2 || k > 64) return 0;
+    return asg_viterbi_workspace_bytes(batch, t_out, k);
+}
+
+extern "C" int sl_asg_viterbi(const float* logq, const float* trans, const float* init, const int32_t* input_len, int32_t* path,
+                              float* score, int batch, int t_out, int k, void* workspace, size_t workspace_bytes, void* stream) {
+    SL_CHECK_ARG(batch > 0 && t_out > 0, "sl_asg_viterbi: need batch, t_out > 0");
+    const int rc = asg_limits("sl_asg_viterbi", k, 0);
+    if (rc != SL_OK) return rc;
+    SL_CHECK_ARG(logq && trans && init && input_len && path && score, "sl_asg_viterbi: null pointer");
+    const size_t need = asg_viterbi_workspace_bytes(batch, t_out, k);
+    if (workspace_bytes < need || (need > 0 && workspace == nullptr)) {
+        sl_set_error("sl_asg_viterbi: workspace too small (%zu < %zu)", workspace_bytes, need);
+        return SL_ERR_WORKSPACE_TOO_SMALL;
+    }
+    return asg_viterbi(logq, trans, init, input_len, path, score, batch, t_out, k, workspace, (hipStream_t)stream);
+}

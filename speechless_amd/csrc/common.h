@@ -165,3 +165,12 @@ int wgrad_tn_f16(const void* x, const void* gr, float* dw, const sl_conv_geom* g
 size_t wgrad_tn_f16_workspace_bytes(const sl_conv_geom* g, int cfg, int groups);
 size_t wgrad_multi_f16_workspace_bytes(const sl_wgrad_job* jobs, int n_jobs);
 int wgrad_multi_f16(const sl_wgrad_job* jobs, int n_jobs, void* ws, size_t ws_bytes, hipStream_t s);
+// asg.hip (arguments validated by capi.hip)
+size_t asg_workspace_bytes(int batch, int t_out, int k, int l_max);
+int asg_loss_grad(const float* probs, const float* trans, const float* init, const int32_t* labels, const int32_t* label_len,
+                  const int32_t* input_len, float* loss, void* dlogits, float* dtrans, float* dinit, int batch, int t_out, int k,
+                  int l_max, int g_row0, int g_row_stride, long g_batch_stride, int dtype, float eps, float grad_scale,
+                  void* workspace, hipStream_t s);
+size_t asg_viterbi_workspace_bytes(int batch, int t_out, int k);
+int asg_viterbi(const float* emis, const float* trans, const float* init, const int32_t* input_len, int32_t* path, float* score,
+                int batch, int t_out, int k, void* workspace, hipStream_t s);

@@ -38,7 +38,12 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
 
     def __init__(self, specs, grapheme_set_size, dtype="bf16", device="cuda:0", ctc_epsilon=1e-8,
                  frozen_layer_count=0, lr=1e-4, beta_1=0.9, beta_2=0.999, adam_epsilon=1e-8, forward_only=False,
-                 clipnorm=0.0, clipvalue=0.0, decay=0.0, track_grad_norm=False):
+                 clipnorm=0.0, clipvalue=0.0, decay=0.0, track_grad_norm=False, criterion="ctc"):
+        if criterion not in ("ctc", "asg"):
+            raise ValueError("criterion must be 'ctc' or 'asg', not {!r}".format(criterion))
+        if criterion == "asg" and (clipnorm or clipvalue or track_grad_norm):
+            raise ValueError("criterion='asg': gradient clipping and the gradient norm cover the conv stack's flat gradient "
+                             "buffer only, not the ASG tables -- clipnorm, clipvalue and track_grad_norm are not supported")
         if not torch.cuda.is_available():
             raise _lib.HipLibraryError("speechless_amd needs a ROCm GPU (torch.cuda.is_available() is False); "
                                        "there is no CPU fallback for the hot path")
@@ -163,6 +168,19 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             self.grads = torch.zeros((off,), dtype=torch.float32, device=dev)
             self.adam_m = torch.zeros((off,), dtype=torch.float32, device=dev)
             self.adam_v = torch.zeros((off,), dtype=torch.float32, device=dev)
+        # ASG criterion (csrc/asg.hip; DESIGN.md "ASG criterion"): the K x K transition scores g[from][to] and the K start
+        # scores g0 are trainable parameters beside the conv stack's, in ONE flat fp32 buffer [g | g0] with a gradient and
+        # Adam moments of the same shape -- one sl_adam_step launch updates both tables.  Zero = the paper's initialisation.
+        self.criterion = criterion
+        self.asg_params = self.asg_grads = self.asg_adam_m = self.asg_adam_v = None
+        if criterion == "asg":
+            if not 2 <= grapheme_set_size <= 64:
+                raise ValueError("criterion='asg' takes 2 .. 64 graphemes (one lane per letter), not {}".format(grapheme_set_size))
+            n_asg = _round_up(grapheme_set_size * (grapheme_set_size + 1), 4)  # (sl_adam_step works on groups of four)
+            self.asg_params = torch.zeros((n_asg,), dtype=torch.float32, device=dev)
+            if not self.forward_only:
+                self.asg_grads, self.asg_adam_m, self.asg_adam_v = (
+                    torch.zeros((n_asg,), dtype=torch.float32, device=dev) for _ in range(3))
         self._weights_set_count = 0
         pl = self.planes  # bf16x3: packed weight rows are [w_hi | w_hi | w_lo]
         self.w_fwd = [torch.zeros((p.cout_pad, p.spec.kernel_size, p.cin_pad * pl), dtype=self.torch_dtype, device=dev)
@@ -228,6 +246,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         # launches (sl_conv1d_backward_1x1_part accumulates the output layer's).  Used where it pays (_split_parts: long
         # utterances in small batches, i.e. configuration 5); SL_SPLIT_TOP=0: the whole-batch sequence everywhere.
         self.split_top = os.environ.get("SL_SPLIT_TOP", "1") != "0"
+        if criterion == "asg":  # the split schedule launches the CTC of each part itself (engine_split.py): whole-batch sequence
+            self.split_top = False
         self.split_min_tiles = None
         # Data-parallel runs: CUs the communication kernels are expected to own while a bucket is on the wire.  The MFMA
         # kernels take a whole CU per work-group and their grids are sized to whole rounds of the chip, so backward() tells
@@ -631,6 +651,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         split_ctc=(grad_scale, a) (train_step_resident, a = split_top_plan()): the top three layers run in two parts of the
         batch -- utterances [0, a) and [a, B) -- and each part's CTC loss + gradient (ctc(grad_scale)) is launched on a side
         stream as soon as its probabilities exist; backward() picks the parts up (see self.split_top)."""
+        if split_ctc is not None and self.criterion == "asg":
+            raise ValueError("criterion='asg': the split-top schedule launches the CTC loss of each part; not supported")
         buf = self.load_input(input_batch) if input_batch is not None else self.cur
         if self._packed_dirty:
             self.repack_weights()
@@ -757,10 +779,12 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         if labels.ndim != 2 or labels.shape[0] != buf.batch:
             raise ValueError("label batch must be (B, Lmax)")
         k = self.grapheme_set_size
+        top = k if self.criterion == "asg" else k - 1  # (ASG has no blank: every index is a label)
         for i in range(buf.batch):
             row = labels[i, :lab_len[i]]
-            if row.size and (row.min() < 0 or row.max() >= k - 1):
-                raise ValueError("label {} holds an index outside [0, {}) (blank is {})".format(i, k - 1, k - 1))
+            if row.size and (row.min() < 0 or row.max() >= top):
+                raise ValueError("label {} holds an index outside [0, {}){}".format(
+                    i, top, "" if self.criterion == "asg" else " (blank is {})".format(k - 1)))
         l_max = max(int(labels.shape[1]), 1)
         if labels.shape[1] == 0:
             labels = np.zeros((buf.batch, 1), dtype=np.int32)
@@ -809,12 +833,150 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                          cp, buf.tt_pad * cp, HALO, buf.rows * cp * self.planes, 0, self._stream())
         return buf.loss
 
+    # ------------------------------------------------------------------ ASG criterion (csrc/asg.hip)
+
+    def _asg_views(self, flat):
+        k = self.grapheme_set_size
+        return flat[:k * k].view(k, k), flat[k * k:k * k + k]
+
+    @property
+    def asg_trans(self):
+        """the transition scores g[from][to], float32 (K, K) in HBM (a view of asg_params)"""
+        return self._asg_views(self.asg_params)[0]
+
+    @property
+    def asg_init(self):
+        """the start scores g0, float32 (K,) in HBM (a view of asg_params)"""
+        return self._asg_views(self.asg_params)[1]
+
+    @property
+    def asg_dtrans(self):
+        return self._asg_views(self.asg_grads)[0]
+
+    @property
+    def asg_dinit(self):
+        return self._asg_views(self.asg_grads)[1]
+
+    def set_asg_scores(self, trans, init):
+        """trans (K, K) [from][to] and init (K,) numpy: the scores themselves (not probabilities)"""
+        k = self.grapheme_set_size
+        trans, init = np.asarray(trans, dtype=np.float32), np.asarray(init, dtype=np.float32)
+        if trans.shape != (k, k) or init.shape != (k,):
+            raise ValueError("ASG scores must have shapes ({0}, {0}) and ({0},), not {1} and {2}".format(k, trans.shape, init.shape))
+        self.asg_params[:k * k + k].copy_(torch.from_numpy(np.concatenate([trans.ravel(), init])))
+        self._weights_set_count += 1
+
+    def get_asg_state(self):
+        """{'trans', 'init'} and, on a training engine, their Adam moments 'trans_m', 'trans_v', 'init_m', 'init_v' (numpy)"""
+        out = {}
+        named = [("", self.asg_params)] + ([] if self.forward_only else [("_m", self.asg_adam_m), ("_v", self.asg_adam_v)])
+        for suffix, flat in named:
+            trans, init = self._asg_views(flat)
+            out["trans" + suffix], out["init" + suffix] = trans.cpu().numpy().copy(), init.cpu().numpy().copy()
+        return out
+
+    def set_asg_state(self, state):
+        """what get_asg_state returned (the moments are optional: a file of scores alone restarts them at zero)"""
+        self.set_asg_scores(state["trans"], state["init"])
+        if self.forward_only:
+            return
+        for suffix, flat in (("_m", self.asg_adam_m), ("_v", self.asg_adam_v)):
+            if "trans" + suffix in state:
+                k = self.grapheme_set_size
+                flat[:k * k + k].copy_(torch.from_numpy(np.concatenate([
+                    np.asarray(state["trans" + suffix], dtype=np.float32).ravel(),
+                    np.asarray(state["init" + suffix], dtype=np.float32).ravel()])))
+            else:
+                flat.zero_()
+
+    def _require_asg(self, what):
+        if self.criterion != "asg":
+            raise ValueError("{} needs an engine built with criterion='asg'".format(what))
+
+    def asg(self, grad_scale=None):
+        """ctc() for the ASG criterion: the per-utterance loss Z - N of the current probabilities under the engine's scores
+        (tensor (B,) in HBM), into g[last] the gradient w.r.t. the output_conv logits of grad_scale * sum_b loss_b (default
+        1/B), and into asg_dtrans / asg_dinit (overwritten) the gradients of the two tables.  A forward_only engine computes
+        the loss alone.  Labels: set_labels, every index in [0, K)."""
+        self._require_asg("asg()")
+        buf = self.cur
+        if grad_scale is None:
+            grad_scale = 1.0 / buf.batch
+        k = self.grapheme_set_size
+        l_max = buf.labels.shape[1]
+        buf.grow("asg_ws", self.lib.raw("sl_asg_workspace_bytes")(buf.batch, buf.tt_pad, k, l_max), 16)
+        trans, init = self._asg_views(self.asg_params)
+        ws = (buf.asg_ws.data_ptr(), buf.asg_ws.numel(), self._stream())
+        if self.forward_only:
+            self._launch("asg", "sl_asg_loss_grad", buf.probs.data_ptr(), buf.logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                         buf.labels.data_ptr(), buf.label_len.data_ptr(), buf.input_len.data_ptr(), buf.loss.data_ptr(), None,
+                         None, None, buf.batch, buf.t_out, k, l_max, 0, k, 0, _lib.SL_F32, self.ctc_epsilon, grad_scale, *ws)
+            return buf.loss
+        buf.ensure_backward(self)
+        last = len(self.plans) - 1
+        cp = self.plans[last].cout_pad
+        x3 = self.planes > 1
+        if x3:  # fp32 dL/dlogits into the staging buffer, then into the planes of g[last] (as ctc())
+            buf.stage32[:buf.batch * buf.tt_pad * cp].zero_()
+            grad, halo, batch_stride, code, scale = buf.stage32, 0, buf.tt_pad * cp, _lib.SL_F32, grad_scale * self.g_scale
+        else:
+            grad, halo, batch_stride, code, scale = buf.g[last], HALO, buf.rows * cp, self.dtype_code, grad_scale
+        dtrans, dinit = self._asg_views(self.asg_grads)
+        self._launch("asg", "sl_asg_loss_grad", buf.probs.data_ptr(), buf.logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                     buf.labels.data_ptr(), buf.label_len.data_ptr(), buf.input_len.data_ptr(), buf.loss.data_ptr(),
+                     grad.data_ptr(), dtrans.data_ptr(), dinit.data_ptr(), buf.batch, buf.t_out, k, l_max, halo, cp,
+                     batch_stride, code, self.ctc_epsilon, scale, *ws)
+        if x3:
+            # (the table gradients carry the planes' power-of-two scale too: taken out again, exactly)
+            if self.g_scale != 1.0:
+                self._launch("scale:asg", "sl_scale", self.asg_grads.data_ptr(), self.asg_grads.numel(), _lib.SL_F32,
+                             1.0 / self.g_scale, self._stream())
+            self._launch("split:asg", self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[last].data_ptr(), None, buf.batch,
+                         buf.t_out, cp, buf.tt_pad * cp, HALO, buf.rows * cp * self.planes, 0, self._stream())
+        return buf.loss
+
+    def loss(self, grad_scale=None):
+        """the engine's criterion on the current probabilities and labels: ctc() or asg()"""
+        return self.asg(grad_scale) if self.criterion == "asg" else self.ctc(grad_scale)
+
+    def asg_viterbi(self, prediction_lengths=None):
+        """greedy_decode() for the ASG criterion: the best letter sequence under emissions + scores (sl_asg_viterbi on the
+        current logq), repeats merged.  Returns (list of index lists, per-frame path (B, T') numpy with -1 past T_b)."""
+        self._require_asg("asg_viterbi()")
+        buf = self.cur
+        if prediction_lengths is not None:
+            self.set_input_lengths(prediction_lengths)
+        k = self.grapheme_set_size
+        buf.grow("asg_vit_ws", self.lib.raw("sl_asg_viterbi_workspace_bytes")(buf.batch, buf.tt_pad, k), 16)
+        if getattr(buf, "asg_score", None) is None:
+            buf.asg_score = torch.zeros((buf.batch,), dtype=torch.float32, device=self.device)
+        trans, init = self._asg_views(self.asg_params)
+        path = buf.frame_argmax  # int32 (B, T'): the per-frame result of the decode, as greedy_decode keeps it
+        self._launch("asg_viterbi", "sl_asg_viterbi", buf.logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                     buf.input_len.data_ptr(), path.data_ptr(), buf.asg_score.data_ptr(), buf.batch, buf.t_out, k,
+                     buf.asg_vit_ws.data_ptr(), buf.asg_vit_ws.numel(), self._stream())
+        paths = path.cpu().numpy()
+        decoded = []
+        for row in paths:
+            row = row[row >= 0]
+            decoded.append([int(g) for g in row[np.concatenate([[True], row[1:] != row[:-1]])]] if row.size else [])
+        return decoded, paths
+
+    def asg_adam_step(self):
+        """Adam on the two ASG tables with the step's hyper-parameters and iteration count (adam_iterations already counts
+        this step): one sl_adam_step launch over [g | g0]."""
+        self._launch("adam:asg", "sl_adam_step", self.asg_params.data_ptr(), self.asg_grads.data_ptr(),
+                     self.asg_adam_m.data_ptr(), self.asg_adam_v.data_ptr(), self.asg_params.numel(), self.adam_iterations,
+                     self._lr_now(), self.beta_1, self.beta_2, self.adam_epsilon, self._stream())
+
     def ctc_align(self, label_batch, label_lengths, prediction_lengths):
         """CTC forced alignment (Viterbi) of the labels on the current buffer set's logq -- the distribution ctc() sees --
         after forward().  label_batch: int (B, Lmax) padded with anything; lengths: (B,) or (B, 1).  Returns (paths int32
         (B, T') numpy: the lattice state of the best path per frame, -1 past the utterance's length or for every frame of
         an infeasible one; scores float32 (B,) numpy: its log-probability, -inf when infeasible).  Semantics:
         sl_ctc_align (include/speechless_hip.h).  Uses tensors of its own: no gradient buffers, labels of ctc() untouched."""
+        if self.criterion == "asg":
+            raise ValueError("criterion='asg': forced alignment runs over the CTC lattice (blank = K - 1); not supported")
         buf = self.cur
         labels = np.asarray(label_batch, dtype=np.int32)
         lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
@@ -1366,6 +1528,9 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
     def train_step_resident(self, reducer=None):
         """Same, with input / labels / lengths already resident in HBM (bench.py's timed region)."""
         dp = reducer is not None and (reducer.world_size > 1 or reducer.force)
+        if dp and self.criterion == "asg":
+            raise ValueError("criterion='asg': the gradients of the ASG tables are in no bucket of the data-parallel exchange; "
+                             "train on one GPU")
         world = reducer.world_size if reducer is not None else 1
         self._sharded_reducer = reducer if (dp and reducer.shard_optimizer) else None
         self.set_comm_cus(getattr(reducer, "comm_cus", 0) if dp else 0)
@@ -1376,10 +1541,12 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             loss = self.cur.loss
         else:
             self.forward(training=True)
-            loss = self.ctc(grad_scale=grad_scale)
+            loss = self.loss(grad_scale=grad_scale)
         if not dp:
             self.backward()
             self.adam_step()
+            if self.criterion == "asg":
+                self.asg_adam_step()
             return loss
         self.backward(on_bucket_ready=reducer.reduce_bucket)
         # every bucket's exchange was started the moment its last weight gradient was enqueued; the big ones finished

@@ -18,7 +18,7 @@ import numpy as np
 
 from .engine import Engine, wav2letter_layer_specs
 from .error_counts import edit_distance, space_index_of
-from .grapheme_encoding import CtcGraphemeEncoding
+from .grapheme_encoding import AsgGraphemeEncoding, CtcGraphemeEncoding
 
 logger = logging.getLogger("results")
 if not logger.handlers:
@@ -249,11 +249,25 @@ class Wav2Letter:
                  # --- extensions of this implementation (keyword-only in spirit) ---
                  compute_dtype=None, device="cuda:0", seed=None, ctc_epsilon=1e-8, layer_sizes=None,
                  load_optimizer_state=False, eval_dtype=None, beam_search_device="host", track_gradient_norm=False,
-                 error_count_device="host"):
+                 error_count_device="host", criterion="ctc"):
         if frozen_layer_count > 0 and load_model_from_directory is None:
             raise ValueError("Layers cannot be frozen if model is trained from scratch.")
         if use_asg:
             raise NotImplementedError("ASG is not yet implemented.")  # as reference net.py:396-399
+        # extension: criterion="asg" is this implementation's ASG (csrc/asg.hip; DESIGN.md "ASG criterion") -- use_asg keeps
+        # raising as the reference does.  "asg" reads asg_transition_probabilities / asg_initial_probabilities (ignored
+        # under "ctc", as ever), encodes labels with AsgGraphemeEncoding (K = characters + 2, no blank), trains and
+        # evaluates with the ASG loss and decodes by the Viterbi path over emissions + transition scores.
+        if criterion not in ("ctc", "asg"):
+            raise ValueError("criterion must be 'ctc' or 'asg', not {!r}".format(criterion))
+        self.criterion = criterion
+        if criterion == "asg":
+            if kenlm_directory is not None:
+                raise ValueError("criterion='asg': the beam search (kenlm_directory) is a CTC decoder; not supported")
+            clipped = optimizer is not None and optimizer_settings(optimizer)
+            if track_gradient_norm or (clipped and (clipped["clipnorm"] or clipped["clipvalue"])):
+                raise ValueError("criterion='asg': gradient clipping (clipnorm / clipvalue) and track_gradient_norm cover the "
+                                 "conv stack's gradients only, not the ASG tables; not supported")
         if dropout is not None and not 0.0 <= dropout < 1.0:
             raise ValueError("dropout must be a rate in [0, 1)")
         self.kenlm_directory = kenlm_directory
@@ -265,7 +279,8 @@ class Wav2Letter:
         self.error_count_device = error_count_device
         # extension: "gpu" takes the letter / word error counts of test_and_predict_batch from csrc/edit_distance.hip
         self._space_index = space_index_of(allowed_characters) if error_count_device == "gpu" else None
-        self.grapheme_encoding = CtcGraphemeEncoding(allowed_characters=allowed_characters)
+        self.grapheme_encoding = (AsgGraphemeEncoding if criterion == "asg" else CtcGraphemeEncoding)(
+            allowed_characters=allowed_characters)
         self.use_asg = use_asg
         self.frozen_layer_count = frozen_layer_count
         self.output_activation = output_activation
@@ -296,7 +311,10 @@ class Wav2Letter:
                                        use_raw_wave_input=use_raw_wave_input, **self._layer_sizes)
         self.engine = Engine(specs, self.grapheme_encoding.grapheme_set_size, dtype=compute_dtype, device=device,
                              ctc_epsilon=ctc_epsilon, frozen_layer_count=frozen_layer_count,
-                             track_grad_norm=track_gradient_norm, **optimizer_settings(self.optimizer))
+                             track_grad_norm=track_gradient_norm, criterion=criterion, **optimizer_settings(self.optimizer))
+        if criterion == "asg":
+            self.engine.set_asg_scores(*self._asg_scores(asg_transition_probabilities, asg_initial_probabilities,
+                                                         self.grapheme_encoding.grapheme_set_size, ctc_epsilon))
         self.engine.dropout_rate = dropout if dropout else None  # applied by training steps only (learning phase 1)
         # the reference signature has no seed: a plain Wav2Letter(..., dropout=0.1) draws one (Keras does the same)
         self.engine.dropout_seed = int(seed) if seed is not None else \
@@ -342,10 +360,47 @@ class Wav2Letter:
                             np.zeros((s.cout,), dtype=np.float32)))
         return weights
 
+    @staticmethod
+    def _asg_scores(transition_probabilities, initial_probabilities, k, eps):
+        """The ASG tables a net starts from: log(P + eps) of the given probabilities -- (K, K) [from][to] and (K,), or the
+        (K + 1, K + 1) / (K + 1,) form of the reference's defaults with row, column and entry 0 dropped (net.py:274-277,
+        285-286) -- and all-zero scores for None, the initialisation of the wav2letter paper.  (The reference's own default
+        is an unseeded random draw, net.py:273 / :285, that nothing can reproduce: it is not imitated.)"""
+        def scores(p, shape, what):
+            if p is None:
+                return np.zeros(shape, dtype=np.float32)
+            p = np.asarray(p, dtype=np.float64)
+            if p.shape == tuple(n + 1 for n in shape):
+                p = p[(slice(1, None),) * len(shape)]
+            if p.shape != shape or (p < 0).any():
+                raise ValueError("{} must be non-negative with shape {} (or one larger: the reference's form with index 0 "
+                                 "unused), got shape {}".format(what, shape, p.shape))
+            return np.log(p + eps).astype(np.float32)
+        return (scores(transition_probabilities, (k, k), "asg_transition_probabilities"),
+                scores(initial_probabilities, (k,), "asg_initial_probabilities"))
+
     # ------------------------------------------------------------------ weights (net.py:184-269, 558-560)
     @staticmethod
     def model_file_name(epoch):
         return "weights-epoch{}.h5".format(epoch)
+
+    @staticmethod
+    def asg_file_name(epoch):
+        return "asg-epoch{}.npz".format(epoch)
+
+    def save_asg_state(self, net_directory, epoch):
+        """criterion="asg": the transition scores, the start scores and their Adam moments, beside the weights file"""
+        Path(net_directory).mkdir(parents=True, exist_ok=True)
+        np.savez(str(Path(net_directory) / self.asg_file_name(epoch)), **self.engine.get_asg_state())
+
+    def _load_asg_state(self, net_directory, epoch, with_moments):
+        """reads asg-epoch{N}.npz when the net is an ASG net and the file is there (a CTC checkpoint has none)"""
+        path = Path(net_directory) / self.asg_file_name(epoch)
+        if self.criterion != "asg" or not path.exists():
+            return
+        data = np.load(str(path))
+        names = [n for n in data.files if with_moments or n in ("trans", "init")]
+        self.engine.set_asg_state({n: data[n] for n in names})
 
     @staticmethod
     def optimizer_state_file_name(epoch):
@@ -363,6 +418,7 @@ class Wav2Letter:
         np.savez(str(Path(net_directory) / self.optimizer_state_file_name(epoch)), **arrays)
 
     def load_optimizer_state(self, net_directory, epoch):
+        self._load_asg_state(net_directory, epoch, with_moments=True)
         data = np.load(str(Path(net_directory) / self.optimizer_state_file_name(epoch)))
         names = [layer.name for layer in self.predictive_net.layers]
         self.engine.set_optimizer_state({
@@ -391,7 +447,11 @@ class Wav2Letter:
         path = Path(load_model_from_directory) / self.model_file_name(load_epoch)
         if allowed_characters_for_loaded_model is None:
             self.predictive_net.load_weights(path)
+            self._load_asg_state(load_model_from_directory, load_epoch, with_moments=False)
             return
+        if self.criterion == "asg":
+            raise ValueError("criterion='asg': re-mapping a loaded model's characters (allowed_characters_for_loaded_model) "
+                             "follows the CTC blank; not supported")
         layer_count = len(self.predictive_net.layers)
         if loaded_first_layers_count is None:
             loaded_first_layers_count = layer_count
@@ -451,8 +511,14 @@ class Wav2Letter:
             Wav2Letter.InputNames.input_batch: input_batch,
             Wav2Letter.InputNames.prediction_lengths: np.reshape(np.array(prediction_lengths), (n, 1)),
             Wav2Letter.InputNames.label_batch: self.grapheme_encoding.encode_label_batch(labels),
-            Wav2Letter.InputNames.label_lengths: np.reshape(np.array([len(l) for l in labels]), (n, 1)),
+            Wav2Letter.InputNames.label_lengths: np.reshape(self._label_lengths(labels), (n, 1)),
         }
+
+    def _label_lengths(self, labels):
+        """graphemes per label: its characters -- under ASG its ENCODED length (a repeat mark replaces one or two letters)"""
+        if self.criterion == "asg":
+            return np.array([len(self.grapheme_encoding.encode(l)) for l in labels], dtype=np.int32)
+        return np.array([len(l) for l in labels], dtype=np.int32)
 
     # ------------------------------------------------------------------ inference (net.py:350-357, 461-498)
     @property
@@ -467,8 +533,9 @@ class Wav2Letter:
         if self._eval_engine is None:
             ev = Engine(list(train.all_specs), self.grapheme_encoding.grapheme_set_size, dtype=self.eval_dtype,
                         device=self.device, ctc_epsilon=self.ctc_epsilon, frozen_layer_count=self.frozen_layer_count,
-                        forward_only=True)
+                        forward_only=True, criterion=self.criterion)
             ev.params = train.params  # the masters themselves: same plan, same offsets (Engine.__init__ does not depend on dtype)
+            ev.asg_params = train.asg_params  # (None under CTC; the ASG tables are read in place, never packed)
             assert ev.param_numel == train.param_numel
             self._eval_engine = ev
             self._eval_weights_version = None
@@ -491,8 +558,15 @@ class Wav2Letter:
         input_batch, prediction_lengths = self._input_batch_and_prediction_lengths(spectrograms)
         engine = self.eval_engine
         engine.forward(input_batch)
-        decoded, _ = engine.greedy_decode(prediction_lengths)
+        decoded, _ = self._decode(engine, prediction_lengths)
         return [self.grapheme_encoding.decode_graphemes(d, merge_repeated=False) for d in decoded]
+
+    def _decode(self, engine, prediction_lengths=None):
+        """greedy CTC decode, or under ASG the Viterbi path with repeats merged (each grapheme is then decoded with its
+        predecessor: AsgGraphemeEncoding.decode_graphemes)"""
+        if self.criterion == "asg":
+            return engine.asg_viterbi(prediction_lengths)
+        return engine.greedy_decode(prediction_lengths)
 
     def predict_batch_greedily_from_audio(self, raw_audio_batch, sample_rate=16000, fourier_window_length=512,
                                           hop_length=128):
@@ -506,7 +580,7 @@ class Wav2Letter:
         x, frames = extractor.batch(raw_audio_batch)
         engine = self.eval_engine
         engine.forward(x)
-        decoded, _ = engine.greedy_decode([n // self.input_to_prediction_length_ratio for n in frames])
+        decoded, _ = self._decode(engine, [n // self.input_to_prediction_length_ratio for n in frames])
         return [self.grapheme_encoding.decode_graphemes(d, merge_repeated=False) for d in decoded]
 
     def test_and_predict_batch(self, labeled_spectrogram_batch):
@@ -517,14 +591,14 @@ class Wav2Letter:
         engine.forward(inputs[names.input_batch])
         engine.set_labels(inputs[names.label_batch], inputs[names.label_lengths],
                           inputs[names.prediction_lengths])
-        losses = engine.ctc().cpu().numpy()
+        losses = engine.loss().cpu().numpy()
         if self._beam_decoder is not None and self.beam_search_device == "gpu":
             decoded, _ = engine.beam_search(self._beam_decoder, inputs[names.prediction_lengths])
         elif self._beam_decoder is not None:  # net.py:444-451: beam search scored by the language model
             decoded, _ = self._beam_decoder.decode(engine.cur.probs.cpu().numpy(),
                                                    inputs[names.prediction_lengths])
         else:
-            decoded, _ = engine.greedy_decode()
+            decoded, _ = self._decode(engine)
         predictions = [self.grapheme_encoding.decode_graphemes(d, merge_repeated=False) for d in decoded]
         n = len(predictions)
         letter_errors = word_errors = [None] * n  # None: ExpectationVsPrediction counts on the host (net.py:31-37)
@@ -543,6 +617,9 @@ class Wav2Letter:
         evaluation engine and one sl_ctc_align launch over the distribution the CTC loss sees.  Inputs and lengths are
         packed as test_and_predict_batch packs them.  Returns a list of alignment.CtcAlignment (frames = output frames)."""
         from .alignment import CtcAlignment
+        if self.criterion == "asg":
+            raise ValueError("criterion='asg': forced alignment (alignment_batch, positional_label_batch) runs over the CTC "
+                             "lattice; not supported")
         inputs = self._input_dictionary_for_loss_net(labeled_spectrogram_batch)
         names = Wav2Letter.InputNames
         engine = self.eval_engine
@@ -624,15 +701,14 @@ class Wav2Letter:
         spectrograms = [np.asarray(x.z_normalized_transposed_spectrogram()) for x in labeled_spectrogram_batch]
         labels = [x.label for x in labeled_spectrogram_batch]
         ratio = self.input_to_prediction_length_ratio
-        return (spectrograms, self.grapheme_encoding.encode_label_batch(labels),
-                np.array([len(l) for l in labels], dtype=np.int32),
+        return (spectrograms, self.grapheme_encoding.encode_label_batch(labels), self._label_lengths(labels),
                 np.array([s.shape[0] // ratio for s in spectrograms], dtype=np.int32))
 
     def _pack_audio_for_staging(self, labeled_example_batch):
         """The host half of a training step from raw audio (pipeline.AudioBatchStager): samples and encoded labels."""
         labels = [x.label for x in labeled_example_batch]
         return ([x.get_raw_audio() for x in labeled_example_batch], self.grapheme_encoding.encode_label_batch(labels),
-                np.array([len(l) for l in labels], dtype=np.int32))
+                self._label_lengths(labels))
 
     def _audio_extractor(self, example):
         """The GPU front end matching this net's input (mel count = input size, or the linear 1 + n_fft / 2 bins) with the
@@ -699,12 +775,12 @@ class Wav2Letter:
             extractor = self._audio_extractor(first[0]) if first else None
             stager = AudioBatchStager(with_first(), self._pack_audio_for_staging, extractor,
                                       self.input_to_prediction_length_ratio, self.engine.device,
-                                      blank=self.grapheme_encoding.grapheme_set_size - 1, depth=prefetch_depth)
+                                      blank=self.grapheme_encoding.grapheme_set_size - (0 if self.criterion == "asg" else 1), depth=prefetch_depth)
             batches = iter(stager)
         elif prefetch_depth > 0:
             from .pipeline import BatchStager
             stager = BatchStager(labeled_spectrogram_batches, self._pack_for_staging, self.engine.device,
-                                 blank=self.grapheme_encoding.grapheme_set_size - 1, depth=prefetch_depth)
+                                 blank=self.grapheme_encoding.grapheme_set_size - (0 if self.criterion == "asg" else 1), depth=prefetch_depth)
             batches = iter(stager)
         else:
             batches = iter(labeled_spectrogram_batches)
@@ -735,6 +811,8 @@ class Wav2Letter:
                 if epoch > 0:
                     Path(net_directory).mkdir(parents=True, exist_ok=True)
                     self.predictive_net.save_weights(Path(net_directory) / self.model_file_name(epoch))
+                    if self.criterion == "asg":
+                        self.save_asg_state(net_directory, epoch)
                     if save_optimizer_state:
                         self.save_optimizer_state(net_directory, epoch)
                 epoch += 1
