@@ -543,6 +543,50 @@ int sl_splitf16_adam_pack_layers_clipped(float* param, const float* grad, float*
                                          int n_layers, int step, float lr, float beta1, float beta2, float eps, float w_scale,
                                          const float* grad_scale, float clipvalue, void* stream);
 
+/* ---- Keras-2.0 optimizers beside Adam (optimizers.py of Keras 2.0.x; restated, like the Adam row -- not checkable offline) --
+ * g: the gradient after clipping (as in the clipped Adam twins); lr: the DECAYED rate lr0 / (1 + decay * it), computed by the
+ * caller; state slots start at zero.
+ *   SGD       v = momentum * m - lr * g;  m' = v;  p' = p + v            (nesterov: p' = p + momentum * v - lr * g)   1 slot
+ *   RMSprop   a' = rho * a + (1 - rho) * g^2;  p' = p - lr * g / (sqrt(a') + eps)                                     1 slot
+ *   Adagrad   a' = a + g^2;                    p' = p - lr * g / (sqrt(a') + eps)                                     1 slot
+ *   Adadelta  a' = rho * a + (1 - rho) * g^2;  u = g * sqrt(d + eps) / sqrt(a' + eps);  p' = p - lr * u;
+ *             d' = rho * d + (1 - rho) * u^2                                                                          2 slots (a, d)
+ *   Adamax    m' = b1 * m + (1 - b1) * g;  u' = max(b2 * u, |g|);  p' = p - lr * m' / (u' + eps), where lr is ALREADY
+ *             lr_decayed / (1 - b1^t), divided by the caller in double                                                2 slots (m, u)
+ * s0 / s1 are the slots in the order named above.  A one-slot rule takes s1 == NULL and the kernels neither read nor write a
+ * second buffer (3 fp32 reads + 2 writes per parameter instead of Adam's 4 + 3); a two-slot rule requires s1.
+ * grad_scale (device float*, NULL = 1) and clipvalue (0 = off) as in the clipped Adam twins: with NULL and 0 the instantiation
+ * without clipping is launched.  The flat and the fused kernels apply ONE definition of each rule: the same bits.
+ * SL_OPT_ADAM names Adam's place in the kernels' rule table; Adam keeps its own entry points above (they take the step
+ * count) and these reject it. */
+#define SL_OPT_ADAM 0
+#define SL_OPT_SGD 1
+#define SL_OPT_RMSPROP 2
+#define SL_OPT_ADAGRAD 3
+#define SL_OPT_ADADELTA 4
+#define SL_OPT_ADAMAX 5
+typedef struct {
+    int32_t rule;     /* SL_OPT_* */
+    float lr;         /* decayed; Adamax: and divided by 1 - beta1^t */
+    float momentum;   /* SGD */
+    int32_t nesterov; /* SGD: 0 / 1 */
+    float rho;        /* RMSprop, Adadelta */
+    float beta1, beta2; /* Adamax */
+    float eps;        /* all but SGD */
+} sl_opt_rule;
+/* sl_adam_step_clipped / sl_adam_pack_layers_clipped / sl_split3_... / sl_splitf16_... for these rules (n a multiple of 4;
+ * 1 .. SL_ADAM_MAX_LAYERS layers, the table and the operand formats of the Adam versions) */
+int sl_optimizer_step(float* param, const float* grad, float* s0, float* s1, size_t n, const sl_opt_rule* rule,
+                      const float* grad_scale, float clipvalue, void* stream);
+int sl_optimizer_pack_layers(float* param, const float* grad, float* s0, float* s1, const sl_adam_layer* layers, int n_layers,
+                             int dtype, const sl_opt_rule* rule, const float* grad_scale, float clipvalue, void* stream);
+int sl_split3_optimizer_pack_layers(float* param, const float* grad, float* s0, float* s1, const sl_adam_layer* layers,
+                                    int n_layers, const sl_opt_rule* rule, const float* grad_scale, float clipvalue,
+                                    void* stream);
+int sl_splitf16_optimizer_pack_layers(float* param, const float* grad, float* s0, float* s1, const sl_adam_layer* layers,
+                                      int n_layers, const sl_opt_rule* rule, float w_scale, const float* grad_scale,
+                                      float clipvalue, void* stream);
+
 /* ---- "bf16x3": the fast parity path ---------------------------------------------------------------------------------------
  * north_star: greedy-decoded indices bit-exact against the reference's fp32 CPU path (net.py:417-436 on Keras / TF float32),
  * gradients within 1e-3.  Every fp32 value is carried as two bf16 numbers (hi = bf16(v), lo = bf16(v - hi)) in THREE planes

@@ -7,7 +7,7 @@ from .grapheme_encoding import CtcGraphemeEncoding, english_frequent_characters,
 
 
 def __getattr__(name):
-    if name in ("Wav2Letter", "Adam", "LabeledSpectrogram", "ExpectationVsPrediction", "ExpectationsVsPredictions",
+    if name in ("Wav2Letter", "Adam", "SGD", "RMSprop", "Adagrad", "Adadelta", "Adamax", "LabeledSpectrogram", "ExpectationVsPrediction", "ExpectationsVsPredictions",
                 "ExpectationsVsPredictionsInBatches", "ExpectationsVsPredictionsInGroupedBatches"):
         from . import net
         return getattr(net, name)

@@ -34,6 +34,17 @@ class AdamLayer(ctypes.Structure):
                 ("cout_pad", c_int32)]
 
 
+class OptRule(ctypes.Structure):
+    """Mirror of sl_opt_rule (include/speechless_hip.h)."""
+    _fields_ = [("rule", c_int32), ("lr", c_float), ("momentum", c_float), ("nesterov", c_int32), ("rho", c_float),
+                ("beta1", c_float), ("beta2", c_float), ("eps", c_float)]
+
+
+# SL_OPT_* (include/speechless_hip.h); the number of fp32 state slots per parameter of each rule
+OPT_RULES = {"adam": 0, "sgd": 1, "rmsprop": 2, "adagrad": 3, "adadelta": 4, "adamax": 5}
+OPT_SLOTS = {"adam": 2, "sgd": 1, "rmsprop": 1, "adagrad": 1, "adadelta": 2, "adamax": 2}
+
+
 class BgwLayer(ctypes.Structure):
     """Mirror of sl_bgw_layer (include/speechless_hip.h)."""
     _fields_ = [("w_off", c_int64), ("b_off", c_int64), ("k", c_int32), ("cin_pad", c_int32), ("cout_pad", c_int32),
@@ -201,6 +212,15 @@ SIGNATURES = {
                                                    c_float, c_float, c_float, c_float, c_void_p, c_float, c_void_p]),
     "sl_splitf16_adam_pack_layers_clipped": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamLayer), c_int, c_int,
                                                      c_float, c_float, c_float, c_float, c_float, c_void_p, c_float, c_void_p]),
+    # the rules beside Adam: param, grad, s0, s1 (NULL for a one-slot rule), ..., rule, [w_scale,] grad_scale, clipvalue, stream
+    "sl_optimizer_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, POINTER(OptRule), c_void_p, c_float,
+                                  c_void_p]),
+    "sl_optimizer_pack_layers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamLayer), c_int, c_int,
+                                         POINTER(OptRule), c_void_p, c_float, c_void_p]),
+    "sl_split3_optimizer_pack_layers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamLayer), c_int,
+                                                POINTER(OptRule), c_void_p, c_float, c_void_p]),
+    "sl_splitf16_optimizer_pack_layers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamLayer), c_int,
+                                                  POINTER(OptRule), c_float, c_void_p, c_float, c_void_p]),
 }
 
 

@@ -174,9 +174,78 @@ __device__ __forceinline__ float clipped_grad(const float g, const float gs, con
     return s;
 }
 
+// The other Keras-2.0 rules (include/speechless_hip.h "Keras-2.0 optimizers beside Adam"), each ONE definition with the
+// contraction pinned like adam_element: the flat kernel (unfused step, sharded slices, ASG tables) and the fused update +
+// repack kernel must give the same bits.  lr is the decayed rate (Adamax: already divided by 1 - b1^t, on the host).
+__device__ __forceinline__ void sgd_element(float& p, const float g, float& m, const float lr, const float momentum,
+                                            const float nesterov) {
+#pragma clang fp contract(off)
+    const float lg = lr * g;
+    const float v = __builtin_fmaf(momentum, m, -lg);
+    m = v;
+    p = nesterov != 0.f ? p + __builtin_fmaf(momentum, v, -lg) : p + v;
+}
+
+__device__ __forceinline__ void rmsprop_element(float& p, const float g, float& a, const float lr, const float rho,
+                                                const float eps) {
+#pragma clang fp contract(off)
+    const float gg = (1.f - rho) * g * g;
+    a = __builtin_fmaf(rho, a, gg);
+    const float step = lr * g / (sqrtf(a) + eps);
+    p = p - step;
+}
+
+__device__ __forceinline__ void adagrad_element(float& p, const float g, float& a, const float lr, const float eps) {
+#pragma clang fp contract(off)
+    a = __builtin_fmaf(g, g, a);
+    const float step = lr * g / (sqrtf(a) + eps);
+    p = p - step;
+}
+
+__device__ __forceinline__ void adadelta_element(float& p, const float g, float& a, float& d, const float lr, const float rho,
+                                                 const float eps) {
+#pragma clang fp contract(off)
+    const float gg = (1.f - rho) * g * g;
+    a = __builtin_fmaf(rho, a, gg);
+    const float u = g * sqrtf(d + eps) / sqrtf(a + eps);
+    const float step = lr * u;
+    p = p - step;
+    const float uu = (1.f - rho) * u * u;
+    d = __builtin_fmaf(rho, d, uu);
+}
+
+// (comparisons, not fmaxf: a NaN gradient stays a NaN in u, as through Keras' maximum)
+__device__ __forceinline__ void adamax_element(float& p, const float g, float& m, float& u, const float lr_t, const float b1,
+                                               const float b2, const float eps) {
+#pragma clang fp contract(off)
+    const float gm = (1.f - b1) * g;
+    m = __builtin_fmaf(b1, m, gm);
+    const float bu = b2 * u, ag = fabsf(g);
+    u = bu > ag ? bu : ag;
+    const float step = lr_t * m / (u + eps);
+    p = p - step;
+}
+
+// RULE: an SL_OPT_* id.  Every update kernel below is an instantiation over it; the four coefficients travel as
+// (lr, c0, c1, eps) -- Adam: lr_t, b1, b2; SGD: lr, momentum, nesterov (0 / 1); RMSprop, Adadelta: lr, rho; Adagrad: lr;
+// Adamax: lr_t, b1, b2.  A rule with one state slot never touches s1 (the kernels get NULL for it).
+__host__ __device__ constexpr bool opt_two_slots(int rule) {
+    return rule == SL_OPT_ADAM || rule == SL_OPT_ADADELTA || rule == SL_OPT_ADAMAX;
+}
+template <int RULE>
+__device__ __forceinline__ void opt_element(float& p, const float g, float& s0, float& s1, const float lr, const float c0,
+                                            const float c1, const float eps) {
+    if (RULE == SL_OPT_ADAM) adam_element(p, g, s0, s1, lr, c0, c1, eps);
+    if (RULE == SL_OPT_SGD) sgd_element(p, g, s0, lr, c0, c1);
+    if (RULE == SL_OPT_RMSPROP) rmsprop_element(p, g, s0, lr, c0, eps);
+    if (RULE == SL_OPT_ADAGRAD) adagrad_element(p, g, s0, lr, eps);
+    if (RULE == SL_OPT_ADADELTA) adadelta_element(p, g, s0, s1, lr, c0, eps);
+    if (RULE == SL_OPT_ADAMAX) adamax_element(p, g, s0, s1, lr, c0, c1, eps);
+}
+
 // CLIP: the gradient goes through clipped_grad first (*gscale read once per thread: NULL = 1); CLIP = false is the kernel
 // as it was -- the twins with no clipping asked for launch that instantiation
-template <bool CLIP = false>
+template <bool CLIP = false, int RULE = SL_OPT_ADAM>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long n4, float lr_t, float b1, float b2, float eps,
                             const float* __restrict__ gscale = nullptr, float cv = 0.f) {
@@ -188,17 +257,18 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
 #pragma unroll
         for (int j = 0; j < 4; ++j) gv[j] = clipped_grad(gv[j], gs, cv);
     }
+    constexpr bool TWO = opt_two_slots(RULE);
     f32x4 mv = ((f32x4*)m)[i];
-    f32x4 vv = ((f32x4*)v)[i];
+    f32x4 vv = TWO ? ((f32x4*)v)[i] : (f32x4){0.f, 0.f, 0.f, 0.f};
     f32x4 pv = ((f32x4*)p)[i];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float pj = pv[j], mj = mv[j], vj = vv[j];
-        adam_element(pj, gv[j], mj, vj, lr_t, b1, b2, eps);
+        opt_element<RULE>(pj, gv[j], mj, vj, lr_t, b1, b2, eps);
         pv[j] = pj, mv[j] = mj, vv[j] = vj;
     }
     ((f32x4*)m)[i] = mv;
-    ((f32x4*)v)[i] = vv;
+    if (TWO) ((f32x4*)v)[i] = vv;
     ((f32x4*)p)[i] = pv;
 }
 
@@ -223,7 +293,7 @@ __device__ __forceinline__ u32x2 pack_lo4(float a0, float a1, float a2, float a3
     auto lo = [](float v) { return v - bf16_bits_to_f32(f32_to_bf16_bits(v)); };
     return (u32x2){pack_bf16x2(lo(a0), lo(a1)), pack_bf16x2(lo(a2), lo(a3))};
 }
-template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0, bool CLIP = false>
+template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0, bool CLIP = false, int RULE = SL_OPT_ADAM>
 __device__ __forceinline__ void adam_pack_block(float (&tile)[32][65], float* __restrict__ p, const float* __restrict__ g,
                                                 float* __restrict__ m, float* __restrict__ v, T* __restrict__ wf,
                                                 T* __restrict__ wd, int k, int cin, int cout, float lr_t, float b1,
@@ -232,18 +302,19 @@ __device__ __forceinline__ void adam_pack_block(float (&tile)[32][65], float* __
     const int tap = bz;
     const int co0 = bx * 64;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    constexpr bool TWO = opt_two_slots(RULE);  // (a one-slot rule: v is NULL, neither read nor written)
     auto adam4 = [&](long idx) {
         if (!ADAM) return *(const f32x4*)(p + idx);  // pack only: the masters are already up to date
         const f32x4 gv = *(const f32x4*)(g + idx);
-        f32x4 mv = *(f32x4*)(m + idx), vv = *(f32x4*)(v + idx), pv = *(f32x4*)(p + idx);
+        f32x4 mv = *(f32x4*)(m + idx), vv = TWO ? *(f32x4*)(v + idx) : (f32x4){0.f, 0.f, 0.f, 0.f}, pv = *(f32x4*)(p + idx);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float pj = pv[j], mj = mv[j], vj = vv[j];
-            adam_element(pj, CLIP ? clipped_grad(gv[j], gs, cv) : gv[j], mj, vj, lr_t, b1, b2, eps);
+            opt_element<RULE>(pj, CLIP ? clipped_grad(gv[j], gs, cv) : gv[j], mj, vj, lr_t, b1, b2, eps);
             pv[j] = pj, mv[j] = mj, vv[j] = vj;
         }
         *(f32x4*)(m + idx) = mv;
-        *(f32x4*)(v + idx) = vv;
+        if (TWO) *(f32x4*)(v + idx) = vv;
         *(f32x4*)(p + idx) = pv;
         return pv;
     };
@@ -315,7 +386,7 @@ struct AdamTable {
     int k[SL_ADAM_MAX_LAYERS], cin[SL_ADAM_MAX_LAYERS], cout[SL_ADAM_MAX_LAYERS];
 };
 
-template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0, bool CLIP = false>
+template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0, bool CLIP = false, int RULE = SL_OPT_ADAM>
 __global__ __launch_bounds__(256) void adam_pack_multi_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                               float* __restrict__ m, float* __restrict__ v, AdamTable t,
                                                               float lr_t, float b1, float b2, float eps, float wscale = 1.f,
@@ -330,9 +401,10 @@ __global__ __launch_bounds__(256) void adam_pack_multi_kernel(float* __restrict_
     const long off = t.offset[layer];
     if (!ADAM && bz == k) return;  // (the bias block has no operand copy)
     const float gs = (CLIP && gscale) ? *gscale : 1.f;
-    adam_pack_block<T, ADAM, PLANES, FMT, CLIP>(tile, p + off, ADAM ? g + off : nullptr, ADAM ? m + off : nullptr,
-                                                ADAM ? v + off : nullptr, (T*)t.wf[layer], (T*)t.wd[layer], k, cin, cout, lr_t,
-                                                b1, b2, eps, bx, by, bz, wscale, gs, cv);
+    adam_pack_block<T, ADAM, PLANES, FMT, CLIP, RULE>(tile, p + off, ADAM ? g + off : nullptr, ADAM ? m + off : nullptr,
+                                                      (ADAM && opt_two_slots(RULE)) ? v + off : nullptr, (T*)t.wf[layer],
+                                                      (T*)t.wd[layer], k, cin, cout, lr_t, b1, b2, eps, bx, by, bz, wscale, gs,
+                                                      cv);
 }
 
 }  // namespace
@@ -755,6 +827,120 @@ extern "C" int sl_adam_step(float* param, const float* grad, float* m, float* v,
                             float beta1, float beta2, float eps, void* stream) {
     return sl_adam_step_clipped(param, grad, m, v, n, step, lr, beta1, beta2, eps, nullptr, 0.f, stream);
 }
+
+// ---- the Keras-2.0 rules beside Adam: one flat and three fused entry points over sl_opt_rule -------------------------------
+namespace {
+struct OptCoeffs {
+    float lr, c0, c1, eps;
+    bool two;
+};
+}  // namespace
+
+static int opt_coeffs_from(const sl_opt_rule* r, const char* who, OptCoeffs* c) {
+    SL_CHECK_ARG(r != nullptr, "%s: null rule", who);
+    c->lr = r->lr, c->eps = r->eps, c->c0 = 0.f, c->c1 = 0.f;
+    switch (r->rule) {
+        case SL_OPT_SGD: c->c0 = r->momentum, c->c1 = r->nesterov ? 1.f : 0.f; break;
+        case SL_OPT_RMSPROP:
+        case SL_OPT_ADADELTA: c->c0 = r->rho; break;
+        case SL_OPT_ADAGRAD: break;
+        case SL_OPT_ADAMAX: c->c0 = r->beta1, c->c1 = r->beta2; break;
+        case SL_OPT_ADAM: SL_CHECK_ARG(false, "%s: Adam has its own entry points (sl_adam_*: they take the step count)", who);
+        default: SL_CHECK_ARG(false, "%s: unknown rule %d", who, r->rule);
+    }
+    c->two = opt_two_slots(r->rule);
+    return SL_OK;
+}
+
+// one switch over the rule ids for every launch of this family: KERNEL is a template over (CLIP, RULE) in that order at its end
+#define SL_OPT_LAUNCH_RULE(RULE, clip, LAUNCH)  \
+    case RULE:                                  \
+        if (clip) { LAUNCH(true, RULE); } else { LAUNCH(false, RULE); } \
+        break;
+#define SL_OPT_DISPATCH(rule, clip, LAUNCH)           \
+    switch (rule) {                                   \
+        SL_OPT_LAUNCH_RULE(SL_OPT_SGD, clip, LAUNCH)      \
+        SL_OPT_LAUNCH_RULE(SL_OPT_RMSPROP, clip, LAUNCH)  \
+        SL_OPT_LAUNCH_RULE(SL_OPT_ADAGRAD, clip, LAUNCH)  \
+        SL_OPT_LAUNCH_RULE(SL_OPT_ADADELTA, clip, LAUNCH) \
+        SL_OPT_LAUNCH_RULE(SL_OPT_ADAMAX, clip, LAUNCH)   \
+        default: break;                               \
+    }
+
+extern "C" int sl_optimizer_step(float* param, const float* grad, float* s0, float* s1, size_t n, const sl_opt_rule* rule,
+                                 const float* grad_scale, float clipvalue, void* stream) {
+    const char* who = "sl_optimizer_step";
+    OptCoeffs c;
+    const int rc = opt_coeffs_from(rule, who, &c);
+    if (rc != SL_OK) return rc;
+    SL_CHECK_ARG(param && grad && s0, "%s: null pointer", who);
+    SL_CHECK_ARG((s1 != nullptr) == c.two, "%s: s1 is required exactly when the rule keeps two state slots", who);
+    SL_CHECK_ARG(n % 4 == 0, "%s: n must be a multiple of 4", who);
+    SL_CHECK_ARG(clipvalue >= 0.f, "%s: clipvalue must be >= 0 (0 = off)", who);
+    const long n4 = (long)(n / 4);
+    if (n4 == 0) return SL_OK;
+    const dim3 grid((unsigned)((n4 + 255) / 256));
+    const bool clip = grad_scale != nullptr || clipvalue > 0.f;
+#define SL_OPT_FLAT(CLIP, RULE)                                                                                            \
+    hipLaunchKernelGGL((adam_kernel<CLIP, RULE>), grid, dim3(256), 0, (hipStream_t)stream, param, grad, s0, s1, n4, c.lr, \
+                       c.c0, c.c1, c.eps, grad_scale, clipvalue)
+    SL_OPT_DISPATCH(rule->rule, clip, SL_OPT_FLAT)
+#undef SL_OPT_FLAT
+    return sl_check_launch(who);
+}
+
+// T / PLANES / FMT: the operand format, as in the Adam entry points above
+template <typename T, int PLANES, int FMT>
+static int optimizer_pack_layers_impl(const char* who, float* param, const float* grad, float* s0, float* s1,
+                                      const sl_adam_layer* layers, int n_layers, const sl_opt_rule* rule, float w_scale,
+                                      const float* grad_scale, float clipvalue, void* stream) {
+    OptCoeffs c;
+    int rc = opt_coeffs_from(rule, who, &c);
+    if (rc != SL_OK) return rc;
+    SL_CHECK_ARG(param && grad && s0 && layers && w_scale > 0.f, "%s: null pointer or bad scale", who);
+    SL_CHECK_ARG((s1 != nullptr) == c.two, "%s: s1 is required exactly when the rule keeps two state slots", who);
+    SL_CHECK_ARG(n_layers >= 1 && n_layers <= SL_ADAM_MAX_LAYERS, "%s: 1..%d layers per call", who, SL_ADAM_MAX_LAYERS);
+    SL_CHECK_ARG(clipvalue >= 0.f, "%s: clipvalue must be >= 0 (0 = off)", who);
+    AdamTable t;
+    int blocks = 0;
+    rc = adam_table_from(layers, n_layers, who, &t, &blocks);
+    if (rc != SL_OK) return rc;
+    const bool clip = grad_scale != nullptr || clipvalue > 0.f;
+#define SL_OPT_PACK(CLIP, RULE)                                                                                            \
+    hipLaunchKernelGGL((adam_pack_multi_kernel<T, true, PLANES, FMT, CLIP, RULE>), dim3(blocks), dim3(256), 0,             \
+                       (hipStream_t)stream, param, grad, s0, s1, t, c.lr, c.c0, c.c1, c.eps, w_scale, grad_scale, clipvalue)
+    SL_OPT_DISPATCH(rule->rule, clip, SL_OPT_PACK)
+#undef SL_OPT_PACK
+    return sl_check_launch(who);
+}
+
+extern "C" int sl_optimizer_pack_layers(float* param, const float* grad, float* s0, float* s1, const sl_adam_layer* layers,
+                                        int n_layers, int dtype, const sl_opt_rule* rule, const float* grad_scale,
+                                        float clipvalue, void* stream) {
+    const char* who = "sl_optimizer_pack_layers";
+    SL_CHECK_ARG(dtype == SL_BF16 || dtype == SL_F32, "%s: bad dtype", who);
+    if (dtype == SL_BF16)
+        return optimizer_pack_layers_impl<unsigned short, 1, 0>(who, param, grad, s0, s1, layers, n_layers, rule, 1.f,
+                                                                grad_scale, clipvalue, stream);
+    return optimizer_pack_layers_impl<float, 1, 0>(who, param, grad, s0, s1, layers, n_layers, rule, 1.f, grad_scale, clipvalue,
+                                                   stream);
+}
+
+extern "C" int sl_split3_optimizer_pack_layers(float* param, const float* grad, float* s0, float* s1,
+                                               const sl_adam_layer* layers, int n_layers, const sl_opt_rule* rule,
+                                               const float* grad_scale, float clipvalue, void* stream) {
+    return optimizer_pack_layers_impl<unsigned short, 3, 0>("sl_split3_optimizer_pack_layers", param, grad, s0, s1, layers,
+                                                            n_layers, rule, 1.f, grad_scale, clipvalue, stream);
+}
+
+extern "C" int sl_splitf16_optimizer_pack_layers(float* param, const float* grad, float* s0, float* s1,
+                                                 const sl_adam_layer* layers, int n_layers, const sl_opt_rule* rule,
+                                                 float w_scale, const float* grad_scale, float clipvalue, void* stream) {
+    return optimizer_pack_layers_impl<unsigned short, 3, 1>("sl_splitf16_optimizer_pack_layers", param, grad, s0, s1, layers,
+                                                            n_layers, rule, w_scale, grad_scale, clipvalue, stream);
+}
+#undef SL_OPT_DISPATCH
+#undef SL_OPT_LAUNCH_RULE
 
 // ---- squared gradient norm + clip factor (include/speechless_hip.h: "Gradient clipping on the device") ----------------------
 namespace {

@@ -38,7 +38,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
 
     def __init__(self, specs, grapheme_set_size, dtype="bf16", device="cuda:0", ctc_epsilon=1e-8,
                  frozen_layer_count=0, lr=1e-4, beta_1=0.9, beta_2=0.999, adam_epsilon=1e-8, forward_only=False,
-                 clipnorm=0.0, clipvalue=0.0, decay=0.0, track_grad_norm=False, criterion="ctc"):
+                 clipnorm=0.0, clipvalue=0.0, decay=0.0, track_grad_norm=False, criterion="ctc", optimizer="adam",
+                 momentum=0.0, nesterov=False, rho=None):
         if criterion not in ("ctc", "asg"):
             raise ValueError("criterion must be 'ctc' or 'asg', not {!r}".format(criterion))
         if criterion == "asg" and (clipnorm or clipvalue or track_grad_norm):
@@ -94,6 +95,17 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.frozen_layer_count = frozen_layer_count
         self.lr, self.beta_1, self.beta_2, self.adam_epsilon = lr, beta_1, beta_2, adam_epsilon
         self.adam_iterations = 0
+        # The update rule (Keras 2.0.x optimizers.py; include/speechless_hip.h "Keras-2.0 optimizers beside Adam"): "adam" (the
+        # default: the sl_adam_* entry points with the arguments they always had), "sgd" (momentum, nesterov), "rmsprop" (rho),
+        # "adagrad", "adadelta" (rho) or "adamax" (beta_1, beta_2).  `adam_epsilon` is every rule's epsilon.  The state buffers
+        # keep their names: adam_m is the first slot of whatever rule runs, adam_v the second -- None for a one-slot rule,
+        # which then moves 3 reads + 2 writes per parameter instead of 4 + 3.
+        if optimizer not in _lib.OPT_RULES:
+            raise ValueError("optimizer must be one of {}, not {!r}".format(", ".join(sorted(_lib.OPT_RULES)), optimizer))
+        self.optimizer = optimizer
+        self.opt_slots = _lib.OPT_SLOTS[optimizer]
+        self.momentum, self.nesterov = float(momentum or 0.0), bool(nesterov)
+        self.rho = float(rho) if rho is not None else (0.95 if optimizer == "adadelta" else 0.9)  # (Keras' defaults)
         # What every Keras 2.0 optimizer takes besides its own hyper-parameters (optimizers.py: Optimizer.get_gradients, the
         # `decay` of Adam.get_updates; include/speechless_hip.h "Gradient clipping on the device").  0 = off, and with all
         # three off the step launches exactly what it launched before they existed.
@@ -167,7 +179,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         if not self.forward_only:
             self.grads = torch.zeros((off,), dtype=torch.float32, device=dev)
             self.adam_m = torch.zeros((off,), dtype=torch.float32, device=dev)
-            self.adam_v = torch.zeros((off,), dtype=torch.float32, device=dev)
+            if self.opt_slots == 2:
+                self.adam_v = torch.zeros((off,), dtype=torch.float32, device=dev)
         # ASG criterion (csrc/asg.hip; DESIGN.md "ASG criterion"): the K x K transition scores g[from][to] and the K start
         # scores g0 are trainable parameters beside the conv stack's, in ONE flat fp32 buffer [g | g0] with a gradient and
         # Adam moments of the same shape -- one sl_adam_step launch updates both tables.  Zero = the paper's initialisation.
@@ -181,6 +194,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             if not self.forward_only:
                 self.asg_grads, self.asg_adam_m, self.asg_adam_v = (
                     torch.zeros((n_asg,), dtype=torch.float32, device=dev) for _ in range(3))
+                if self.opt_slots == 1:
+                    self.asg_adam_v = None
         self._weights_set_count = 0
         pl = self.planes  # bf16x3: packed weight rows are [w_hi | w_hi | w_lo]
         self.w_fwd = [torch.zeros((p.cout_pad, p.spec.kernel_size, p.cin_pad * pl), dtype=self.torch_dtype, device=dev)
@@ -545,16 +560,27 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         own slice of each bucket only: they are all-gathered here first, bucket by bucket with the slices of gather_bucket --
         a COLLECTIVE call in that case (every rank must make it; Wav2Letter.train does, each rank saves at the same epoch)."""
         reducer = self._sharded_reducer
+        slots = self._state_slots()
         if reducer is not None and (reducer.world_size > 1 or reducer.force):
-            for flat in (self.adam_m, self.adam_v):
+            for _, flat in slots:
                 for b in range(len(reducer.ranges)):
                     reducer.gather_bucket(b, flat)
             reducer.wait_all()
-        return {"m": self._unpad(self.adam_m), "v": self._unpad(self.adam_v), "iterations": int(self.adam_iterations),
-                "dropout_steps": int(self._dropout_steps)}
+        state = {name: self._unpad(flat) for name, flat in slots}
+        state.update(iterations=int(self.adam_iterations), dropout_steps=int(self._dropout_steps))
+        if self.optimizer != "adam":  # (an Adam state is the dictionary it always was; a state without the key is Adam)
+            state["optimizer"] = self.optimizer
+        return state
+
+    def _state_slots(self):
+        """the state buffers that exist, under the keys of the optimizer state: [("m", first slot)] or with ("v", second slot)"""
+        return [("m", self.adam_m), ("v", self.adam_v)][:self.opt_slots]
 
     def set_optimizer_state(self, state):
-        for name, flat in (("m", self.adam_m), ("v", self.adam_v)):
+        rule = str(state.get("optimizer", "adam"))
+        if rule != self.optimizer:
+            raise ValueError("the optimizer state is one of {!r}, this engine runs {!r}".format(rule, self.optimizer))
+        for name, flat in self._state_slots():
             self._write_padded(flat, state[name], "optimizer state of layer {} has shape {} / {}")
         self.adam_iterations = int(state["iterations"])
         self._dropout_steps = int(state.get("dropout_steps", 0))
@@ -869,7 +895,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
     def get_asg_state(self):
         """{'trans', 'init'} and, on a training engine, their Adam moments 'trans_m', 'trans_v', 'init_m', 'init_v' (numpy)"""
         out = {}
-        named = [("", self.asg_params)] + ([] if self.forward_only else [("_m", self.asg_adam_m), ("_v", self.asg_adam_v)])
+        named = [("", self.asg_params)] + ([] if self.forward_only else self._asg_state_slots())
         for suffix, flat in named:
             trans, init = self._asg_views(flat)
             out["trans" + suffix], out["init" + suffix] = trans.cpu().numpy().copy(), init.cpu().numpy().copy()
@@ -880,7 +906,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.set_asg_scores(state["trans"], state["init"])
         if self.forward_only:
             return
-        for suffix, flat in (("_m", self.asg_adam_m), ("_v", self.asg_adam_v)):
+        for suffix, flat in self._asg_state_slots():
             if "trans" + suffix in state:
                 k = self.grapheme_set_size
                 flat[:k * k + k].copy_(torch.from_numpy(np.concatenate([
@@ -888,6 +914,9 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                     np.asarray(state["init" + suffix], dtype=np.float32).ravel()])))
             else:
                 flat.zero_()
+
+    def _asg_state_slots(self):
+        return [("_m", self.asg_adam_m), ("_v", self.asg_adam_v)][:self.opt_slots]
 
     def _require_asg(self, what):
         if self.criterion != "asg":
@@ -964,7 +993,13 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
 
     def asg_adam_step(self):
         """Adam on the two ASG tables with the step's hyper-parameters and iteration count (adam_iterations already counts
-        this step): one sl_adam_step launch over [g | g0]."""
+        this step): one sl_adam_step launch over [g | g0].  Another rule: the same launch of its flat kernel."""
+        if self.optimizer != "adam":
+            self._launch("opt:{}:asg".format(self.optimizer), "sl_optimizer_step", self.asg_params.data_ptr(),
+                         self.asg_grads.data_ptr(), self.asg_adam_m.data_ptr(),
+                         self.asg_adam_v.data_ptr() if self.opt_slots == 2 else None, self.asg_params.numel(), self._opt_rule(),
+                         None, 0.0, self._stream())
+            return
         self._launch("adam:asg", "sl_adam_step", self.asg_params.data_ptr(), self.asg_grads.data_ptr(),
                      self.asg_adam_m.data_ptr(), self.asg_adam_v.data_ptr(), self.asg_params.numel(), self.adam_iterations,
                      self._lr_now(), self.beta_1, self.beta_2, self.adam_epsilon, self._stream())
@@ -1393,8 +1428,29 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             return None
         return (self._norm_out[1:].data_ptr() if self.clipnorm > 0 else None, self.clipvalue)
 
+    def _opt_rule(self):
+        """sl_opt_rule of the update being launched (a rule beside Adam; self.adam_iterations already counts it): the decayed
+        rate -- Adamax: divided by 1 - beta_1^t here, in double -- and the rule's coefficients"""
+        rule = _lib.OptRule()
+        rule.rule = _lib.OPT_RULES[self.optimizer]
+        lr = self._lr_now()
+        if self.optimizer == "adamax":
+            lr = lr / (1.0 - self.beta_1 ** self.adam_iterations)
+        rule.lr, rule.momentum, rule.nesterov, rule.rho = lr, self.momentum, int(self.nesterov), self.rho
+        rule.beta1, rule.beta2, rule.eps = self.beta_1, self.beta_2, self.adam_epsilon
+        return rule
+
     def _launch_adam_flat(self, tag, lo, hi, st):
-        """plain elementwise Adam on [lo, hi) of the flat buffers (the unfused step; a rank's slice under the sharded optimizer)"""
+        """plain elementwise update on [lo, hi) of the flat buffers (the unfused step; a rank's slice under the sharded
+        optimizer).  tag: 'adam' / 'adam_shard:<b>'; another rule launches as 'opt:<rule>' / 'opt_shard:<rule>:<b>'"""
+        if self.optimizer != "adam":
+            kind, _, rest = tag.partition(":")
+            tag = "{}:{}{}".format(kind.replace("adam", "opt"), self.optimizer, ":" + rest if rest else "")
+            clip = self._clip_args() or (None, 0.0)
+            self._launch(tag, "sl_optimizer_step", self.params[lo:hi].data_ptr(), self.grads[lo:hi].data_ptr(),
+                         self.adam_m[lo:hi].data_ptr(), self.adam_v[lo:hi].data_ptr() if self.opt_slots == 2 else None, hi - lo,
+                         self._opt_rule(), *clip, st)
+            return
         what = (self.params[lo:hi].data_ptr(), self.grads[lo:hi].data_ptr(), self.adam_m[lo:hi].data_ptr(),
                 self.adam_v[lo:hi].data_ptr(), hi - lo, self.adam_iterations, self._lr_now(), self.beta_1, self.beta_2,
                 self.adam_epsilon)
@@ -1503,6 +1559,9 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         for lo in range(0, len(layers), 16):
             chunk = layers[lo:lo + 16]
             table = self._adam_table(chunk)
+            if self.optimizer != "adam":
+                self._opt_layers(chunk, table, st)
+                continue
             tag = "adam:{}..{}".format(self.all_plans[chunk[0]].spec.name, self.all_plans[chunk[-1]].spec.name)
             what = (self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), table,
                     len(chunk))
@@ -1517,6 +1576,23 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                     self._pack_pair_dgrad_x3(st)
             else:
                 self._launch(tag, "sl_adam_pack_layers" + twin, *what, self.dtype_code, *how, *clip, st)
+
+    def _opt_layers(self, chunk, table, st):
+        """_adam_layers for a rule beside Adam: the same fused update + repack launch (sl_*optimizer_pack_layers), no second
+        state pointer for a one-slot rule"""
+        tag = "opt:{}:{}..{}".format(self.optimizer, self.all_plans[chunk[0]].spec.name, self.all_plans[chunk[-1]].spec.name)
+        what = (self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(),
+                self.adam_v.data_ptr() if self.opt_slots == 2 else None, table, len(chunk))
+        rule = self._opt_rule()
+        clip = self._clip_args() or (None, 0.0)  # (None, 0: the entry points launch the instantiation without clipping)
+        if self.planes == 3 and self.x3_f16:
+            self._launch(tag, "sl_splitf16_optimizer_pack_layers", *what, rule, self.w_scale, *clip, st)
+        elif self.planes == 3:
+            self._launch(tag, "sl_split3_optimizer_pack_layers", *what, rule, *clip, st)
+            if 0 in chunk and self.w_dgrad[0] is not None:
+                self._pack_pair_dgrad_x3(st)
+        else:
+            self._launch(tag, "sl_optimizer_pack_layers", *what, self.dtype_code, rule, *clip, st)
 
     def train_step(self, input_batch, label_batch, label_lengths, prediction_lengths, reducer=None):
         """One full optimisation step (forward, CTC, backward, [gradient all-reduce], Adam, weight repack).

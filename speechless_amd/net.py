@@ -47,12 +47,107 @@ class Adam:
         self.decay, self.clipnorm, self.clipvalue = decay, clipnorm, clipvalue
 
 
+class _KerasOptimizer:
+    """what the optimizer classes below share: Keras 2.0's keyword names, plus the `decay`, `clipnorm` and `clipvalue` of Adam"""
+
+    def __init__(self, lr, decay, clipnorm, clipvalue, **own):
+        self.lr, self.decay, self.clipnorm, self.clipvalue = lr, decay, clipnorm, clipvalue
+        for name, value in own.items():
+            setattr(self, name, value)
+
+
+class SGD(_KerasOptimizer):
+    """keras.optimizers.SGD (2.0.x): v = momentum * m - lr * g; p += v (nesterov: p += momentum * v - lr * g)"""
+
+    def __init__(self, lr=0.01, momentum=0.0, decay=0.0, nesterov=False, clipnorm=0.0, clipvalue=0.0):
+        super().__init__(lr, decay, clipnorm, clipvalue, momentum=momentum, nesterov=nesterov)
+
+
+class RMSprop(_KerasOptimizer):
+    """keras.optimizers.RMSprop (2.0.x): a = rho * a + (1 - rho) * g^2; p -= lr * g / (sqrt(a) + epsilon)"""
+
+    def __init__(self, lr=0.001, rho=0.9, epsilon=1e-8, decay=0.0, clipnorm=0.0, clipvalue=0.0):
+        super().__init__(lr, decay, clipnorm, clipvalue, rho=rho, epsilon=epsilon)
+
+
+class Adagrad(_KerasOptimizer):
+    """keras.optimizers.Adagrad (2.0.x): a += g^2; p -= lr * g / (sqrt(a) + epsilon)"""
+
+    def __init__(self, lr=0.01, epsilon=1e-8, decay=0.0, clipnorm=0.0, clipvalue=0.0):
+        super().__init__(lr, decay, clipnorm, clipvalue, epsilon=epsilon)
+
+
+class Adadelta(_KerasOptimizer):
+    """keras.optimizers.Adadelta (2.0.x): a = rho * a + (1 - rho) * g^2; u = g * sqrt(d + epsilon) / sqrt(a + epsilon);
+    p -= lr * u; d = rho * d + (1 - rho) * u^2"""
+
+    def __init__(self, lr=1.0, rho=0.95, epsilon=1e-8, decay=0.0, clipnorm=0.0, clipvalue=0.0):
+        super().__init__(lr, decay, clipnorm, clipvalue, rho=rho, epsilon=epsilon)
+
+
+class Adamax(_KerasOptimizer):
+    """keras.optimizers.Adamax (2.0.x): m = beta_1 * m + (1 - beta_1) * g; u = max(beta_2 * u, |g|);
+    p -= lr / (1 - beta_1^t) * m / (u + epsilon)"""
+
+    def __init__(self, lr=0.002, beta_1=0.9, beta_2=0.999, epsilon=1e-8, decay=0.0, clipnorm=0.0, clipvalue=0.0):
+        super().__init__(lr, decay, clipnorm, clipvalue, beta_1=beta_1, beta_2=beta_2, epsilon=epsilon)
+
+
+# class name -> (Engine `optimizer`, {Engine keyword: attribute read off the object}); only these attributes are read
+_OPTIMIZER_RULES = {
+    "SGD": ("sgd", {"momentum": "momentum", "nesterov": "nesterov"}),
+    "RMSprop": ("rmsprop", {"rho": "rho", "adam_epsilon": "epsilon"}),
+    "Adagrad": ("adagrad", {"adam_epsilon": "epsilon"}),
+    "Adadelta": ("adadelta", {"rho": "rho", "adam_epsilon": "epsilon"}),
+    "Adamax": ("adamax", {"beta_1": "beta_1", "beta_2": "beta_2", "adam_epsilon": "epsilon"}),
+}
+
+
 def optimizer_settings(optimizer):
-    """The Engine keyword arguments an optimizer object stands for: lr, beta_1, beta_2, epsilon as they always were read,
+    """The Engine keyword arguments an optimizer object stands for.  The rule is picked by the NAME of the object's class
+    (a real Keras SGD / RMSprop / Adagrad / Adadelta / Adamax works like the classes above) and only that rule's attributes
+    are read; any other class but Nadam is read as Adam always was: lr, beta_1, beta_2, epsilon,
     and decay / clipnorm / clipvalue where the object has them (a Keras optimizer carries clipnorm / clipvalue only when
     they were given: absent = 0 = off)."""
     extra = {name: float(getattr(optimizer, name, 0.0) or 0.0) for name in ("decay", "clipnorm", "clipvalue")}
+    name = type(optimizer).__name__
+    if name in _OPTIMIZER_RULES:
+        rule, attributes = _OPTIMIZER_RULES[name]
+        own = {keyword: getattr(optimizer, attribute) for keyword, attribute in attributes.items()}
+        return dict(optimizer=rule, lr=optimizer.lr, **own, **extra)
+    supported = "Adam, " + ", ".join(_OPTIMIZER_RULES)
+    if name == "Nadam":
+        raise ValueError("Nadam is not supported (its momentum schedule is host state of another kind); the optimizers are "
+                         + supported)
+    if not all(hasattr(optimizer, a) for a in ("lr", "beta_1", "beta_2", "epsilon")):
+        raise ValueError("unknown optimizer class {!r}: the supported optimizers are {}".format(name, supported))
     return dict(lr=optimizer.lr, beta_1=optimizer.beta_1, beta_2=optimizer.beta_2, adam_epsilon=optimizer.epsilon, **extra)
+
+
+def optimizer_state_to_arrays(state, layer_names):
+    """Engine.get_optimizer_state() as the flat {name: array} dictionary of a weights-epoch{N}.opt.npz file: the rule's name
+    (left out for Adam: its files are what they always were) and, per layer, the slots the rule has ('m', and 'v' for a
+    two-slot rule)"""
+    arrays = {"iterations": np.int64(state["iterations"]), "dropout_steps": np.int64(state["dropout_steps"])}
+    if state.get("optimizer", "adam") != "adam":
+        arrays["optimizer"] = np.array(state["optimizer"])
+    for slot in ("m", "v"):
+        if slot in state:
+            for name, (w, b) in zip(layer_names, state[slot]):
+                arrays["{}/kernel/{}".format(name, slot)], arrays["{}/bias/{}".format(name, slot)] = w, b
+    return arrays
+
+
+def optimizer_state_from_arrays(data, layer_names):
+    """the reverse (data: an opened .npz or a dictionary); a file without the rule's name is an Adam state"""
+    rule = str(data["optimizer"]) if "optimizer" in data else "adam"
+    state = {"iterations": int(data["iterations"]), "dropout_steps": int(data["dropout_steps"])}
+    if rule != "adam":
+        state["optimizer"] = rule
+    for slot in ("m", "v"):
+        if "{}/kernel/{}".format(layer_names[0], slot) in data:
+            state[slot] = [(data["{}/kernel/{}".format(n, slot)], data["{}/bias/{}".format(n, slot)]) for n in layer_names]
+    return state
 
 
 class LabeledSpectrogram:
@@ -409,22 +504,14 @@ class Wav2Letter:
     def save_optimizer_state(self, net_directory, epoch):
         """Extension: the reference saves the weights only (net.py:564-572), so a resumed run
         restarts Adam's moments and bias correction.  This writes them next to the weights file of the same epoch."""
-        state = self.engine.get_optimizer_state()
-        arrays = {"iterations": np.int64(state["iterations"]), "dropout_steps": np.int64(state["dropout_steps"])}
-        for layer, (mw, mb), (vw, vb) in zip(self.predictive_net.layers, state["m"], state["v"]):
-            arrays[layer.name + "/kernel/m"], arrays[layer.name + "/bias/m"] = mw, mb
-            arrays[layer.name + "/kernel/v"], arrays[layer.name + "/bias/v"] = vw, vb
+        arrays = optimizer_state_to_arrays(self.engine.get_optimizer_state(), [l.name for l in self.predictive_net.layers])
         Path(net_directory).mkdir(parents=True, exist_ok=True)
         np.savez(str(Path(net_directory) / self.optimizer_state_file_name(epoch)), **arrays)
 
     def load_optimizer_state(self, net_directory, epoch):
         self._load_asg_state(net_directory, epoch, with_moments=True)
         data = np.load(str(Path(net_directory) / self.optimizer_state_file_name(epoch)))
-        names = [layer.name for layer in self.predictive_net.layers]
-        self.engine.set_optimizer_state({
-            "m": [(data[n + "/kernel/m"], data[n + "/bias/m"]) for n in names],
-            "v": [(data[n + "/kernel/v"], data[n + "/bias/v"]) for n in names],
-            "iterations": int(data["iterations"]), "dropout_steps": int(data["dropout_steps"])})
+        self.engine.set_optimizer_state(optimizer_state_from_arrays(data, [l.name for l in self.predictive_net.layers]))
 
     @staticmethod
     def indices_to_load_by_target_index(allowed_characters_for_loaded_model, allowed_characters):
