@@ -381,6 +381,30 @@ size_t sl_asg_viterbi_workspace_bytes(int batch, int t_out, int k);
 int sl_asg_viterbi(const float* logq, const float* trans, const float* init, const int32_t* input_len, int32_t* path,
                    float* score, int batch, int t_out, int k, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ASG forced alignment: the best segmentation of a label over the frames (Viterbi over the label's own states; the ASG
+ *      counterpart of sl_ctc_align -- no blank, transition and start scores, the run-length-encoded label).
+ * logq: float[B][t_out][k], the emissions e_t(j) used AS THEY ARE (as sl_asg_viterbi).  trans[i*k + j] = g(i, j), init[j] =
+ * g0(j).  labels, label_len, input_len: as for sl_asg_loss_grad (L = label_len clamped to [0, l_max], T_b = input_len clamped
+ * to [0, t_out], label values clamped to [0, k)); adjacent equal labels need no special rule.  fp32, states s in [0, L),
+ * state s = letter l_s:
+ *   delta_0(0) = g0(l_0) + e_0(l_0);   delta_0(s > 0) = -inf
+ *   stay = delta_{t-1}(s) + g(l_s, l_s);   move = delta_{t-1}(s-1) + g(l_{s-1}, l_s)  (s >= 1)
+ *   delta_t(s) = (move > stay ? move : stay) + e_t(l_s)   for 0 < t < T_b   (a tie keeps stay)
+ * Every operation is an exact max or ONE fp32 add in the order written (no multiply, nothing to contract or reassociate), so
+ * a float32 restatement reproduces path and score bit for bit.  -inf entries of trans / init are legal and propagate as -inf;
+ * finite-or--inf inputs never give a NaN.
+ * End state: L-1 at frame T_b-1.  score[b] = delta_{T_b-1}(L-1); path int32[B][t_out]: path[b][t] = the state occupied at
+ * frame t for t < T_b (found by backtracking the recorded decisions), -1 for t >= T_b.  An utterance with L = 0, T_b = 0,
+ * L > T_b or a score of -inf is infeasible: score -inf and the whole row -1 (where sl_asg_loss_grad gives +inf).
+ * Limits: 2 <= k <= 64, 1 <= l_max <= 511, SL_ERR_UNSUPPORTED otherwise (nothing is written).
+ * workspace: sl_asg_align_workspace_bytes(batch, t_out, l_max) bytes, 0 when the backpointers (ONE bit per state and frame)
+ * fit the work-group's LDS -- otherwise they go to HBM (monotonic in t_out and l_max).  One wave per utterance; all work on
+ * the caller's stream, no allocation, no synchronisation. */
+size_t sl_asg_align_workspace_bytes(int batch, int t_out, int l_max);
+int sl_asg_align(const float* logq, const float* trans, const float* init, const int32_t* labels, const int32_t* label_len,
+                 const int32_t* input_len, int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
 /* ---- CTC beam search, optionally scored by an n-gram language model: the device twin of sl_host_ctc_beam_search
  *      (include/speechless_host.h; speechless/net.py:444-451).  The host decoder is the specification: for the same
  *      inputs the result is the same search, step for step --

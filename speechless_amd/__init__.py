@@ -11,7 +11,7 @@ def __getattr__(name):
                 "ExpectationsVsPredictionsInBatches", "ExpectationsVsPredictionsInGroupedBatches"):
         from . import net
         return getattr(net, name)
-    if name in ("PositionalLabel", "CtcAlignment"):
+    if name in ("PositionalLabel", "CtcAlignment", "AsgAlignment"):
         from . import alignment
         return getattr(alignment, name)
     if name == "Engine":

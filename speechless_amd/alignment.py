@@ -1,8 +1,10 @@
-"""Result types of CTC forced alignment (Wav2Letter.alignment_batch / positional_label_batch).
+"""Result types of forced alignment (Wav2Letter.alignment_batch / positional_label_batch under CTC, asg_alignment_batch /
+asg_positional_label_batch under ASG).
 
 `PositionalLabel` is the reference's word-timing label (speechless/labeled_example.py:32-60): `(word, (start, end))`
 sections, which LabeledExampleFromFile.sections() (:219-234) uses to cut long recordings.  `CtcAlignment` is one
-utterance's Viterbi alignment (include/speechless_hip.h, sl_ctc_align) turned into character and word frame ranges."""
+utterance's Viterbi alignment (include/speechless_hip.h, sl_ctc_align) turned into character and word frame ranges;
+`AsgAlignment` is the same for the ASG criterion (sl_asg_align), whose path runs over the run-length-encoded label."""
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -41,7 +43,36 @@ class PositionalLabel:
         return PositionalLabel(sections)
 
 
-class CtcAlignment:
+def _word_frames(label: str, character_frames) -> List[Tuple[str, Tuple[int, int]]]:
+    """(word, (first, end)) per space-separated word of `label`: from its first character's first frame to its last one's end"""
+    words = []
+    i = 0
+    while i < len(label):
+        if label[i] == " ":
+            i += 1
+            continue
+        j = i
+        while j < len(label) and label[j] != " ":
+            j += 1
+        words.append((label[i:j], (character_frames[i][0], character_frames[j - 1][1])))
+        i = j
+    return words
+
+
+class _WordTimings:
+    """what an alignment with `word_frames` offers on top of them"""
+    word_frames = []  # type: List[Tuple[str, Tuple[int, int]]]
+
+    def positional_label(self, seconds_per_frame: float) -> Optional[PositionalLabel]:
+        """The word ranges in seconds (output frame t covers [t, t + 1) * seconds_per_frame), or None when the
+        utterance is infeasible or has no words."""
+        if not self.word_frames:
+            return None
+        return PositionalLabel([(word, (first * seconds_per_frame, end * seconds_per_frame))
+                                for word, (first, end) in self.word_frames])
+
+
+class CtcAlignment(_WordTimings):
     """The best CTC path of one utterance through its label.
 
     frame_label_positions: int32 (T',), -1 where the path is on a blank (and past the utterance's frames), otherwise the
@@ -64,26 +95,7 @@ class CtcAlignment:
                     raise ValueError("alignment path skips character {} of {!r}".format(i, label))
                 self.character_frames.append((int(frames[0]), int(frames[-1]) + 1))
         # (word, (first, end)) per space-separated word: from its first character's first frame to its last one's end
-        self.word_frames = []  # type: List[Tuple[str, Tuple[int, int]]]
-        if self.feasible:
-            i = 0
-            while i < len(label):
-                if label[i] == " ":
-                    i += 1
-                    continue
-                j = i
-                while j < len(label) and label[j] != " ":
-                    j += 1
-                self.word_frames.append((label[i:j], (self.character_frames[i][0], self.character_frames[j - 1][1])))
-                i = j
-
-    def positional_label(self, seconds_per_frame: float) -> Optional[PositionalLabel]:
-        """The word ranges in seconds (output frame t covers [t, t + 1) * seconds_per_frame), or None when the
-        utterance is infeasible or has no words."""
-        if not self.word_frames:
-            return None
-        return PositionalLabel([(word, (first * seconds_per_frame, end * seconds_per_frame))
-                                for word, (first, end) in self.word_frames])
+        self.word_frames = _word_frames(label, self.character_frames) if self.feasible else []
 
     @staticmethod
     def from_path(label: str, log_probability: float, path) -> "CtcAlignment":
@@ -94,3 +106,69 @@ class CtcAlignment:
 
     def __repr__(self):
         return "CtcAlignment({!r}, log_probability={}, words={})".format(self.label, self.log_probability, self.word_frames)
+
+
+def _characters_per_grapheme(label: str) -> List[Tuple[int, bool]]:
+    """(characters, is a repeat mark) per grapheme of the ASG encoding of `label`: a letter stands for 1 character; a run of
+    two / three equal letters is written as the letter and a repeat mark that stands for 1 / 2 characters.
+    (AsgGraphemeEncoding.encode refuses longer runs.)"""
+    counts = []
+    i = 0
+    while i < len(label):
+        j = i
+        while j < len(label) and label[j] == label[i]:
+            j += 1
+        if j - i > 3:
+            raise ValueError("{}-fold repetition found, ASG only supports up to 3-fold.".format(j - i))
+        counts.extend([[(1, False)], [(1, False), (1, True)], [(1, False), (2, True)]][j - i - 1])
+        i = j
+    return counts
+
+
+class AsgAlignment(_WordTimings):
+    """The best ASG path of one utterance through its encoded label (no blank: every frame lies on a grapheme).
+
+    encoded_label: the label as AsgGraphemeEncoding.encode writes it (a run of two / three equal letters is the letter and
+    a repeat mark).  frame_grapheme_positions: int32 (T',), the index into `encoded_label` of the grapheme the frame is
+    aligned to, -1 past the utterance's frames.  log_probability: the path's score, -inf when the frames cannot hold the
+    label or -inf scores close every path (then every position is -1 and there are no ranges)."""
+
+    def __init__(self, label: str, encoded_label, log_probability: float, frame_grapheme_positions):
+        self.label = label
+        self.encoded_label = [int(g) for g in encoded_label]
+        self.log_probability = float(log_probability)
+        self.frame_grapheme_positions = np.asarray(frame_grapheme_positions, dtype=np.int32)
+        self.feasible = self.log_probability != -np.inf
+        counts = _characters_per_grapheme(label)
+        if len(counts) != len(self.encoded_label):
+            raise ValueError("{!r} is written with {} graphemes, not {}".format(label, len(counts), len(self.encoded_label)))
+        # (first, end) half-open output-frame range per encoded grapheme: contiguous, non-empty, covering [0, T_b)
+        self.grapheme_frames = []  # type: List[Tuple[int, int]]
+        # the same per character of `label`: a letter takes its grapheme's range; of a run written as letter + mark the
+        # first character takes the letter's range and the one or two others take the mark's
+        self.character_frames = []  # type: List[Tuple[int, int]]
+        if self.feasible:
+            positions = self.frame_grapheme_positions
+            end = 0
+            for i, (count, _) in enumerate(counts):
+                frames = np.flatnonzero(positions == i)
+                if frames.size == 0 or frames[0] != end or frames[-1] + 1 - frames[0] != frames.size:
+                    raise ValueError("alignment path does not pass grapheme {} of {!r} in one run behind grapheme {}".format(
+                        i, label, i - 1))
+                end = int(frames[-1]) + 1
+                self.grapheme_frames.append((int(frames[0]), end))
+                self.character_frames.extend([self.grapheme_frames[-1]] * count)
+        self.word_frames = _word_frames(label, self.character_frames) if self.feasible else []
+
+    @staticmethod
+    def from_path(label: str, encoded_label, twice_index: int, thrice_index: int, score: float, path) -> "AsgAlignment":
+        """From sl_asg_align's output row: the state = position in the encoded label per frame, -1 = none.  twice_index /
+        thrice_index: the encoding's repeat marks, checked against where the label's runs put them."""
+        if any(is_mark and int(g) != (twice_index if count == 1 else thrice_index)
+               for g, (count, is_mark) in zip(encoded_label, _characters_per_grapheme(label))):
+            raise ValueError("encoded label of {!r} does not hold its repeat marks ({}, {}) where its runs are".format(
+                label, twice_index, thrice_index))
+        return AsgAlignment(label, encoded_label, score, np.asarray(path, dtype=np.int32))
+
+    def __repr__(self):
+        return "AsgAlignment({!r}, log_probability={}, words={})".format(self.label, self.log_probability, self.word_frames)

@@ -367,16 +367,16 @@ class _Buffers:
         if self.labels is None or self.labels.shape[1] < l_max:
             self.labels = torch.zeros((self.batch, l_max), dtype=torch.int32, device=eng.device)
 
-    def ensure_align(self, eng, l_max):
-        """Tensors of Engine.ctc_align, apart from those of the CTC loss (a forward-only engine aligns without gradient
-        buffers): labels of up to l_max graphemes, lengths, the (B, tt_pad) path / (B,) score results and the workspace,
-        allocated on first use and grown with l_max only."""
+    def ensure_align(self, eng, l_max, workspace_query="sl_ctc_align_workspace_bytes"):
+        """Tensors of Engine.ctc_align / asg_align (an engine has one criterion, so one of the two), apart from those of the
+        loss (a forward-only engine aligns without gradient buffers): labels of up to l_max graphemes, lengths, the
+        (B, tt_pad) path / (B,) score results and the workspace, allocated on first use and grown with l_max only."""
         if self.align_labels is None or self.align_labels.shape[1] < l_max:
             self.align_labels = torch.zeros((self.batch, l_max), dtype=torch.int32, device=eng.device)
             self.align_label_len = torch.zeros((self.batch,), dtype=torch.int32, device=eng.device)
             self._align_path_flat = torch.zeros((self.batch * self.tt_pad,), dtype=torch.int32, device=eng.device)
             self.align_score = torch.zeros((self.batch,), dtype=torch.float32, device=eng.device)
-        need = lib().raw("sl_ctc_align_workspace_bytes")(self.batch, self.tt_pad, l_max)  # covers every length
+        need = lib().raw(workspace_query)(self.batch, self.tt_pad, l_max)  # covers every length
         if self.align_ws is None or self.align_ws.numel() < need:
             self.align_ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=eng.device)
 

@@ -27,7 +27,7 @@
 // and frame, in LDS when T' * K bytes fit, else in the workspace.
 #include <math.h>
 
-#include "common.h"
+#include "lattice.h"
 
 namespace {
 
@@ -74,16 +74,6 @@ __device__ __forceinline__ double lse2(double x, double y) {
     const double m = fmax(x, y);
     if (m == -INFINITY) return m;
     return m + log1p(exp(fmin(x, y) - m));
-}
-
-__device__ __forceinline__ int clamp_label(int c, int k) { return c < 0 ? 0 : (c >= k ? k - 1 : c); }
-
-__device__ __forceinline__ void clamp_lengths(const int32_t* label_len, const int32_t* input_len, int b, int l_max, int t_out,
-                                              int& L, int& T) {
-    L = label_len[b];
-    L = L < 0 ? 0 : (L > l_max ? l_max : L);
-    T = input_len[b];
-    T = T < 0 ? 0 : (T > t_out ? t_out : T);
 }
 
 // ---------------------------------------------------------------------------------------------- numerator lattices

@@ -12,22 +12,17 @@
 // short / dword -- are stored as one row of 16*NJ bytes per frame in which state s sits at bits 2s.  Emissions come from LDS: the wave stages CH frames of logq rows (k <= 64
 // floats, one coalesced read per frame) while it works on the previous CH frames.
 //   BP_LDS = 1: the T' rows fit the work-group's LDS (config 3: 500 frames x 128 bytes) and the backtrace reads them there.
-//   BP_LDS = 0: rows go to the workspace in HBM; the backtrace copies windows of W frames (the whole rows: contiguous
+//   BP_LDS = 0: rows go to the workspace in HBM; the backtrace copies windows of BT_W frames (the whole rows: contiguous
 //   bytes) into LDS, the next window's loads in flight while the current one is resolved, so that no frame of the T'-long
 //   backtrace waits on a dependent HBM load.
 // The backtrace is run by every lane of the wave on the same (wave-uniform) state: its LDS reads are broadcasts, and lane
 // t - w0 keeps the state of frame t, so the path leaves as one coalesced store per window.
-#include "common.h"
+#include "lattice.h"
 
 namespace {
 
 constexpr int CH = 16;  // frames of logq per LDS staging chunk
-constexpr int W = 64;   // frames per backtrace window (one per lane)
 constexpr int LDS_MAX = 160 * 1024;
-
-__device__ __forceinline__ float dpp_float_from_lower_lane(float v, float lane0_value) {  // lane l <- lane l-1
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0_value), __float_as_int(v), 0x138, 0xf, 0xf, false));
-}
 
 template <int NJ>
 struct BpWord;
@@ -40,27 +35,7 @@ struct BpWord<16> { typedef uint32_t T; };
 
 __host__ __device__ constexpr int row_bytes(int nj) { return 16 * nj; }  // 64 lanes x 2 bits x nj states
 
-// backtrace window w of an utterance's HBM rows (rows w*W .. min(T, w*W + W) - 1: one contiguous range) into registers, and
-// from there into LDS window buffer w & 1
-template <int V, int R>
-__device__ __forceinline__ void load_window(u32x4 (&wreg)[V], const uint8_t* bp_utt, int w, int T, int lane) {
-    const int w0 = w * W;
-    const int n16 = ((T - w0 < W ? T - w0 : W) * R) / 16;
-    const u32x4* src = (const u32x4*)(bp_utt + (long)w0 * R);
-#pragma unroll
-    for (int m = 0; m < V; ++m) {
-        const int i = m * 64 + lane;
-        if (i < n16) wreg[m] = src[i];
-    }
-}
-template <int V, int R>
-__device__ __forceinline__ void store_window(const u32x4 (&wreg)[V], uint8_t* rows, int w, int lane) {
-    u32x4* dst = (u32x4*)(rows + (w & 1) * W * R);
-#pragma unroll
-    for (int m = 0; m < V; ++m) dst[m * 64 + lane] = wreg[m];
-}
-
-// LDS: [logq chunk CH x 64 floats][final scores 64*NJ floats][backpointer rows: T' rows (BP_LDS) or two windows of W rows]
+// LDS: [logq chunk CH x 64 floats][final scores 64*NJ floats][backpointer rows: T' rows (BP_LDS) or two windows of BT_W rows]
 template <int NJ, bool BP_LDS>
 __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__ logq, const int32_t* __restrict__ labels,
                                                         const int32_t* __restrict__ label_len,
@@ -191,22 +166,22 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
     if (S >= 2 && fin[S - 2] > fin[S - 1]) s = S - 2;
     if (lane == 0) score[b] = fin[s];
 
-    // backtrace, windows [w0, w0 + W) from the last one down
-    const int nwin = (T + W - 1) / W;
-    constexpr int V = W * R / 16 / 64;  // u32x4 per lane of one window
+    // backtrace, windows [w0, w0 + BT_W) from the last one down
+    const int nwin = (T + BT_W - 1) / BT_W;
+    constexpr int V = BT_W * R / 16 / 64;  // u32x4 per lane of one window
     constexpr int VR = BP_LDS ? 1 : V;  // (no window registers when the rows stay in LDS)
     u32x4 wreg[VR];
     const uint8_t* bp_utt = bp_hbm + (long)b * t_out * R;
     if (!BP_LDS) {
-        load_window<VR, R>(wreg, bp_utt, nwin - 1, T, lane);
-        store_window<VR, R>(wreg, rows, nwin - 1, lane);
+        load_window<u32x4, VR, R>(wreg, bp_utt, nwin - 1, T, lane);
+        store_window<u32x4, VR, R>(wreg, rows, nwin - 1, lane);
     }
     for (int w = nwin - 1; w >= 0; --w) {
-        const int w0 = w * W;
-        const int w1 = T - w0 < W ? T : w0 + W;
-        if (!BP_LDS && w > 0) load_window<VR, R>(wreg, bp_utt, w - 1, T, lane);
+        const int w0 = w * BT_W;
+        const int w1 = T - w0 < BT_W ? T : w0 + BT_W;
+        if (!BP_LDS && w > 0) load_window<u32x4, VR, R>(wreg, bp_utt, w - 1, T, lane);
         __syncthreads();
-        const uint8_t* base = BP_LDS ? rows + (long)w0 * R : rows + (w & 1) * W * R;
+        const uint8_t* base = BP_LDS ? rows + (long)w0 * R : rows + (w & 1) * BT_W * R;
         int mine = -1;
         for (int t = w1 - 1; t >= w0; --t) {
             if (lane == t - w0) mine = s;
@@ -218,14 +193,14 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
         if (w0 + lane < w1) prow[w0 + lane] = mine;
         if (!BP_LDS && w > 0) {
             __syncthreads();
-            store_window<VR, R>(wreg, rows, w - 1, lane);
+            store_window<u32x4, VR, R>(wreg, rows, w - 1, lane);
         }
     }
 }
 
 template <int NJ, bool BP_LDS>
 size_t align_lds_bytes(int t_out) {
-    return (size_t)(CH * 64 + 64 * NJ) * sizeof(float) + (size_t)(BP_LDS ? t_out : 2 * W) * row_bytes(NJ);
+    return (size_t)(CH * 64 + 64 * NJ) * sizeof(float) + (size_t)(BP_LDS ? t_out : 2 * BT_W) * row_bytes(NJ);
 }
 
 int states_per_lane(int l_max) { return 2 * l_max + 1 <= 256 ? 4 : (2 * l_max + 1 <= 512 ? 8 : 16); }

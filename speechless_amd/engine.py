@@ -1036,6 +1036,40 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                      buf.align_labels.shape[1], buf.align_ws.data_ptr(), buf.align_ws.numel(), self._stream())
         return path.view(buf.batch, buf.t_out).cpu().numpy(), buf.align_score.cpu().numpy()
 
+    def asg_align(self, label_batch, label_lengths, prediction_lengths):
+        """ctc_align() for the ASG criterion: the best segmentation of the (run-length-encoded) labels over the frames under
+        the current buffer set's logq -- the emissions asg_viterbi() sees -- and the engine's asg_trans / asg_init, after
+        forward().  label_batch: int (B, Lmax) padded with anything; lengths: (B,) or (B, 1).  Returns (paths int32 (B, T')
+        numpy: the label position of the best path per frame, -1 past the utterance's length or for every frame of an
+        infeasible one; scores float32 (B,) numpy: the path's score, -inf when infeasible).  Semantics: sl_asg_align
+        (include/speechless_hip.h).  Uses tensors of its own: no gradient buffers, labels of asg() untouched."""
+        self._require_asg("asg_align()")
+        buf = self.cur
+        labels = np.asarray(label_batch, dtype=np.int32)
+        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
+        if labels.ndim != 2 or labels.shape[0] != buf.batch or lab_len.shape[0] != buf.batch:
+            raise ValueError("label batch must be (B, Lmax) with B lengths")
+        k = self.grapheme_set_size
+        for i in range(buf.batch):
+            if not 0 <= lab_len[i] <= labels.shape[1]:
+                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
+            row = labels[i, :lab_len[i]]
+            if row.size and (row.min() < 0 or row.max() >= k):
+                raise ValueError("label {} holds an index outside [0, {})".format(i, k))
+        l_max = max(int(labels.shape[1]), 1)
+        buf.ensure_align(self, l_max, "sl_asg_align_workspace_bytes")
+        buf.align_labels.zero_()
+        buf.align_labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
+        buf.align_label_len.copy_(torch.from_numpy(lab_len))
+        self.set_input_lengths(prediction_lengths)
+        path = buf._align_path_flat[:buf.batch * buf.t_out]
+        trans, init = self._asg_views(self.asg_params)
+        self._launch("asg_align", "sl_asg_align", buf.logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                     buf.align_labels.data_ptr(), buf.align_label_len.data_ptr(), buf.input_len.data_ptr(), path.data_ptr(),
+                     buf.align_score.data_ptr(), buf.batch, buf.t_out, k, buf.align_labels.shape[1], buf.align_ws.data_ptr(),
+                     buf.align_ws.numel(), self._stream())
+        return path.view(buf.batch, buf.t_out).cpu().numpy(), buf.align_score.cpu().numpy()
+
     def error_counts(self, space_index):
         """Letter and word error counts of the greedy transcriptions against the labels, after forward() + set_labels() +
         greedy_decode(): one sl_edit_distance launch on buf.labels / label_len and buf.decoded / decoded_len where they lie.

@@ -725,6 +725,33 @@ class Wav2Letter:
         ratio = self.input_to_prediction_length_ratio
         return [a.positional_label(ratio * s) for a, s in zip(self.alignment_batch(labeled_spectrogram_batch), seconds)]
 
+    def asg_alignment_batch(self, labeled_spectrogram_batch):
+        """alignment_batch for criterion='asg': the best segmentation of every example's encoded label over the frames, one
+        forward pass on the evaluation engine and one sl_asg_align launch over the emissions and scores the ASG loss and
+        decode see.  Returns a list of alignment.AsgAlignment (frames = output frames)."""
+        from .alignment import AsgAlignment
+        if self.criterion != "asg":
+            raise ValueError("asg_alignment_batch / asg_positional_label_batch need a net built with criterion='asg' "
+                             "(a CTC net aligns with alignment_batch / positional_label_batch)")
+        inputs = self._input_dictionary_for_loss_net(labeled_spectrogram_batch)
+        names = Wav2Letter.InputNames
+        engine = self.eval_engine
+        engine.forward(inputs[names.input_batch])
+        label_lengths = inputs[names.label_lengths].reshape(-1)
+        paths, scores = engine.asg_align(inputs[names.label_batch], label_lengths, inputs[names.prediction_lengths])
+        enc = self.grapheme_encoding
+        return [AsgAlignment.from_path(x.label, row[:n], enc.asg_twice, enc.asg_thrice, score, path)
+                for x, row, n, score, path in zip(labeled_spectrogram_batch, inputs[names.label_batch], label_lengths, scores,
+                                                  paths)]
+
+    def asg_positional_label_batch(self, labeled_spectrogram_batch, seconds_per_input_step=None):
+        """positional_label_batch for criterion='asg': the word timings in seconds of every example from
+        asg_alignment_batch, None where the label cannot be aligned or has no words."""
+        alignments = self.asg_alignment_batch(labeled_spectrogram_batch)  # (first: a CTC net is refused before anything else)
+        seconds = [self._seconds_per_input_step(x, seconds_per_input_step) for x in labeled_spectrogram_batch]
+        ratio = self.input_to_prediction_length_ratio
+        return [a.positional_label(ratio * s) for a, s in zip(alignments, seconds)]
+
     def _seconds_per_input_step(self, example, seconds_per_input_step):
         if seconds_per_input_step is not None:
             return float(seconds_per_input_step)
