@@ -442,6 +442,46 @@ int sl_ctc_beam_search(const float* probs, const int32_t* lengths, int batch, in
                        int merge_repeated, float eps, const sl_beam_lm* lm, int32_t* out, int32_t* out_len,
                        float* log_prob, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- ASG beam search, optionally scored by an n-gram language model: the max (Viterbi) search over prefixes under emissions
+ *      + transition scores + scorer terms.  No reference or host counterpart; this text is the definition, and a float32
+ *      restatement (tests/asg_beam_ref.py) reproduces transcripts and scores bit for bit.
+ * Inputs.  logq: float[B][t_out][k], used AS IT IS (as sl_asg_viterbi); trans[i*k + j] = g(i, j), init[j] = g0(j); input_len
+ * clamped to [0, t_out] = T_b.  k = characters + 2: asg_twice = k-2, asg_thrice = k-1.  1 <= beam_width W <= 128, 2 <= k <= 64.
+ * lm: NULL (plain search) or the sl_beam_lm tables of sl_host_scorer_export built for the k-2 CHARACTERS (trie tables of k-2
+ * columns, space_label in [-1, k-2), order <= 6).
+ * Hypotheses.  A hypothesis is a prefix: a grapheme sequence with no two adjacent graphemes equal, with a float32 score a and
+ * a scorer state.  The beam is an ordered list of at most W hypotheses.  A candidate is a pair (i, j): the position of its
+ * source in the current beam and a grapheme.  Candidate order: score descending, then i ascending, then j ascending (a total
+ * order: no two candidates share a key).
+ * Arithmetic.  float32; each line below is ONE rounded operation in the order written, no contraction; -inf entries of
+ * trans / init are legal.
+ * Scorer terms.  The characters grapheme j writes behind last grapheme l: j itself if j < k-2; nothing if j is a mark and l
+ * is absent or a mark; l once (asg_twice) or l twice (asg_thrice) otherwise (AsgGraphemeEncoding.decode_grapheme; a mark
+ * behind the space writes spaces, each scoring an empty word as <unk> like any other).  For each written character in turn:
+ *   state = expand(state, c);   a = lw * state.delta + a     (one multiply, then one add)
+ * expand / expand_end are the CTC decoder's scorer in the arithmetic and operation order of ctc_beam.hip.  lm == NULL: no
+ * scorer terms.  A grapheme that writes nothing leaves state and score alone.
+ * Frame 0, every j:   a = g0(j) + e_0(j);   the scorer terms of j from the initial state;   source position 0.
+ * Frame t > 0, every hypothesis i (last grapheme l, score s) and every j:
+ *   a = s + g(l, j);   a = a + e_t(j);   j == l: i's own prefix, state unchanged (a stay);   otherwise the child prefix with
+ *   the scorer terms of j behind l.
+ * Merge.  Two candidates can name the same prefix -- at most two: the stay of (p, l) and the extension of p by l.  The one
+ * that comes first in candidate order survives with its own key; the other is dropped.
+ * Prune.  Candidates of score -inf are dropped; the first W in candidate order, in that order, are the next beam.  Prefix
+ * identity is the sequence itself: a prefix that leaves the beam and is created again later is the same prefix (a canonical
+ * node id per (parent, label), as in sl_ctc_beam_search).
+ * End.  After frame T_b - 1: total_i = lw * expand_end(state_i).delta + a_i with lm, a_i without.  The result is the first
+ * maximal total in beam order (strict >).  out: int32[B][t_out], the prefix's graphemes then -1; out_len: int32[B]; score:
+ * float[B] or NULL.  T_b = 0 or an empty beam: out_len 0, score -inf.
+ * Status codes and argument checks as sl_ctc_beam_search; t_out * beam_width < 2^25.  workspace:
+ * sl_asg_beam_search_workspace_bytes(batch, t_out, k, beam_width) bytes (0 = unsupported shape; node arena + hash map per
+ * utterance, cleared by the call); out_len[b] = -1 flags an arena overflow, which the workspace bound rules out.  One
+ * work-group per utterance; all work on the caller's stream, no allocation, no synchronisation. */
+size_t sl_asg_beam_search_workspace_bytes(int batch, int t_out, int k, int beam_width);
+int sl_asg_beam_search(const float* logq, const float* trans, const float* init, const int32_t* input_len, int batch, int t_out,
+                       int k, int beam_width, const sl_beam_lm* lm, int32_t* out, int32_t* out_len, float* score,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- letter and word error counts: the two editdistance.eval calls of the reference's result object (speechless/net.py:
  *      31-37, over the characters and over the .split() of expected / predicted), on index rows that are in HBM already. ----
  * a: int32[batch] rows a_stride apart, the expected indices (the labels of sl_ctc_loss_grad); b: likewise b_stride apart,

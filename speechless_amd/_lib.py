@@ -158,6 +158,10 @@ SIGNATURES = {
     "sl_ctc_beam_search_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "sl_ctc_beam_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, POINTER(BeamLm),
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sl_asg_beam_search_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    # logq, trans, init, input_len, batch, t_out, k, beam_width, lm, out, out_len, score, workspace, bytes, stream
+    "sl_asg_beam_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(BeamLm),
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "sl_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_float, c_float, c_float,
                              c_float, c_void_p]),
     "sl_adam_pack_layer": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

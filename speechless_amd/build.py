@@ -13,7 +13,7 @@ HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csr
 CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "misc.hip", "spectrogram.hip", "conv_chain_bf16.hip",
            "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip",
-           "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip"]
+           "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_beam.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
 # f16x3 parity path (csrc/common.h: SL_MFMA16; only the fp32 / plane-output instantiations, about a third of the bf16 build)
 F16_VARIANTS = {"conv_nt_f16": "conv_nt_bf16.hip", "wgrad_tn_f16": "wgrad_tn_bf16.hip"}
@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 
 
 def _newest_source_mtime():
-    files = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "lds_dma.h", CSRC / "lattice.h", PACKAGE_DIR.parent / "include" / "speechless_hip.h"]
+    files = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "lds_dma.h", CSRC / "lattice.h", CSRC / "beam_lm.h", PACKAGE_DIR.parent / "include" / "speechless_hip.h"]
     return max(f.stat().st_mtime for f in files)
 
 
@@ -38,8 +38,10 @@ def _newest_source_mtime():
 # (asg.hip: a lane's label states, prefetched frames and letter-pair sums are register arrays indexed by unrolled constants;
 # scratch there puts memory traffic on the T'-long sequential path of a lone wave)
 # (asg_align.hip: the same lone wave and sequential path; its states, scores and backpointer words are register arrays)
+# (asg_beam.hip: a thread's scorer state is nine registers and the beam lives in LDS; scratch there means the state struct
+# went through memory on every expansion of the per-frame sequential path)
 NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
-              "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip"}
+              "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_beam.hip"}
 
 
 def _scratch_users(remarks):
@@ -59,7 +61,9 @@ def _scratch_users(remarks):
 # (v_pk_mul_f32 out of the SLP vectorizer) costs such a wave more than the two scalar instructions it replaces
 # ctc_beam.hip: the host decoder rounds lm_weight * delta and the add separately (no FMA may form)
 # asg_align.hip: every add of the recurrence is rounded on its own (it has no multiply; the flag states the contract)
-FILE_FLAGS = {"ctc.hip": ["-fno-slp-vectorize"], "ctc_beam.hip": ["-ffp-contract=off"], "asg_align.hip": ["-ffp-contract=off"]}
+# asg_beam.hip: lm_weight * delta is rounded before it is added (sl_asg_beam_search is defined bit for bit)
+FILE_FLAGS = {"ctc.hip": ["-fno-slp-vectorize"], "ctc_beam.hip": ["-ffp-contract=off"], "asg_align.hip": ["-ffp-contract=off"],
+              "asg_beam.hip": ["-ffp-contract=off"]}
 
 
 def _compile(unit):

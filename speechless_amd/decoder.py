@@ -144,6 +144,44 @@ def export_scorer_tables(scorer_handle):
     return t
 
 
+def _upload_scorer(hip, characters, language_model, kenlm_weight, word_count_weight, valid_word_count_weight, device):
+    """The host scorer over `characters`, flattened and uploaded: (dict of device tensors that keeps the memory alive,
+    the BeamLm structure of their pointers and scalars)."""
+    import torch
+    host = CtcBeamSearchDecoder(characters, language_model, beam_width=1, kenlm_weight=kenlm_weight,
+                                word_count_weight=word_count_weight, valid_word_count_weight=valid_word_count_weight)
+    t = export_scorer_tables(host._scorer)
+    dev = {name: torch.from_numpy(t[name].view(np.int32) if name == "ngrams" else t[name]).to(device)
+           for name in ("trie_child", "trie_min", "trie_word", "ngrams")}
+    p, ids = t["params"], t["ids"]
+    lm = hip.BeamLm(dev["trie_child"].data_ptr(), dev["trie_min"].data_ptr(), dev["trie_word"].data_ptr(),
+                    dev["ngrams"].data_ptr(), t["trie_word"].shape[0], t["ngrams"].shape[0], t["order"],
+                    int(ids[0]), int(ids[1]), int(ids[2]), float(p[0]), float(p[1]), float(p[2]), float(p[3]))
+    return dev, lm
+
+
+def _check_gpu_limits(k, beam_width, language_model):
+    if not 2 <= k <= GPU_MAX_CLASSES:
+        raise BeamSearchLimitError("the GPU beam search takes 2..{} classes (one lane each), not {}".format(
+            GPU_MAX_CLASSES, k))
+    if not 1 <= beam_width <= GPU_MAX_BEAM_WIDTH:
+        raise BeamSearchLimitError("the GPU beam search takes a beam width of 1..{}, not {}".format(
+            GPU_MAX_BEAM_WIDTH, beam_width))
+    if language_model is not None and not 1 <= language_model.order <= GPU_MAX_LM_ORDER:
+        raise BeamSearchLimitError("the GPU beam search takes a language model of order 1..{}, not {}".format(
+            GPU_MAX_LM_ORDER, language_model.order))
+
+
+def _to_device(array, dtype, device):
+    import torch
+    if isinstance(array, torch.Tensor):
+        if array.device.type != "cuda":
+            array = array.to(device)
+        return array.to(dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(array), dtype={torch.float32: np.float32,
+                                                                            torch.int32: np.int32}[dtype])).to(device)
+
+
 class GpuCtcBeamSearchDecoder:
     """CtcBeamSearchDecoder on the GPU (ctc_beam.hip): the same search and the same results, one wave per utterance.
     The language model's tables are exported from the host scorer and uploaded once.  Limits: at most 64 classes,
@@ -156,15 +194,7 @@ class GpuCtcBeamSearchDecoder:
         from . import _lib as hip
         self.allowed_characters = list(allowed_characters)
         k = len(self.allowed_characters) + 1
-        if not 2 <= k <= GPU_MAX_CLASSES:
-            raise BeamSearchLimitError("the GPU beam search takes 2..{} classes (one lane each), not {}".format(
-                GPU_MAX_CLASSES, k))
-        if not 1 <= beam_width <= GPU_MAX_BEAM_WIDTH:
-            raise BeamSearchLimitError("the GPU beam search takes a beam width of 1..{}, not {}".format(
-                GPU_MAX_BEAM_WIDTH, beam_width))
-        if language_model is not None and not 1 <= language_model.order <= GPU_MAX_LM_ORDER:
-            raise BeamSearchLimitError("the GPU beam search takes a language model of order 1..{}, not {}".format(
-                GPU_MAX_LM_ORDER, language_model.order))
+        _check_gpu_limits(k, beam_width, language_model)
         self.beam_width = beam_width
         self.merge_repeated = merge_repeated
         self.epsilon = epsilon
@@ -176,18 +206,8 @@ class GpuCtcBeamSearchDecoder:
         self._lm = None
         self._workspace = None
         if language_model is not None:
-            host = CtcBeamSearchDecoder(self.allowed_characters, language_model, beam_width=1,
-                                        kenlm_weight=kenlm_weight, word_count_weight=word_count_weight,
-                                        valid_word_count_weight=valid_word_count_weight)
-            t = export_scorer_tables(host._scorer)
-            dev = {name: torch.from_numpy(t[name].view(np.int32) if name == "ngrams" else t[name]).to(self.device)
-                   for name in ("trie_child", "trie_min", "trie_word", "ngrams")}
-            self._tables = dev  # keeps the device memory alive
-            p, ids = t["params"], t["ids"]
-            self._lm = hip.BeamLm(dev["trie_child"].data_ptr(), dev["trie_min"].data_ptr(), dev["trie_word"].data_ptr(),
-                                  dev["ngrams"].data_ptr(), t["trie_word"].shape[0], t["ngrams"].shape[0], t["order"],
-                                  int(ids[0]), int(ids[1]), int(ids[2]), float(p[0]), float(p[1]), float(p[2]),
-                                  float(p[3]))
+            self._tables, self._lm = _upload_scorer(hip, self.allowed_characters, language_model, kenlm_weight,
+                                                    word_count_weight, valid_word_count_weight, self.device)
 
     @classmethod
     def from_kenlm_directory(cls, kenlm_directory, allowed_characters, **kw):
@@ -236,3 +256,74 @@ class GpuCtcBeamSearchDecoder:
         if (out_len < 0).any():
             raise RuntimeError("sl_ctc_beam_search: node arena overflow")
         return [list(map(int, out[i, :out_len[i]])) for i in range(b)], log_prob
+
+
+class GpuAsgBeamSearchDecoder:
+    """The ASG beam search on the GPU (asg_beam.hip; definition: include/speechless_hip.h, sl_asg_beam_search): a max search
+    over grapheme prefixes under emissions + transition scores, scored by the n-gram model when there is one.  The graphemes
+    are the allowed characters and the two repeat marks (AsgGraphemeEncoding); the scorer is built over the characters, and
+    a repeat mark feeds it the characters it stands for.  Limits: at most 64 graphemes, beam width 1..128, language-model
+    order <= 6 (BeamSearchLimitError, a ValueError, otherwise)."""
+
+    def __init__(self, allowed_characters, language_model=None, beam_width=DEFAULT_BEAM_WIDTH, kenlm_weight=KENLM_WEIGHT,
+                 word_count_weight=WORD_COUNT_WEIGHT, valid_word_count_weight=VALID_WORD_COUNT_WEIGHT, device="cuda:0"):
+        self.allowed_characters = list(allowed_characters)
+        self.grapheme_set_size = len(self.allowed_characters) + 2
+        _check_gpu_limits(self.grapheme_set_size, beam_width, language_model)
+        if language_model is not None and not self.allowed_characters:
+            raise BeamSearchLimitError("a language model needs at least one character beside the two repeat marks")
+        import torch
+        from . import _lib as hip
+        self.beam_width = beam_width
+        self.language_model = language_model
+        self.device = torch.device(device)
+        self._hip = hip
+        self._tables = None
+        self._lm = None
+        self._workspace = None
+        if language_model is not None:
+            self._tables, self._lm = _upload_scorer(hip, self.allowed_characters, language_model, kenlm_weight,
+                                                    word_count_weight, valid_word_count_weight, self.device)
+
+    @classmethod
+    def from_kenlm_directory(cls, kenlm_directory, allowed_characters, **kw):
+        return cls(allowed_characters, NGramLanguageModel(find_arpa(kenlm_directory)), **kw)
+
+    def decode(self, logq, trans, init, prediction_lengths):
+        """logq: (B, T', K) emissions, trans: (K, K) [from][to], init: (K,) -- numpy arrays or float32 tensors on the GPU
+        (used in place); prediction_lengths: (B,) numbers, numpy or tensor.  Returns (list of grapheme index lists, scores
+        (B,) numpy)."""
+        import torch
+        logq = _to_device(logq, torch.float32, self.device)
+        if logq.dim() != 3:
+            raise ValueError("logq must be (B, T', K)")
+        b, t, k = logq.shape
+        if k != self.grapheme_set_size:
+            raise ValueError("{} classes for {} characters + 2 repeat marks".format(k, len(self.allowed_characters)))
+        trans = _to_device(trans, torch.float32, logq.device)
+        init = _to_device(init, torch.float32, logq.device)
+        if tuple(trans.shape) != (k, k) or tuple(init.shape) != (k,):
+            raise ValueError("ASG scores must have shapes ({0}, {0}) and ({0},), not {1} and {2}".format(
+                k, tuple(trans.shape), tuple(init.shape)))
+        lengths = _to_device(prediction_lengths, torch.int32, logq.device).reshape(-1)
+        if lengths.numel() != b:
+            raise ValueError("{} lengths for a batch of {}".format(lengths.numel(), b))
+        lib = self._hip.lib()
+        need = lib.raw("sl_asg_beam_search_workspace_bytes")(b, t, k, self.beam_width)
+        if need == 0:
+            raise BeamSearchLimitError("the GPU beam search cannot take a ({}, {}, {}) batch at beam width {}".format(
+                b, t, k, self.beam_width))
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != logq.device:
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=logq.device)
+        out = torch.empty((b, t), dtype=torch.int32, device=logq.device)
+        out_len = torch.empty((b,), dtype=torch.int32, device=logq.device)
+        score = torch.empty((b,), dtype=torch.float32, device=logq.device)
+        with torch.cuda.device(logq.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            lib.call("sl_asg_beam_search", logq.data_ptr(), trans.data_ptr(), init.data_ptr(), lengths.data_ptr(), b, t, k,
+                     self.beam_width, ctypes.byref(self._lm) if self._lm is not None else None, out.data_ptr(),
+                     out_len.data_ptr(), score.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), stream)
+        out, out_len, score = out.cpu().numpy(), out_len.cpu().numpy(), score.cpu().numpy()
+        if (out_len < 0).any():
+            raise RuntimeError("sl_asg_beam_search: node arena overflow")
+        return [list(map(int, out[i, :out_len[i]])) for i in range(b)], score

@@ -991,6 +991,17 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             decoded.append([int(g) for g in row[np.concatenate([[True], row[1:] != row[:-1]])]] if row.size else [])
         return decoded, paths
 
+    def asg_beam_search(self, decoder, prediction_lengths=None):
+        """asg_viterbi() with a beam and, if the decoder has one, the n-gram language model (decoder:
+        decoder.GpuAsgBeamSearchDecoder): sl_asg_beam_search over the current logq and the engine's asg_trans / asg_init, in
+        place on the device and on the current stream.  Returns (list of grapheme index lists, scores (B,) numpy)."""
+        self._require_asg("asg_beam_search()")
+        buf = self.cur
+        if prediction_lengths is not None:
+            self.set_input_lengths(prediction_lengths)
+        trans, init = self._asg_views(self.asg_params)
+        return decoder.decode(buf.logq, trans, init, buf.input_len)
+
     def asg_adam_step(self):
         """Adam on the two ASG tables with the step's hyper-parameters and iteration count (adam_iterations already counts
         this step): one sl_adam_step launch over [g | g0].  Another rule: the same launch of its flat kernel."""

@@ -357,8 +357,9 @@ class Wav2Letter:
             raise ValueError("criterion must be 'ctc' or 'asg', not {!r}".format(criterion))
         self.criterion = criterion
         if criterion == "asg":
-            if kenlm_directory is not None:
-                raise ValueError("criterion='asg': the beam search (kenlm_directory) is a CTC decoder; not supported")
+            if kenlm_directory is not None and beam_search_device != "gpu":
+                raise ValueError("criterion='asg': kenlm_directory needs beam_search_device='gpu' (asg_beam.hip); there is "
+                                 "no host ASG beam search")
             clipped = optimizer is not None and optimizer_settings(optimizer)
             if track_gradient_norm or (clipped and (clipped["clipnorm"] or clipped["clipvalue"])):
                 raise ValueError("criterion='asg': gradient clipping (clipnorm / clipvalue) and track_gradient_norm cover the "
@@ -430,7 +431,11 @@ class Wav2Letter:
             if list(allowed_characters) != expected:
                 raise ValueError("Allowed characters {} differ from those expected by kenlm decoder: {}".format(
                     allowed_characters, expected))
-            if beam_search_device == "gpu":  # extension: the same search in ctc_beam.hip (Engine.beam_search)
+            if criterion == "asg":  # extension: the ASG beam search of asg_beam.hip (Engine.asg_beam_search)
+                from .decoder import GpuAsgBeamSearchDecoder
+                self._beam_decoder = GpuAsgBeamSearchDecoder.from_kenlm_directory(
+                    self.kenlm_directory, allowed_characters, device=device)
+            elif beam_search_device == "gpu":  # extension: the same search in ctc_beam.hip (Engine.beam_search)
                 from .decoder import GpuCtcBeamSearchDecoder
                 self._beam_decoder = GpuCtcBeamSearchDecoder.from_kenlm_directory(
                     self.kenlm_directory, allowed_characters, epsilon=ctc_epsilon, device=device)
@@ -679,7 +684,9 @@ class Wav2Letter:
         engine.set_labels(inputs[names.label_batch], inputs[names.label_lengths],
                           inputs[names.prediction_lengths])
         losses = engine.loss().cpu().numpy()
-        if self._beam_decoder is not None and self.beam_search_device == "gpu":
+        if self._beam_decoder is not None and self.criterion == "asg":
+            decoded, _ = engine.asg_beam_search(self._beam_decoder, inputs[names.prediction_lengths])
+        elif self._beam_decoder is not None and self.beam_search_device == "gpu":
             decoded, _ = engine.beam_search(self._beam_decoder, inputs[names.prediction_lengths])
         elif self._beam_decoder is not None:  # net.py:444-451: beam search scored by the language model
             decoded, _ = self._beam_decoder.decode(engine.cur.probs.cpu().numpy(),
