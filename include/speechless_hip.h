@@ -341,6 +341,20 @@ int sl_ctc_align(const float* logq, const int32_t* labels, const int32_t* label_
                  int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- CTC forced alignment of long recordings: sl_ctc_align beyond 511 letters.  Arguments, their order and every rule
+ *      (states, recursion, strict-> tie order stay / s-1 / s-2, end state, infeasible rows, L = 0, T_b = 0, the clamping of
+ *      label_len, input_len and label values) are those of sl_ctc_align above; score and path are bit for bit what it
+ *      returns where both accept the shape.  Limits: 1 < k <= 64, 0 <= l_max <= 8191 (16 383 lattice states: one work-group
+ *      of 1 / 2 / 4 / 8 / 16 waves per recording for l_max <= 511 / 1023 / 2047 / 4095 / 8191, 16 states per lane),
+ *      SL_ERR_UNSUPPORTED otherwise; t_out is limited by the workspace only.  A null pointer is SL_ERR_INVALID_ARGUMENT, a
+ *      workspace below the size asked for SL_ERR_WORKSPACE_TOO_SMALL; all of these are refused on the host before any launch.
+ * workspace: sl_ctc_align_long_workspace_bytes(batch, t_out, l_max) bytes = batch * t_out * 256 * waves: the backpointers (2 bits
+ * per state and frame) always go to HBM.  Monotonic in t_out and l_max, 0 for arguments out of range. */
+size_t sl_ctc_align_long_workspace_bytes(int batch, int t_out, int l_max);
+int sl_ctc_align_long(const float* logq, const int32_t* labels, const int32_t* label_len, const int32_t* input_len,
+                      int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* ---- ASG criterion (auto segmentation criterion of the wav2letter paper, arXiv:1609.03193).  No reference counterpart:
  *      the reference raises NotImplementedError where its ASG loss would be (speechless/net.py:397-399). ----------------------
  * K = k letters and NO blank.  trans: float[k][k], trans[i*k + j] = g(i, j) = the score of moving from letter i to letter

@@ -11,9 +11,12 @@ def __getattr__(name):
                 "ExpectationsVsPredictionsInBatches", "ExpectationsVsPredictionsInGroupedBatches"):
         from . import net
         return getattr(net, name)
-    if name in ("PositionalLabel", "CtcAlignment", "AsgAlignment"):
+    if name in ("PositionalLabel", "CtcAlignment", "AsgAlignment", "cut_sections"):
         from . import alignment
         return getattr(alignment, name)
+    if name == "window_plan":
+        from .longform import window_plan
+        return window_plan
     if name == "Engine":
         from .engine import Engine
         return Engine

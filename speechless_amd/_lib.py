@@ -140,6 +140,9 @@ SIGNATURES = {
     "sl_ctc_align_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sl_ctc_align": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_void_p, c_size_t, c_void_p]),
+    "sl_ctc_align_long_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sl_ctc_align_long": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_void_p, c_size_t, c_void_p]),
     "sl_asg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     # probs, logq, trans, init, labels, label_len, input_len, loss, dlogits, dtrans, dinit; then sl_ctc_loss_grad's tail
     "sl_asg_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -108,6 +108,32 @@ class CtcAlignment(_WordTimings):
         return "CtcAlignment({!r}, log_probability={}, words={})".format(self.label, self.log_probability, self.word_frames)
 
 
+def cut_sections(alignment, max_frames: int) -> List[Tuple[str, Tuple[int, int]]]:
+    """Cuts an aligned recording (Wav2Letter.align_recording) into sections of whole words, (text, (first, end)) in output
+    frames: what LabeledExampleFromFile.sections() (labeled_example.py:219-234) needs to turn a long recording into utterances.
+    Greedy: a section takes words while its last word's end - its first word's first <= max_frames; a single word longer
+    than that is a section by itself.  The cut between two sections lies at the midpoint (integer floor) of the gap between
+    the neighbouring words; the first section starts at its first word's first frame, the last ends at its last word's end.
+    Empty for an infeasible alignment (or one without words)."""
+    words = alignment.word_frames
+    groups = []  # type: List[List[int]]
+    for i, (_, (first, end)) in enumerate(words):
+        if groups and end - words[groups[-1][0]][1][0] <= max_frames:
+            groups[-1].append(i)
+        else:
+            groups.append([i])
+    sections = []
+    for n, group in enumerate(groups):
+        start = words[group[0]][1][0]
+        end = words[group[-1]][1][1]
+        if n > 0:
+            start = (words[group[0] - 1][1][1] + start) // 2
+        if n + 1 < len(groups):
+            end = (end + words[group[-1] + 1][1][0]) // 2
+        sections.append((" ".join(words[i][0] for i in group), (start, end)))
+    return sections
+
+
 def _characters_per_grapheme(label: str) -> List[Tuple[int, bool]]:
     """(characters, is a repeat mark) per grapheme of the ASG encoding of `label`: a letter stands for 1 character; a run of
     two / three equal letters is written as the letter and a repeat mark that stands for 1 / 2 characters.

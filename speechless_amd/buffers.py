@@ -393,3 +393,27 @@ class _Buffers:
         if self.edit_rows is None or self.edit_rows.numel() < count:
             self.edit_rows = torch.zeros((count,), dtype=torch.int32, device=eng.device)
         return self.edit_rows[:count]
+
+
+class _LongAlignBuffers:
+    """Tensors of Engine.ctc_align_long, which aligns a logq tensor handed to it and so belongs to no (batch, frames) buffer
+    set: labels, lengths, the path / score results and the backpointer workspace of sl_ctc_align_long, grown only."""
+
+    def __init__(self, device):
+        self.device = device
+        self.labels = self.label_len = self.input_len = self.score = self.path = self.ws = None
+
+    def ensure(self, batch, t_out, l_max):
+        dev = self.device
+        if self.labels is None or self.labels.shape[0] != batch or self.labels.shape[1] < l_max:
+            self.labels = torch.zeros((batch, l_max), dtype=torch.int32, device=dev)
+            self.label_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
+            self.input_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
+            self.score = torch.zeros((batch,), dtype=torch.float32, device=dev)
+        if self.path is None or self.path.numel() < batch * t_out:
+            self.path = torch.zeros((batch * t_out,), dtype=torch.int32, device=dev)
+        need = lib().raw("sl_ctc_align_long_workspace_bytes")(batch, t_out, self.labels.shape[1])
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = None  # (free the old one first: at the limit a recording's backpointers take 4 KB per frame)
+            self.ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+        return need

@@ -213,6 +213,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.dropout_seed = 0
         self._dropout_steps = 0
         self.cur = None
+        self._long_align = None  # buffers._LongAlignBuffers of ctc_align_long, on first use
         self.timeline = None
         self.kernel_timeline = None  # (set of tags, list of (tag, start, stop)): see _around
         self._side_stream = None
@@ -1046,6 +1047,104 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                      buf.input_len.data_ptr(), path.data_ptr(), buf.align_score.data_ptr(), buf.batch, buf.t_out, k,
                      buf.align_labels.shape[1], buf.align_ws.data_ptr(), buf.align_ws.numel(), self._stream())
         return path.view(buf.batch, buf.t_out).cpu().numpy(), buf.align_score.cpu().numpy()
+
+    # ------------------------------------------------------------------ long recordings (longform.py)
+
+    def forward_long(self, input_2d, window_input_frames=None, batch_windows=8):
+        """forward() over a recording of any length: the windows of longform.window_plan run through forward() in batches of
+        up to batch_windows, and the output frames of each that equal a single pass over the whole recording are copied on
+        the device into tensors of this call's own.  input_2d: (T, F) numpy or float32 tensor.  Returns (probs, logq), fp32
+        (1, ceil(T / ratio), K) in HBM; nothing but the input crosses PCIe.  window_input_frames: None = DEFAULT_WINDOW."""
+        from . import longform
+        if self.front_plan is not None:
+            raise ValueError("forward_long: raw-wave input is not supported (the window geometry of the sample-rate front "
+                             "layer is out of scope)")
+        if isinstance(input_2d, np.ndarray):
+            src = torch.from_numpy(np.ascontiguousarray(input_2d, dtype=np.float32)).to(self.device, non_blocking=True)
+        else:
+            src = input_2d.to(device=self.device, dtype=torch.float32).contiguous()
+        if src.dim() != 2 or src.shape[0] < 1:
+            raise ValueError("forward_long takes one recording: (frames, bins) with at least one frame")
+        window = longform.DEFAULT_WINDOW if window_input_frames is None else int(window_input_frames)
+        plan = longform.window_plan(int(src.shape[0]), self.plans, window)
+        k = self.grapheme_set_size
+        frames_out = plan[-1].out_end
+        probs = torch.empty((1, frames_out, k), dtype=torch.float32, device=self.device)
+        logq = torch.empty((1, frames_out, k), dtype=torch.float32, device=self.device)
+        step = max(int(batch_windows), 1)
+        for i in range(0, len(plan), step):
+            part = plan[i:i + step]
+            batch = torch.stack([src[w.input_start:w.input_start + w.input_length] for w in part])
+            self.forward(batch)
+            buf = self.cur
+            for row, w in enumerate(part):
+                probs[0, w.out_start:w.out_end].copy_(buf.probs[row, w.keep_start:w.keep_end])
+                logq[0, w.out_start:w.out_end].copy_(buf.logq[row, w.keep_start:w.keep_end])
+        return probs, logq
+
+    def greedy_decode_long(self, probs):
+        """Greedy CTC decode (sl_greedy_decode) of a (B, T', K) fp32 probability tensor in HBM, e.g. forward_long's, over all
+        of its frames.  Returns a list of index lists.  The kernel keeps a recording's frame argmax in LDS: beyond
+        longform.GREEDY_DECODE_MAX_FRAMES output frames it raises longform.RecordingTooLongError."""
+        from . import longform
+        b, t_out, k = probs.shape
+        if t_out > longform.GREEDY_DECODE_MAX_FRAMES:
+            raise longform.RecordingTooLongError(
+                "greedy decoding takes at most {} output frames per recording (sl_greedy_decode keeps them in LDS), not {}".format(
+                    longform.GREEDY_DECODE_MAX_FRAMES, t_out))
+        if t_out == 0:
+            return [[] for _ in range(b)]
+        dev = self.device
+        lens = torch.full((b,), t_out, dtype=torch.int32, device=dev)
+        out = torch.zeros((b, t_out), dtype=torch.int32, device=dev)
+        out_len = torch.zeros((b,), dtype=torch.int32, device=dev)
+        probs = probs.contiguous()
+        self._launch("decode_long", "sl_greedy_decode", probs.data_ptr(), lens.data_ptr(), out.data_ptr(), out_len.data_ptr(),
+                     None, b, t_out, k, k - 1, self._stream())
+        dec, n = out.cpu().numpy(), out_len.cpu().numpy()
+        return [list(map(int, dec[i, :n[i]])) for i in range(b)]
+
+    def ctc_align_long(self, logq, label_batch, label_lengths, prediction_lengths):
+        """ctc_align() beyond 511 letters, on a given (B, T', K) fp32 logq tensor in HBM (forward_long's): one
+        sl_ctc_align_long launch (include/speechless_hip.h; labels of up to longform.ALIGN_MAX_LABEL letters).  Does not touch
+        the current buffer set.  label_batch: int (B, Lmax) padded with anything; lengths: (B,) or (B, 1).  Returns (paths
+        int32 (B, T') numpy, scores float32 (B,) numpy) as ctc_align does."""
+        from . import longform
+        from .buffers import _LongAlignBuffers
+        if self.criterion == "asg":
+            raise ValueError("criterion='asg': forced alignment runs over the CTC lattice (blank = K - 1); not supported")
+        k = self.grapheme_set_size
+        if logq.dim() != 3 or logq.shape[2] != k or logq.dtype != torch.float32 or not logq.is_cuda:
+            raise ValueError("logq must be a float32 (B, T', {}) tensor on the device".format(k))
+        logq = logq.contiguous()
+        batch, t_out = int(logq.shape[0]), int(logq.shape[1])
+        labels = np.asarray(label_batch, dtype=np.int32)
+        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
+        in_len = np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)
+        if labels.ndim != 2 or labels.shape[0] != batch or lab_len.shape[0] != batch or in_len.shape[0] != batch:
+            raise ValueError("label batch must be (B, Lmax) with B label lengths and B prediction lengths")
+        if labels.shape[1] > longform.ALIGN_MAX_LABEL:
+            raise ValueError("labels of {} letters: forced alignment takes at most {} (sl_ctc_align_long)".format(
+                labels.shape[1], longform.ALIGN_MAX_LABEL))
+        for i in range(batch):
+            if not 0 <= lab_len[i] <= labels.shape[1]:
+                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
+            row = labels[i, :lab_len[i]]
+            if row.size and (row.min() < 0 or row.max() >= k - 1):
+                raise ValueError("label {} holds an index outside [0, {}) (blank is {})".format(i, k - 1, k - 1))
+        if self._long_align is None:
+            self._long_align = _LongAlignBuffers(self.device)
+        la = self._long_align
+        need = la.ensure(batch, t_out, max(int(labels.shape[1]), 1))
+        la.labels.zero_()
+        la.labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
+        la.label_len.copy_(torch.from_numpy(lab_len))
+        la.input_len.copy_(torch.from_numpy(in_len))
+        path = la.path[:batch * t_out]
+        self._launch("align_long", "sl_ctc_align_long", logq.data_ptr(), la.labels.data_ptr(), la.label_len.data_ptr(),
+                     la.input_len.data_ptr(), path.data_ptr(), la.score.data_ptr(), batch, t_out, k, la.labels.shape[1],
+                     la.ws.data_ptr(), need, self._stream())
+        return path.view(batch, t_out).cpu().numpy(), la.score.cpu().numpy()
 
     def asg_align(self, label_batch, label_lengths, prediction_lengths):
         """ctc_align() for the ASG criterion: the best segmentation of the (run-length-encoded) labels over the frames under

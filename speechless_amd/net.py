@@ -732,6 +732,54 @@ class Wav2Letter:
         ratio = self.input_to_prediction_length_ratio
         return [a.positional_label(ratio * s) for a, s in zip(self.alignment_batch(labeled_spectrogram_batch), seconds)]
 
+    # ------------------------------------------------------------------ long recordings (extension; longform.py)
+    def _recording_spectrogram(self, spectrogram_or_example, what):
+        if self.use_raw_wave_input:
+            raise ValueError("{}: a net with use_raw_wave_input=True is not supported (the window geometry of the raw-wave "
+                             "front layer is out of scope)".format(what))
+        x = spectrogram_or_example
+        if hasattr(x, "z_normalized_transposed_spectrogram"):
+            x = x.z_normalized_transposed_spectrogram()
+        return np.asarray(x, dtype=np.float32)
+
+    def predict_recording(self, spectrogram_or_example, window_input_frames=None):
+        """Greedy transcript of ONE recording of any length (a (T, F) spectrogram as predict_batch_greedily takes them, or an
+        example): Engine.forward_long over windows, one sl_greedy_decode over the stitched probabilities."""
+        if self.criterion == "asg":
+            raise ValueError("criterion='asg': predict_recording decodes the CTC way (blank = K - 1); not supported")
+        spectrogram = self._recording_spectrogram(spectrogram_or_example, "predict_recording")
+        engine = self.eval_engine
+        probs, _ = engine.forward_long(spectrogram, window_input_frames)
+        decoded = engine.greedy_decode_long(probs[:, :spectrogram.shape[0] // self.input_to_prediction_length_ratio])[0]
+        return self.grapheme_encoding.decode_graphemes(decoded, merge_repeated=False)
+
+    def align_recording(self, example, window_input_frames=None):
+        """alignment_batch for ONE recording of any length and a label of up to longform.ALIGN_MAX_LABEL letters:
+        Engine.forward_long over windows, then one sl_ctc_align_long launch over the stitched logq.  Returns an
+        alignment.CtcAlignment (frames = output frames); alignment.cut_sections cuts it into utterances."""
+        from . import longform
+        from .alignment import CtcAlignment
+        if self.criterion == "asg":
+            raise ValueError("criterion='asg': forced alignment (align_recording, positional_label_of_recording) runs over the "
+                             "CTC lattice; not supported")
+        spectrogram = self._recording_spectrogram(example, "align_recording")
+        if len(example.label) > longform.ALIGN_MAX_LABEL:
+            raise ValueError("a label of {} letters: align_recording takes at most {} (sl_ctc_align_long)".format(
+                len(example.label), longform.ALIGN_MAX_LABEL))
+        engine = self.eval_engine
+        _, logq = engine.forward_long(spectrogram, window_input_frames)
+        labels = self.grapheme_encoding.encode_label_batch([example.label])
+        paths, scores = engine.ctc_align_long(logq, labels, [len(example.label)],
+                                              [spectrogram.shape[0] // self.input_to_prediction_length_ratio])
+        return CtcAlignment.from_path(example.label, scores[0], paths[0])
+
+    def positional_label_of_recording(self, example, seconds_per_input_step=None, window_input_frames=None):
+        """positional_label_batch for ONE recording of any length (align_recording): its word timings in seconds, None where
+        the label cannot be aligned or has no words."""
+        alignment = self.align_recording(example, window_input_frames)  # (first: it refuses what it cannot align)
+        seconds = self._seconds_per_input_step(example, seconds_per_input_step)
+        return alignment.positional_label(self.input_to_prediction_length_ratio * seconds)
+
     def asg_alignment_batch(self, labeled_spectrogram_batch):
         """alignment_batch for criterion='asg': the best segmentation of every example's encoded label over the frames, one
         forward pass on the evaluation engine and one sl_asg_align launch over the emissions and scores the ASG loss and
