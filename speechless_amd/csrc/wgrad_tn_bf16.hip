@@ -94,6 +94,70 @@ __device__ __forceinline__ int dma_src_offset(int j, int lane, int row_stride) {
     return row * row_stride + chunk16 * 8;
 }
 
+// ---- the tile of a TnArgs work-group (the 16-wave template and the two 8-wave TnArgs kernels)
+// logical id = (((group * splits + split) * co_tiles + co_tile) * ci_tiles + ci_tile) * taps + tap
+struct TnTile {
+    int group, tap, ci_tile, co_tile, split;
+    int b_begin, nb;  // this split's utterances: first one and their number
+    __device__ __forceinline__ bool decode(const TnArgs& a) {
+        int wg = xcd_remap(blockIdx.x, a.tiles * a.splits * a.groups);
+        if (wg >= a.tiles * a.splits * a.groups) return false;  // grid padding (xcd_grid)
+        group = wg / (a.tiles * a.splits);
+        wg -= group * (a.tiles * a.splits);
+        tap = wg % a.taps;
+        wg /= a.taps;
+        ci_tile = wg % a.ci_tiles;
+        wg /= a.ci_tiles;
+        co_tile = wg % a.co_tiles;
+        split = wg / a.co_tiles;
+        b_begin = split * a.b_per_split;
+        int b_end = b_begin + a.b_per_split;
+        if (b_end > a.batch) b_end = a.batch;
+        nb = b_end - b_begin;
+        return true;
+    }
+    // the tile's first rows in utterance b_begin (tiles of tci input and tco output channels)
+    __device__ __forceinline__ const __bf16* x_src(const TnArgs& a, int tci) const {
+        return a.x + group * a.x_gs + (long)(a.x_row0 + tap) * a.x_rs + ci_tile * tci + (long)b_begin * a.x_bs;
+    }
+    __device__ __forceinline__ const __bf16* g_src(const TnArgs& a, int tco) const {
+        return a.g + group * a.g_gs + (long)a.g_row0 * a.g_rs + co_tile * tco + (long)b_begin * a.g_bs;
+    }
+    __device__ __forceinline__ float* out(const TnArgs& a) const {
+        return a.splits > 1 ? a.out + ((long)group * a.splits + split) * a.split_stride : a.out + group * a.dw_gs;
+    }
+};
+
+// ---- a wave's accumulators: 64 output channels (jn) x 16 * NT input channels (it)
+// (zero_acc: the 16-wave template and wgrad_tn_ilv_kernel; wgrad_tn_ilv32_kernel and wgrad_tn_ilv_multi_kernel zero in place, each
+// for the reason given there)
+template <int NT>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[4][NT]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+// store: the lane holds columns col0 + jn * 16 + {0..3} of rows row0 + it * 16 of a matrix of `pitch` floats per row
+// (callers: row0 ends in lane & 15, col0 in (lane >> 4) * 4; I = long where rows * pitch may pass 2^31)
+template <int NT, typename I>
+__device__ __forceinline__ void store_acc(const f32x4 (&acc)[4][NT], float* out, I row0, int col0, int pitch) {
+#pragma unroll
+    for (int it = 0; it < NT; ++it) {
+        const I row = (row0 + it * 16) * pitch;
+#pragma unroll
+        for (int jn = 0; jn < 4; ++jn) *(f32x4*)(out + row + col0 + jn * 16) = acc[jn][it];
+    }
+}
+// ... of a TnArgs tile: wave (wm, wn) of a tile of tci x tco channels, into dw[tap][cin][cout] or its split's partial
+template <int NT>
+__device__ __forceinline__ void store_tn_tile(const TnArgs& a, const TnTile& t, const f32x4 (&acc)[4][NT], int tci, int tco,
+                                              int wm, int wn, int lane) {
+    const int ci_base = t.ci_tile * tci + wm * (16 * NT) + (lane & 15);
+    const int co_base = t.co_tile * tco + wn * 64 + (lane >> 4) * 4;
+    store_acc(acc, t.out(a), (long)t.tap * a.cin + ci_base, co_base, a.cout);
+}
+
 template <int WM, int WN, int STAGES>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void wgrad_tn_bf16_kernel(TnArgs a) {
     constexpr int NW = WM * WN;
@@ -116,29 +180,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void wgrad_t
     const int wn = wave % WN;  // co block
     const int g = lane >> 4;
 
-    // logical id = ((split * co_tiles + co_tile) * ci_tiles + ci_tile) * taps + tap
-    int wg = xcd_remap(blockIdx.x, a.tiles * a.splits * a.groups);
-    if (wg >= a.tiles * a.splits * a.groups) return;  // grid padding (xcd_grid)
-    const int group = wg / (a.tiles * a.splits);
-    wg -= group * (a.tiles * a.splits);
-    const int tap = wg % a.taps;
-    wg /= a.taps;
-    const int ci_tile = wg % a.ci_tiles;
-    wg /= a.ci_tiles;
-    const int co_tile = wg % a.co_tiles;
-    const int split = wg / a.co_tiles;
-    const int b_begin = split * a.b_per_split;
-    int b_end = b_begin + a.b_per_split;
-    if (b_end > a.batch) b_end = a.batch;
-    const int n = (b_end - b_begin) * a.t_chunks;
-
+    TnTile t;
+    if (!t.decode(a)) return;
+    const int n = t.nb * a.t_chunks;
     int xoff[XPW], goff_src[GPW];
 #pragma unroll
     for (int q = 0; q < XPW; ++q) xoff[q] = dma_src_offset<WM>(wave * XPW + q, lane, a.x_rs);
 #pragma unroll
     for (int q = 0; q < GPW; ++q) goff_src[q] = dma_src_offset<WN>(wave * GPW + q, lane, a.g_rs);
-    const __bf16* xbase = a.x + group * a.x_gs + (long)(a.x_row0 + tap) * a.x_rs + ci_tile * TCI;
-    const __bf16* gbase = a.g + group * a.g_gs + (long)a.g_row0 * a.g_rs + co_tile * TCO;
 
     // the tiles are requested in step order: the sources advance by pointer increments (one 64-row chunk down, or on to
     // the next utterance) instead of a per-step "step -> (utterance, chunk)" division and 64-bit multiplies -- with one
@@ -146,8 +195,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void wgrad_t
     const long x_step = (long)TK * a.x_rs, g_step = (long)TK * a.g_rs;
     const long x_wrap = (long)a.x_bs - (long)(a.t_chunks - 1) * x_step;
     const long g_wrap = (long)a.g_bs - (long)(a.t_chunks - 1) * g_step;
-    const __bf16* xs_r = xbase + (long)b_begin * a.x_bs;
-    const __bf16* gs_r = gbase + (long)b_begin * a.g_bs;
+    const __bf16* xs_r = t.x_src(a, TCI);
+    const __bf16* gs_r = t.g_src(a, TCO);
     int tc_r = 0;
     auto stage = [&](int buf) {
         char* xl = smem + buf * STAGE_BYTES + (wave * XPW) * 1024;
@@ -174,10 +223,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void wgrad_t
     }
 
     f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     const unsigned lds0 = (unsigned)(size_t)smem;
     // One 64-row step = 2 k-halves x 2 channel-halves = 4 quarters of 8 MFMAs; the fragments of the next quarter are
@@ -245,16 +291,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void wgrad_t
         nxt = (nxt + 1 == STAGES) ? 0 : nxt + 1;
     }
 
-    // ---- store: lane holds co = co_base + jn*16 + g*4 + {0..3} for ci = ci_base + it*16 + (lane & 15)
-    float* out = a.splits > 1 ? a.out + ((long)group * a.splits + split) * a.split_stride : a.out + group * a.dw_gs;
-    const int ci_base = ci_tile * TCI + wm * 64 + (lane & 15);
-    const int co_base = co_tile * TCO + wn * 64 + g * 4;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const long row = ((long)tap * a.cin + ci_base + it * 16) * a.cout;
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) *(f32x4*)(out + row + co_base + jn * 16) = acc[jn][it];
-    }
+    store_tn_tile(a, t, acc, TCI, TCO, wm, wn, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -315,361 +352,313 @@ struct TrPhase<KK, NQ, NQ> {
                                                const unsigned (&)[8], const Hook&) {}
 };
 
-__global__ __launch_bounds__(512, 2) void wgrad_tn_ilv_kernel(TnArgs a) {
-    constexpr int NW = 8, STAGES = 2;
-    constexpr int TCI = 256, TCO = 256;
-    constexpr int XRB = 512, GRB = 512;
-    constexpr int X_BYTES = TK * XRB;
-    constexpr int STAGE_BYTES = TK * (XRB + GRB);
-    constexpr int XPW = 32 / NW, GPW = 32 / NW;  // 1-KiB DMA instructions per wave per stage and operand
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+// ---- the pieces the three 8-wave kernels below are made of
+// wave w holds the 128 (input channels) x 64 (output channels) patch (w >> 2, w & 3) of the 256 x 256 tile
+struct IlvWave {
+    int wave, wm, wn;
+};
+template <bool PRIO_YOUNG>
+__device__ __forceinline__ IlvWave ilv_wave() {
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
 #if !defined(SL_NO_PRIO_YOUNG)
     // static priority for the second-dispatched half of the waves (MI355X_MICROARCH.md, "two waves per SIMD", item 4: the younger
     // wave of a SIMD loses every issue arbitration): same-box A/B of the config-3 step 2.2475 -> 2.2374 ms, three alternations
     // of the two builds, every one in favour (profiles/r05_prio_young_ab.txt)
-    if (wave >= (int)(blockDim.x >> 7)) __builtin_amdgcn_s_setprio(1);
+    if constexpr (PRIO_YOUNG)
+        if (wave >= (int)(blockDim.x >> 7)) __builtin_amdgcn_s_setprio(1);
 #endif
-    const int wm = wave >> 2;  // 128-channel block of ci
-    const int wn = wave & 3;   // 64-channel block of co
-    const int g = lane >> 4;
+    return IlvWave{wave, wave >> 2, wave & 3};
+}
+// the lane id from the hardware's mbcnt on an opaque zero: a value the compiler cannot keep alive in place of rebuilding it
+// (and not from threadIdx.x: v0 need not stay alive either)
+__device__ __forceinline__ int opaque_lane() {
+    int zero = 0;
+    asm volatile("" : "+v"(zero));
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+}
 
-    int wg = xcd_remap(blockIdx.x, a.tiles * a.splits * a.groups);
-    if (wg >= a.tiles * a.splits * a.groups) return;  // grid padding (xcd_grid)
-    const int group = wg / (a.tiles * a.splits);
-    wg -= group * (a.tiles * a.splits);
-    const int tap = wg % a.taps;
-    wg /= a.taps;
-    const int ci_tile = wg % a.ci_tiles;
-    wg /= a.ci_tiles;
-    const int co_tile = wg % a.co_tiles;
-    const int split = wg / a.co_tiles;
-    const int b_begin = split * a.b_per_split;
-    int b_end = b_begin + a.b_per_split;
-    if (b_end > a.batch) b_end = a.batch;
-    const int n = (b_end - b_begin) * a.t_chunks;
+// Request stream of a [ROWS][256] + [ROWS][256] bf16 stage per LDS slot: the sources of the NEXT tile, advanced by pointer
+// increments (one ROWS-row chunk down, or on to the next utterance); past the end the last tile is requested again into a
+// dead slot.  The former per-step "step -> (utterance, chunk)" division plus 64-bit multiplies was a ~55-instruction scalar
+// clump between phase A and the barrier, executed by all eight waves at the same moment with the matrix pipe empty.
+// STRIDE: the type of the pointer increments (long; int where the host has checked that an utterance's tensor has fewer than
+// 2^31 elements and the scalar register file is full).
+template <int ROWS, typename STRIDE>
+struct TnStream {
+    static constexpr int X_BYTES = ROWS * 512;     // the activation half of a slot; the gradient half follows it
+    static constexpr int SLOT_BYTES = 2 * X_BYTES;
+    static constexpr int PW = X_BYTES / 1024 / 8;  // 1-KiB DMA instructions per wave, stage and operand
+    static constexpr int NI = 2 * PW;
+    // FRAGILE: the member order (gs_r before xs_r; in IlvRing cur and slot_delta first) is the order in which this compiler
+    // emits the scalar register copies that end a step.  It is chosen so that the step loops of the three kernels are
+    // instruction for instruction what they were when each kernel held these variables as locals; any other order computes
+    // the same but moves those copies.  Compare the loops' assembly with the previous build after touching it.
+    int xoff[PW], goff[PW];  // per-lane source offsets of this wave's DMA instructions
+    const __bf16* xs_n;      // sources of the stage being requested piece by piece
+    const __bf16* gs_n;
+    unsigned xl_n, gl_n;  // LDS byte offsets of this wave's part of the slot being refilled
+    STRIDE x_step, g_step, x_wrap, g_wrap;
+    const __bf16* gs_r;  // sources of the stage begin() takes next
+    const __bf16* xs_r;
+    int tc_r, chunks, left;
+    unsigned wave_x, wave_g;
 
-    int xoff[XPW], goff_src[GPW];
+    // x0 / g0: the first stage's rows, chunk tc_begin of `chunks` per utterance; n stages in all
+    __device__ __forceinline__ void init(const __bf16* x0, const __bf16* g0, int x_rs, int g_rs, long x_bs, long g_bs,
+                                         int chunks_per_utterance, int tc_begin, int n, int wave, int lane) {
 #pragma unroll
-    for (int q = 0; q < XPW; ++q) xoff[q] = dma_src_offset<4>(wave * XPW + q, lane, a.x_rs);
+        for (int q = 0; q < PW; ++q) xoff[q] = dma_src_offset<4>(wave * PW + q, lane, x_rs);
 #pragma unroll
-    for (int q = 0; q < GPW; ++q) goff_src[q] = dma_src_offset<4>(wave * GPW + q, lane, a.g_rs);
-    const __bf16* xbase = a.x + group * a.x_gs + (long)(a.x_row0 + tap) * a.x_rs + ci_tile * TCI;
-    const __bf16* gbase = a.g + group * a.g_gs + (long)a.g_row0 * a.g_rs + co_tile * TCO;
-
-    // Request stream: sources of the NEXT tile, advanced by pointer increments (one 64-row chunk down, or on to the
-    // next utterance); past the end the last tile is requested again into a dead slot.  The former per-step
-    // "step -> (utterance, chunk)" division plus 64-bit multiplies was a ~55-instruction scalar clump between phase A
-    // and the barrier, executed by all eight waves at the same moment with the matrix pipe empty.
-    const __bf16* xs_n = nullptr;
-    const __bf16* gs_n = nullptr;
-    unsigned xl_n = 0, gl_n = 0;  // LDS byte offsets of this wave's part of the slot being refilled
-    const long x_step = (long)TK * a.x_rs, g_step = (long)TK * a.g_rs;
-    const long x_wrap = (long)a.x_bs - (long)(a.t_chunks - 1) * x_step;
-    const long g_wrap = (long)a.g_bs - (long)(a.t_chunks - 1) * g_step;
-    const __bf16* xs_r = xbase + (long)b_begin * a.x_bs;
-    const __bf16* gs_r = gbase + (long)b_begin * a.g_bs;
-    int tc_r = 0, left = n;
-    const unsigned wave_x = (wave * XPW) * 1024, wave_g = X_BYTES + (wave * GPW) * 1024;
-    auto begin_stage = [&](int buf) {
+        for (int q = 0; q < PW; ++q) goff[q] = dma_src_offset<4>(wave * PW + q, lane, g_rs);
+        chunks = chunks_per_utterance;
+        xs_n = nullptr;
+        gs_n = nullptr;
+        xl_n = 0;
+        gl_n = 0;
+        x_step = (STRIDE)ROWS * x_rs;
+        g_step = (STRIDE)ROWS * g_rs;
+        x_wrap = (STRIDE)x_bs - (STRIDE)(chunks - 1) * x_step;
+        g_wrap = (STRIDE)g_bs - (STRIDE)(chunks - 1) * g_step;
+        xs_r = x0;
+        gs_r = g0;
+        tc_r = tc_begin;
+        left = n;
+        wave_x = (wave * PW) * 1024;
+        wave_g = X_BYTES + (wave * PW) * 1024;
+    }
+    __device__ __forceinline__ void begin(int slot) {
         xs_n = xs_r;
         gs_n = gs_r;
-        xl_n = buf * STAGE_BYTES + wave_x;
-        gl_n = buf * STAGE_BYTES + wave_g;
+        xl_n = slot * SLOT_BYTES + wave_x;
+        gl_n = slot * SLOT_BYTES + wave_g;
         const bool more = left > 1;
-        const bool wrap = tc_r + 1 == a.t_chunks;
-        long dx = wrap ? x_wrap : x_step;
-        long dg = wrap ? g_wrap : g_step;
-        dx = more ? dx : 0L;
-        dg = more ? dg : 0L;
+        const bool wrap = tc_r + 1 == chunks;
+        STRIDE dx = wrap ? x_wrap : x_step;
+        STRIDE dg = wrap ? g_wrap : g_step;
+        dx = more ? dx : (STRIDE)0;
+        dg = more ? dg : (STRIDE)0;
         xs_r += dx;
         gs_r += dg;
         tc_r = wrap ? 0 : tc_r + 1;
         left = more ? left - 1 : left;
-    };
-    auto dma_piece = [&](auto q_c) {
-        constexpr int Q = decltype(q_c)::value;
+    }
+    // begin() whose results are pinned into scalar registers where it stands (in the shadow of an MFMA group)
+    __device__ __forceinline__ void pin(int slot) {
+        begin(slot);
+        asm volatile("" : "+s"(xs_n), "+s"(gs_n), "+s"(xl_n), "+s"(gl_n), "+s"(xs_r), "+s"(gs_r));
+    }
+    // request Q of the NI of the stage begun last (Q >= NI: none)
+    template <int Q>
+    __device__ __forceinline__ void piece(char* lds) const {
 #if !defined(SL_WGRAD_PROBE_NO_DMA)
-        if constexpr (Q < XPW)
-            glds16(xs_n + xoff[Q], smem + xl_n + Q * 1024);
-        else if constexpr (Q < XPW + GPW)
-            glds16(gs_n + goff_src[Q - XPW], smem + gl_n + (Q - XPW) * 1024);
+        if constexpr (Q < PW)
+            glds16(xs_n + xoff[Q], lds + xl_n + Q * 1024);
+        else if constexpr (Q < NI)
+            glds16(gs_n + goff[Q - PW], lds + gl_n + (Q - PW) * 1024);
 #endif
-    };
-    const int i16 = lane & 15;
-    const int rkey = (i16 >> 2) | ((g & 1) << 2);
-    const int rrow = g * 8 + (i16 >> 2);
-    const unsigned lds0 = (unsigned)(size_t)smem;
-    unsigned xrel[8], grel[4];  // read offsets inside a stage (k-half 0)
+    }
+    // the prologue: the first N stages into slots 0 .. N-1, whole
+    template <int N>
+    __device__ __forceinline__ void request_slots(char* lds) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) xrel[j] = rrow * XRB + (((wm * 8 + j) ^ rkey) * 32) + (i16 & 3) * 8;
+        for (int i = 0; i < N; ++i) {
+            begin(i);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) grel[j] = X_BYTES + rrow * GRB + (((wn * 4 + j) ^ rkey) * 32) + (i16 & 3) * 8;
-
-    f32x4 acc[4][8];
+            for (int q = 0; q < PW; ++q) glds16(xs_n + xoff[q], lds + xl_n + q * 1024);
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    if (n > 0) {
-#pragma unroll
-        for (int i = 0; i < STAGES; ++i) {
-            begin_stage(i);
-#pragma unroll
-            for (int q = 0; q < XPW; ++q) glds16(xs_n + xoff[q], smem + xl_n + q * 1024);
-#pragma unroll
-            for (int q = 0; q < GPW; ++q) glds16(gs_n + goff_src[q], smem + gl_n + q * 1024);
+            for (int q = 0; q < PW; ++q) glds16(gs_n + goff[q], lds + gl_n + q * 1024);
         }
-        wait_vmcnt<(XPW + GPW) * (STAGES - 1)>();
+    }
+};
+
+// Transpose-read addresses of wave (wm, wn) in the slot being read (k-half 0; TrPhase adds the k-half as an offset).
+// lane (g, i): row = kk*32 + g*8 + h*4 + (i>>2); 8-B piece (i&3) of 16-column block c16
+struct TrAddr {
+    unsigned ga[4], xa[8];
+    __device__ __forceinline__ void init(unsigned lds0, int x_bytes, int wm, int wn, int lane) {
+        const int g = lane >> 4, i16 = lane & 15;
+        const int rkey = (i16 >> 2) | ((g & 1) << 2);
+        const int rrow = g * 8 + (i16 >> 2);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ga[j] = lds0 + x_bytes + rrow * 512 + (((wn * 4 + j) ^ rkey) * 32) + (i16 & 3) * 8;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) xa[j] = lds0 + rrow * 512 + (((wm * 8 + j) ^ rkey) * 32) + (i16 & 3) * 8;
+    }
+    __device__ __forceinline__ void first_reads(TrFrags& f) const {  // the twelve reads no phase issues
+#pragma unroll
+        for (int j = 0; j < 4; ++j) tr_read8<0, 512>(f.gl[j], f.gh[j], ga[j]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) tr_read8<0, 512>(f.xl[j], f.xh[j], xa[j]);
+    }
+    __device__ __forceinline__ void move_g(int delta) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ga[j] += delta;
+        asm volatile("" : "+v"(ga[0]), "+v"(ga[1]), "+v"(ga[2]), "+v"(ga[3]));
+    }
+    __device__ __forceinline__ void move_x(int j0, int delta) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) xa[j0 + j] += delta;
+        asm volatile("" : "+v"(xa[j0]), "+v"(xa[j0 + 1]), "+v"(xa[j0 + 2]), "+v"(xa[j0 + 3]));
+    }
+    // hook of MFMA group Q of a phase whose own twelve reads are out after group 11: groups 12-14 move the addresses
+    template <int Q>
+    __device__ __forceinline__ void moved(int delta) {
+        if constexpr (Q == 12) move_g(delta);
+        if constexpr (Q == 13) move_x(0, delta);
+        if constexpr (Q == 14) move_x(4, delta);
+    }
+};
+
+// The 2-slot ring of 64-row steps (wgrad_tn_ilv_kernel and, per item, wgrad_tn_ilv_multi_kernel):
+//     ring.begin(...); for (i < n) ring.step(...); ring.finish(...);
+// begin: the first two tiles requested, the first landed, its k-half 0 being read.  step: phase A (k-half 0 multiplies, k-half
+// 1 is read), barrier, phase B (k-half 1 multiplies, the next tile's k-half 0 is read, the tile after it is requested).
+struct IlvRing {
+    int cur;
+    int slot_delta;  // byte distance from the slot phase A reads to the slot phase B (and the next phase A) reads
+    TrFrags f0, f1;
+    TrAddr r;
+    template <typename Stream>
+    __device__ __forceinline__ void begin(Stream& s, char* smem, const IlvWave& w, int lane) {
+        s.template request_slots<2>(smem);
+        wait_vmcnt<Stream::NI>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        TrFrags f0, f1;
-        unsigned ga[4], xa[8];  // fragment read addresses in the slot being read (k-half 0)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ga[j] = lds0 + grel[j];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xa[j] = lds0 + xrel[j];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tr_read8<0, GRB>(f0.gl[j], f0.gh[j], ga[j]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) tr_read8<0, XRB>(f0.xl[j], f0.xh[j], xa[j]);
-        int cur = 0;
-        int slot_delta = 0;  // byte distance from the slot phase A reads to the slot phase B (and the next phase A) reads
-        // Phase A carries, in the shadow of its MFMA groups: the request-stream arithmetic (group 1) and, once its own
-        // twelve fragment reads are out (groups 12-14), the move of the read addresses to the other slot.
-        auto pin_stage = [&]() {
-            begin_stage(cur);
-            asm volatile("" : "+s"(xs_n), "+s"(gs_n), "+s"(xl_n), "+s"(gl_n), "+s"(xs_r), "+s"(gs_r));
-        };
-        auto move_g = [&]() {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ga[j] += slot_delta;
-            asm volatile("" : "+v"(ga[0]), "+v"(ga[1]), "+v"(ga[2]), "+v"(ga[3]));
-        };
-        auto move_x = [&](int j0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xa[j0 + j] += slot_delta;
-            asm volatile("" : "+v"(xa[j0]), "+v"(xa[j0 + 1]), "+v"(xa[j0 + 2]), "+v"(xa[j0 + 3]));
-        };
-        auto hook_a = [&](auto q_c) {
-            constexpr int Q = decltype(q_c)::value;
-            if constexpr (Q == 1) pin_stage();
-            if constexpr (Q == 12) move_g();
-            if constexpr (Q == 13) move_x(0);
-            if constexpr (Q == 14) move_x(4);
-        };
+        r.init((unsigned)(size_t)smem, Stream::X_BYTES, w.wm, w.wn, lane);
+        r.first_reads(f0);
+        cur = 0;
+        slot_delta = 0;
 #if defined(SL_PROBE_SKEW)
         // TIMING PROBE (wrong results by construction): the second-dispatched half of
         // the waves runs ONE PHASE behind the first -- a barrier per phase instead of one per step, so that in every phase
         // one wave of a SIMD issues MFMAs on fragments it holds while the other issues its fragment reads / requests.  The
         // data hazards a real version would have to solve (requests into a slot the other half still reads: the request
         // stream split by k-half) are ignored here: same instruction stream, same bytes, the timing of the skewed loop.
-        if (wave >= 4) __builtin_amdgcn_s_barrier();
+        if (w.wave >= 4) __builtin_amdgcn_s_barrier();
 #endif
-        for (int i = 0; i < n; ++i) {
-            const int nxt = cur ^ 1;
-            slot_delta = (nxt - cur) * STAGE_BYTES;
-            wait_trfrags(f0);
-            TrPhase<1, 0, 16>::run(acc, f0, f1, ga, xa, hook_a);  // k-half 0 multiplies, k-half 1 is read
-            wait_trfrags(f1);  // my reads of slot cur are complete
+    }
+    template <typename Stream>
+    __device__ __forceinline__ void step(f32x4 (&acc)[4][8], Stream& s, char* smem) {
+        // Phase A carries, in the shadow of its MFMA groups: the request-stream arithmetic (group 1) and, once its own
+        // twelve fragment reads are out (groups 12-14), the move of the read addresses to the other slot.
+        auto hook_a = [&](auto q_c) {
+            constexpr int Q = decltype(q_c)::value;
+            if constexpr (Q == 1) s.pin(cur);
+            r.template moved<Q>(slot_delta);
+        };
+        // Phase B: after the barrier one request of the next tile rides behind each of its first eight MFMA groups
+        auto hook_b = [&](auto q_c) { s.template piece<decltype(q_c)::value>(smem); };
+        const int nxt = cur ^ 1;
+        slot_delta = (nxt - cur) * Stream::SLOT_BYTES;
+        wait_trfrags(f0);
+        TrPhase<1, 0, 16>::run(acc, f0, f1, r.ga, r.xa, hook_a);  // k-half 0 multiplies, k-half 1 is read
+        wait_trfrags(f1);  // my reads of slot cur are complete
 #if defined(SL_PROBE_SKEW)
-            __builtin_amdgcn_s_barrier();
-            wait_vmcnt<0>();
+        __builtin_amdgcn_s_barrier();
+        wait_vmcnt<0>();
 #else
-            wait_vmcnt<0>();   // tile i+1 has landed (2-slot ring)
-            __builtin_amdgcn_s_barrier();
+        wait_vmcnt<0>();   // tile i+1 has landed (2-slot ring)
+        __builtin_amdgcn_s_barrier();
 #endif
-            asm volatile("" ::: "memory");
-            TrPhase<0, 0, 16>::run(acc, f1, f0, ga, xa, dma_piece);  // k-half 1 multiplies, next tile's k-half 0 is read
+        asm volatile("" ::: "memory");
+        TrPhase<0, 0, 16>::run(acc, f1, f0, r.ga, r.xa, hook_b);  // k-half 1 multiplies, next tile's k-half 0 is read
 #if defined(SL_PROBE_SKEW)
-            __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
 #endif
-            cur = nxt;
-        }
+        cur = nxt;
+    }
+    __device__ __forceinline__ void finish(const IlvWave& w) {
 #if defined(SL_PROBE_SKEW)
-        if (wave < 4) __builtin_amdgcn_s_barrier();
+        if (w.wave < 4) __builtin_amdgcn_s_barrier();
 #endif
         wait_vmcnt<0>();   // the surplus requests still target this work-group's LDS
         wait_trfrags(f0);  // ... and the surplus fragment reads these registers
     }
+};
 
-    // ---- store: lane holds co = co_base + jn*16 + g*4 + {0..3} for ci = ci_base + it*16 + (lane & 15)
-    float* out = a.splits > 1 ? a.out + ((long)group * a.splits + split) * a.split_stride : a.out + group * a.dw_gs;
-    const int ci_base = ci_tile * TCI + wm * 128 + (lane & 15);
-    const int co_base = co_tile * TCO + wn * 64 + g * 4;
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-        const long row = ((long)tap * a.cin + ci_base + it * 16) * a.cout;
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) *(f32x4*)(out + row + co_base + jn * 16) = acc[jn][it];
+// 2-slot ring of 64-frame steps (cfg stages 10): a TnArgs tile (TnTile) through IlvRing.
+__global__ __launch_bounds__(512, 2) void wgrad_tn_ilv_kernel(TnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x & 63;
+    const IlvWave w = ilv_wave<true>();
+    TnTile t;
+    if (!t.decode(a)) return;
+    const int n = t.nb * a.t_chunks;
+    TnStream<TK, long> s;
+    s.init(t.x_src(a, 256), t.g_src(a, 256), a.x_rs, a.g_rs, a.x_bs, a.g_bs, a.t_chunks, 0, n, w.wave, lane);
+    f32x4 acc[4][8];
+    zero_acc(acc);
+    if (n > 0) {
+        IlvRing ring;
+        ring.begin(s, smem, w, lane);
+        for (int i = 0; i < n; ++i) ring.step(acc, s, smem);
+        ring.finish(w);
     }
+    store_tn_tile(a, t, acc, 256, 256, w.wm, w.wn, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // Deep-ring variant of the interleaved kernel (cfg stages 11): 32-frame stages, FOUR LDS slots of 32 KB, one barrier per
-// stage.  Same tile (256 x 256, eight waves of 128 x 64), same fragment reads, same MFMA order inside a stage; what changes
-// is the distance between a tile's request and its first read: three stages (~2 us) instead of one 64-frame step (~1.3 us).
+// stage.  Tile, waves, request stream (TnStream), read addresses (TrAddr) and the MFMA order inside a stage (TrPhase) are
+// those of wgrad_tn_ilv_kernel; its own is the loop: one phase per stage instead of two per step, and with it the distance
+// between a tile's request and its first read: three stages (~2 us) instead of one 64-frame step (~1.3 us).
 // The launches whose operand tiles are new data at every step (big_conv_2, the inner layers: each tile is shared by only
 // 4-8 work-groups of an XCD, so a step's tiles are compulsory L2 misses) wait for exactly that with the 2-slot ring:
 // PMC (profiles/r03_pmc_wgrad_*.json) MFMA pipe busy 59 % / 53 % against 71 % for big_conv_1, whose operands stay in L2.
 //   phase(j): MFMAs of stage j from registers | fragment reads of stage j + 1 | requests of stage j + 4 into slot j % 4
 //   barrier(j + 1): stage j + 2 landed (vmcnt: two younger stages may stay in flight), everybody done reading slot (j+1) % 4
 __global__ __launch_bounds__(512, 2) void wgrad_tn_ilv32_kernel(TnArgs a) {
-    constexpr int NW = 8, SLOTS = 4, TS = 32;
-    constexpr int TCI = 256, TCO = 256;
-    constexpr int XRB = 512, GRB = 512;
-    constexpr int X_BYTES = TS * XRB;               // 16 KB
-    constexpr int STAGE_BYTES = TS * (XRB + GRB);   // 32 KB
-    constexpr int XPW = 16 / NW, GPW = 16 / NW;     // 1-KiB DMA instructions per wave, stage and operand
-    constexpr int NI = XPW + GPW;
+    constexpr int SLOTS = 4;
+    using Stream = TnStream<32, long>;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if !defined(SL_NO_PRIO_YOUNG)
-    // static priority for the second-dispatched half of the waves (MI355X_MICROARCH.md, "two waves per SIMD", item 4: the younger
-    // wave of a SIMD loses every issue arbitration): same-box A/B of the config-3 step 2.2475 -> 2.2374 ms, three alternations
-    // of the two builds, every one in favour (profiles/r05_prio_young_ab.txt)
-    if (wave >= (int)(blockDim.x >> 7)) __builtin_amdgcn_s_setprio(1);
-#endif
-    const int wm = wave >> 2;
-    const int wn = wave & 3;
-    const int g = lane >> 4;
-
-    int wg = xcd_remap(blockIdx.x, a.tiles * a.splits * a.groups);
-    if (wg >= a.tiles * a.splits * a.groups) return;
-    const int group = wg / (a.tiles * a.splits);
-    wg -= group * (a.tiles * a.splits);
-    const int tap = wg % a.taps;
-    wg /= a.taps;
-    const int ci_tile = wg % a.ci_tiles;
-    wg /= a.ci_tiles;
-    const int co_tile = wg % a.co_tiles;
-    const int split = wg / a.co_tiles;
-    const int b_begin = split * a.b_per_split;
-    int b_end = b_begin + a.b_per_split;
-    if (b_end > a.batch) b_end = a.batch;
-    const int tc32 = 2 * a.t_chunks;             // 32-frame stages per utterance
-    const int n = (b_end - b_begin) * tc32;      // stages of this work-group (even)
-
-    int xoff[XPW], goff_src[GPW];
-#pragma unroll
-    for (int q = 0; q < XPW; ++q) xoff[q] = dma_src_offset<4>(wave * XPW + q, lane, a.x_rs);
-#pragma unroll
-    for (int q = 0; q < GPW; ++q) goff_src[q] = dma_src_offset<4>(wave * GPW + q, lane, a.g_rs);
-    const __bf16* xbase = a.x + group * a.x_gs + (long)(a.x_row0 + tap) * a.x_rs + ci_tile * TCI;
-    const __bf16* gbase = a.g + group * a.g_gs + (long)a.g_row0 * a.g_rs + co_tile * TCO;
-
-    const __bf16* xs_n = nullptr;
-    const __bf16* gs_n = nullptr;
-    unsigned xl_n = 0, gl_n = 0;
-    const long x_step = (long)TS * a.x_rs, g_step = (long)TS * a.g_rs;
-    const long x_wrap = (long)a.x_bs - (long)(tc32 - 1) * x_step;
-    const long g_wrap = (long)a.g_bs - (long)(tc32 - 1) * g_step;
-    const __bf16* xs_r = xbase + (long)b_begin * a.x_bs;
-    const __bf16* gs_r = gbase + (long)b_begin * a.g_bs;
-    int tc_r = 0, left = n;
-    const unsigned wave_x = (wave * XPW) * 1024, wave_g = X_BYTES + (wave * GPW) * 1024;
-    auto begin_stage = [&](int slot) {
-        xs_n = xs_r;
-        gs_n = gs_r;
-        xl_n = slot * STAGE_BYTES + wave_x;
-        gl_n = slot * STAGE_BYTES + wave_g;
-        const bool more = left > 1;
-        const bool wrap = tc_r + 1 == tc32;
-        long dx = wrap ? x_wrap : x_step;
-        long dg = wrap ? g_wrap : g_step;
-        dx = more ? dx : 0L;
-        dg = more ? dg : 0L;
-        xs_r += dx;
-        gs_r += dg;
-        tc_r = wrap ? 0 : tc_r + 1;
-        left = more ? left - 1 : left;
-    };
-    auto dma_piece = [&](auto q_c) {
-        constexpr int Q = decltype(q_c)::value;
-        if constexpr (Q < XPW)
-            glds16(xs_n + xoff[Q], smem + xl_n + Q * 1024);
-        else if constexpr (Q < XPW + GPW)
-            glds16(gs_n + goff_src[Q - XPW], smem + gl_n + (Q - XPW) * 1024);
-    };
-    const int i16 = lane & 15;
-    const int rkey = (i16 >> 2) | ((g & 1) << 2);
-    const int rrow = g * 8 + (i16 >> 2);
-    const unsigned lds0 = (unsigned)(size_t)smem;
-
+    const int lane = threadIdx.x & 63;
+    const IlvWave w = ilv_wave<true>();
+    TnTile t;
+    if (!t.decode(a)) return;
+    const int tc32 = 2 * a.t_chunks;  // 32-frame stages per utterance
+    const int n = t.nb * tc32;        // stages of this work-group (even)
+    Stream s;
+    s.init(t.x_src(a, 256), t.g_src(a, 256), a.x_rs, a.g_rs, a.x_bs, a.g_bs, tc32, 0, n, w.wave, lane);
     f32x4 acc[4][8];
 #pragma unroll
+    // (its own copy, not zero_acc: through the helper the compiler orders this kernel's first MFMA group differently -- a
+    // request and an MFMA change places -- and the loop is kept as it was)
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     if (n > 0) {
-#pragma unroll
-        for (int i = 0; i < SLOTS; ++i) {
-            begin_stage(i);
-#pragma unroll
-            for (int q = 0; q < XPW; ++q) glds16(xs_n + xoff[q], smem + xl_n + q * 1024);
-#pragma unroll
-            for (int q = 0; q < GPW; ++q) glds16(gs_n + goff_src[q], smem + gl_n + q * 1024);
-        }
-        wait_vmcnt<NI*(SLOTS - 1)>();  // stage 0
+        s.request_slots<SLOTS>(smem);
+        wait_vmcnt<Stream::NI*(SLOTS - 1)>();  // stage 0
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         TrFrags f0, f1;
-        unsigned ga[4], xa[8];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ga[j] = lds0 + X_BYTES + rrow * GRB + (((wn * 4 + j) ^ rkey) * 32) + (i16 & 3) * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xa[j] = lds0 + rrow * XRB + (((wm * 8 + j) ^ rkey) * 32) + (i16 & 3) * 8;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tr_read8<0, GRB>(f0.gl[j], f0.gh[j], ga[j]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) tr_read8<0, XRB>(f0.xl[j], f0.xh[j], xa[j]);
+        TrAddr r;
+        r.init((unsigned)(size_t)smem, Stream::X_BYTES, w.wm, w.wn, lane);
+        r.first_reads(f0);
         // the read addresses point at the slot read NEXT (stage 1); every phase moves them one slot on behind its reads
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ga[j] += STAGE_BYTES;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xa[j] += STAGE_BYTES;
+        r.move_g(Stream::SLOT_BYTES);
+        r.move_x(0, Stream::SLOT_BYTES);
+        r.move_x(4, Stream::SLOT_BYTES);
         int rd = 1;           // slot the next phase reads
         int slot_delta = 0;   // set per phase: distance to the slot after that
         int rq = 0;           // slot the next phase refills (= the slot of the stage it multiplies)
-        auto pin_stage = [&]() {
-            begin_stage(rq);
-            asm volatile("" : "+s"(xs_n), "+s"(gs_n), "+s"(xl_n), "+s"(gl_n), "+s"(xs_r), "+s"(gs_r));
-        };
-        auto move_g = [&]() {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ga[j] += slot_delta;
-            asm volatile("" : "+v"(ga[0]), "+v"(ga[1]), "+v"(ga[2]), "+v"(ga[3]));
-        };
-        auto move_x = [&](int j0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xa[j0 + j] += slot_delta;
-            asm volatile("" : "+v"(xa[j0]), "+v"(xa[j0 + 1]), "+v"(xa[j0 + 2]), "+v"(xa[j0 + 3]));
-        };
-        // groups 0 .. 3 of a phase: one request each (the stage's four instructions of this wave); group 4: the request
-        // stream's arithmetic for the NEXT phase; groups 12 .. 14: the read addresses move on (their twelve reads are out)
+        // groups 0 .. 3 of a phase: one request each (the stage's four instructions of this wave); groups 12 .. 14: the read
+        // addresses move on (their twelve reads are out)
         auto hook = [&](auto q_c) {
             constexpr int Q = decltype(q_c)::value;
-            dma_piece(q_c);
-            if constexpr (Q == 12) move_g();
-            if constexpr (Q == 13) move_x(0);
-            if constexpr (Q == 14) move_x(4);
+            s.piece<Q>(smem);
+            r.moved<Q>(slot_delta);
         };
         auto phase = [&](TrFrags& cur, TrFrags& nxt) {
             wait_trfrags(cur);
-            wait_vmcnt<NI * 2>();  // the stage the reads below address has landed; the two younger ones stay in flight
+            wait_vmcnt<Stream::NI * 2>();  // the stage the reads below address has landed; the two younger ones stay in flight
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            slot_delta = rd == SLOTS - 1 ? -(SLOTS - 1) * STAGE_BYTES : STAGE_BYTES;
-            pin_stage();  // requests of this phase go to slot rq
-            TrPhase<0, 0, 16>::run(acc, cur, nxt, ga, xa, hook);
+            slot_delta = rd == SLOTS - 1 ? -(SLOTS - 1) * Stream::SLOT_BYTES : Stream::SLOT_BYTES;
+            s.pin(rq);  // requests of this phase go to slot rq
+            TrPhase<0, 0, 16>::run(acc, cur, nxt, r.ga, r.xa, hook);
             rd = rd == SLOTS - 1 ? 0 : rd + 1;
             rq = rq == SLOTS - 1 ? 0 : rq + 1;
         };
@@ -680,38 +669,7 @@ __global__ __launch_bounds__(512, 2) void wgrad_tn_ilv32_kernel(TnArgs a) {
         wait_vmcnt<0>();   // the surplus requests still target this work-group's LDS
         wait_trfrags(f0);  // ... and the surplus fragment reads these registers
     }
-
-    float* out = a.splits > 1 ? a.out + ((long)group * a.splits + split) * a.split_stride : a.out + group * a.dw_gs;
-    const int ci_base = ci_tile * TCI + wm * 128 + (lane & 15);
-    const int co_base = co_tile * TCO + wn * 64 + g * 4;
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-        const long row = ((long)tap * a.cin + ci_base + it * 16) * a.cout;
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn) *(f32x4*)(out + row + co_base + jn * 16) = acc[jn][it];
-    }
-}
-
-int launch_ilv32(const TnArgs& a, hipStream_t s) {
-    constexpr int LDS_BYTES = 4 * 32 * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_tn_ilv32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        attr_set = true;
-    }
-    SL_LAUNCH_MAIN(wgrad_tn_ilv32_kernel, dim3(xcd_grid(a.tiles * a.splits * a.groups)), dim3(512), LDS_BYTES, s, a);
-    return sl_check_launch("sl_conv1d_wgrad(bf16, interleaved, 4-slot ring)");
-}
-
-int launch_ilv(const TnArgs& a, hipStream_t s) {
-    constexpr int LDS_BYTES = 2 * TK * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_tn_ilv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        attr_set = true;
-    }
-    SL_LAUNCH_MAIN(wgrad_tn_ilv_kernel, dim3(xcd_grid(a.tiles * a.splits * a.groups)), dim3(512), LDS_BYTES, s, a);
-    return sl_check_launch("sl_conv1d_wgrad(bf16, interleaved)");
+    store_tn_tile(a, t, acc, 256, 256, w.wm, w.wn, lane);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -726,8 +684,8 @@ int launch_ilv(const TnArgs& a, hipStream_t s) {
 // operand tiles in the XCD's L2.  (A first version cut the concatenated (tile, step) sequence into equal ranges,
 // "stream-K": balanced too, but neighbouring work-groups then sit at unrelated frames, nothing is shared and the launch
 // became bandwidth-bound: 2.1 us per step instead of 1.4.)  Every item's partial tile goes to its own slot and one
-// table-free reduction launch adds a tile's slots in a fixed order (deterministic).  The step loop is the interleaved
-// 8-wave loop of wgrad_tn_ilv_kernel, unchanged.
+// table-free reduction launch adds a tile's slots in a fixed order (deterministic).  An item's steps run through IlvRing,
+// as wgrad_tn_ilv_kernel's do; this kernel's own are the item decode, the 32-bit strides and the slot the tile is stored to.
 constexpr int MULTI_MAX_JOBS = 16;
 struct MultiJob {
     const __bf16* x;
@@ -750,21 +708,14 @@ struct MultiArgs {
 __device__ __forceinline__ int multi_seg_begin(const MultiArgs& a, int p) { return (int)((long)a.spt * p / a.segs); }
 
 __global__ __launch_bounds__(512, 2) void wgrad_tn_ilv_multi_kernel(MultiArgs a) {
-    constexpr int NW = 8, STAGES = 2;
-    constexpr int XRB = 512, GRB = 512;
-    constexpr int X_BYTES = TK * XRB;
-    constexpr int STAGE_BYTES = TK * (XRB + GRB);
-    constexpr int XPW = 32 / NW, GPW = 32 / NW;
-
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-    const int wm = wave >> 2;
-    const int wn = wave & 3;
+    const IlvWave w = ilv_wave<false>();
 
     if (xcd_remap(blockIdx.x, a.workers) >= a.workers) return;  // grid padding (xcd_grid)
-    const unsigned lds0 = (unsigned)(size_t)smem;
-    const unsigned wave_x = (wave * XPW) * 1024, wave_g = X_BYTES + (wave * GPW) * 1024;
 
+    // (not to be unrolled: with the read addresses in TrAddr the compiler otherwise unrolls the two items into two copies
+    // of the step loop, with another register allocation than the one this kernel's budget was fitted to)
+#pragma unroll 1
     for (int item = 0; item < 2; ++item) {
         // ---- this work-group's item: one or two per work-group, derived from the block id again for the second one (all
         // wave-uniform and pinned into scalar registers; kept live across the step loop they would not fit: this kernel
@@ -776,15 +727,10 @@ __global__ __launch_bounds__(512, 2) void wgrad_tn_ilv_multi_kernel(MultiArgs a)
         const int k0 = __builtin_amdgcn_readfirstlane(pair ? ws / a.total_tiles : 0);
         const int off = __builtin_amdgcn_readfirstlane(multi_seg_begin(a, pair ? 2 * k0 : a.segs - 1));
         const int n = __builtin_amdgcn_readfirstlane(multi_seg_begin(a, pair ? 2 * k0 + 2 : a.segs)) - off;
-        // Lane-derived values are rebuilt per item (and once more for the epilogue) from an opaque copy of the thread id:
-        // hoisted out of the item loop they would stay live across the step loop, which has two registers to spare.
-        int zero_i = 0;  // (the lane id from the hardware's mbcnt, not from threadIdx.x: v0 need not stay alive either)
-        asm volatile("" : "+v"(zero_i));
-        const int lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero_i));
-        const int g = lane >> 4;
-        const int i16 = lane & 15;
-        const int rkey = (i16 >> 2) | ((g & 1) << 2);
-        const int rrow = g * 8 + (i16 >> 2);
+        // Lane-derived values (the request stream's source offsets, the read addresses inside IlvRing) are rebuilt per item,
+        // and the lane once more for the epilogue: hoisted out of the item loop they would stay live across the step loop,
+        // which has two registers to spare -- the read addresses alone are the twelve registers that spill.
+        const int lane = opaque_lane();
         int ji = 0;
         while (ji + 1 < a.n_jobs && tile >= a.job[ji + 1].tile_begin) ++ji;
         const MultiJob& J = a.job[ji];
@@ -795,130 +741,34 @@ __global__ __launch_bounds__(512, 2) void wgrad_tn_ilv_multi_kernel(MultiArgs a)
         const int co_tile = __builtin_amdgcn_readfirstlane(lt / J.ci_tiles);
         const int b_begin = __builtin_amdgcn_readfirstlane(off / a.t_chunks), tc_begin = off - b_begin * a.t_chunks;
         const int x_rs = J.x_rs, g_rs = J.g_rs;
-
-        int xoff[XPW], goff_src[GPW];
-#pragma unroll
-        for (int q = 0; q < XPW; ++q) xoff[q] = dma_src_offset<4>(wave * XPW + q, lane, x_rs);
-#pragma unroll
-        for (int q = 0; q < GPW; ++q) goff_src[q] = dma_src_offset<4>(wave * GPW + q, lane, g_rs);
-        // (32-bit strides: the host checks that an utterance's tensor has fewer than 2^31 elements; the scalar register
-        // file is as full as the vector one in this kernel)
-        const int x_step = TK * x_rs, g_step = TK * g_rs;
-        const int x_wrap = (int)J.x_bs - (a.t_chunks - 1) * x_step;
-        const int g_wrap = (int)J.g_bs - (a.t_chunks - 1) * g_step;
         // (a channel count that is not a multiple of 256 -- the 640-wide pair view of 257 bins -- ends with a tile that starts
         // at cin - 256 and overlaps its neighbour; the reduction writes the overlapped rows from the neighbour only)
         const int ci_start = __builtin_amdgcn_readfirstlane(min(ci_tile * 256, J.cin - 256));
-        const __bf16* xs_r = J.x + (long)(J.x_row0 + tap) * x_rs + ci_start + (long)b_begin * J.x_bs + (long)tc_begin * x_step;
-        const __bf16* gs_r = J.g + (long)J.g_row0 * g_rs + co_tile * 256 + (long)b_begin * J.g_bs + (long)tc_begin * g_step;
-        const __bf16* xs_n = nullptr;
-        const __bf16* gs_n = nullptr;
-        unsigned xl_n = 0, gl_n = 0;
-        int tc_r = tc_begin, left = n;
-        auto begin_stage = [&](int buf) {
-            xs_n = xs_r;
-            gs_n = gs_r;
-            xl_n = buf * STAGE_BYTES + wave_x;
-            gl_n = buf * STAGE_BYTES + wave_g;
-            const bool more = left > 1;
-            const bool wrap = tc_r + 1 == a.t_chunks;
-            int dx = wrap ? x_wrap : x_step;
-            int dg = wrap ? g_wrap : g_step;
-            dx = more ? dx : 0;
-            dg = more ? dg : 0;
-            xs_r += dx;
-            gs_r += dg;
-            tc_r = wrap ? 0 : tc_r + 1;
-            left = more ? left - 1 : left;
-        };
-        auto dma_piece = [&](auto q_c) {
-            constexpr int Q = decltype(q_c)::value;
-            if constexpr (Q < XPW)
-                glds16(xs_n + xoff[Q], smem + xl_n + Q * 1024);
-            else if constexpr (Q < XPW + GPW)
-                glds16(gs_n + goff_src[Q - XPW], smem + gl_n + (Q - XPW) * 1024);
-        };
+        // (32-bit strides: multi_fill checks that an utterance's tensor has fewer than 2^31 elements)
+        TnStream<TK, int> s;
+        s.init(J.x + (long)(J.x_row0 + tap) * x_rs + ci_start + (long)b_begin * J.x_bs + (long)tc_begin * (TK * x_rs),
+               J.g + (long)J.g_row0 * g_rs + co_tile * 256 + (long)b_begin * J.g_bs + (long)tc_begin * (TK * g_rs), x_rs, g_rs,
+               J.x_bs, J.g_bs, a.t_chunks, tc_begin, n, w.wave, lane);
 
         f32x4 acc[4][8];
 #pragma unroll
+        // (its own copy, not zero_acc: through the helper this kernel, at 256 VGPRs, spills 12 bytes per lane)
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
         if (item > 0) {  // the previous item's last fragment reads must be over before its slots are refilled
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
-#pragma unroll
-        for (int i = 0; i < STAGES; ++i) {
-            begin_stage(i);
-#pragma unroll
-            for (int q = 0; q < XPW; ++q) glds16(xs_n + xoff[q], smem + xl_n + q * 1024);
-#pragma unroll
-            for (int q = 0; q < GPW; ++q) glds16(gs_n + goff_src[q], smem + gl_n + q * 1024);
-        }
-        wait_vmcnt<(XPW + GPW) * (STAGES - 1)>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        TrFrags f0, f1;
-        unsigned ga[4], xa[8];  // (rebuilt per item: kept live across items they cost the twelve registers that spill)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) ga[j] = lds0 + X_BYTES + rrow * GRB + (((wn * 4 + j) ^ rkey) * 32) + (i16 & 3) * 8;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) xa[j] = lds0 + rrow * XRB + (((wm * 8 + j) ^ rkey) * 32) + (i16 & 3) * 8;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) tr_read8<0, GRB>(f0.gl[j], f0.gh[j], ga[j]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) tr_read8<0, XRB>(f0.xl[j], f0.xh[j], xa[j]);
-        int cur = 0;
-        int slot_delta = 0;
-        auto pin_stage = [&]() {
-            begin_stage(cur);
-            asm volatile("" : "+s"(xs_n), "+s"(gs_n), "+s"(xl_n), "+s"(gl_n), "+s"(xs_r), "+s"(gs_r));
-        };
-        auto move_g = [&]() {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) ga[j] += slot_delta;
-            asm volatile("" : "+v"(ga[0]), "+v"(ga[1]), "+v"(ga[2]), "+v"(ga[3]));
-        };
-        auto move_x = [&](int j0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) xa[j0 + j] += slot_delta;
-            asm volatile("" : "+v"(xa[j0]), "+v"(xa[j0 + 1]), "+v"(xa[j0 + 2]), "+v"(xa[j0 + 3]));
-        };
-        auto hook_a = [&](auto q_c) {
-            constexpr int Q = decltype(q_c)::value;
-            if constexpr (Q == 1) pin_stage();
-            if constexpr (Q == 12) move_g();
-            if constexpr (Q == 13) move_x(0);
-            if constexpr (Q == 14) move_x(4);
-        };
-        for (int i = 0; i < n; ++i) {
-            const int nxt = cur ^ 1;
-            slot_delta = (nxt - cur) * STAGE_BYTES;
-            wait_trfrags(f0);
-            TrPhase<1, 0, 16>::run(acc, f0, f1, ga, xa, hook_a);
-            wait_trfrags(f1);
-            wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            TrPhase<0, 0, 16>::run(acc, f1, f0, ga, xa, dma_piece);
-            cur = nxt;
-        }
-        wait_vmcnt<0>();
-        wait_trfrags(f0);
+        IlvRing ring;
+        ring.begin(s, smem, w, lane);
+        for (int i = 0; i < n; ++i) ring.step(acc, s, smem);
+        ring.finish(w);
 
         // ---- this item's partial tile: dense [256 ci][256 co] floats in slot (w, item)
         float* out = a.slots + ((long)__builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, a.workers)) * 2 + item) * (256 * 256);
-        int zero_e = 0;
-        asm volatile("" : "+v"(zero_e));
-        const int lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero_e));
-        const int ci_l = wm * 128 + (lane_e & 15);
-        const int co_l = wn * 64 + (lane_e >> 4) * 4;
-#pragma unroll
-        for (int it = 0; it < 8; ++it)
-#pragma unroll
-            for (int jn = 0; jn < 4; ++jn) *(f32x4*)(out + (ci_l + it * 16) * 256 + co_l + jn * 16) = acc[jn][it];
+        const int lane_e = opaque_lane();
+        store_acc(acc, out, w.wm * 128 + (lane_e & 15), w.wn * 64 + (lane_e >> 4) * 4, 256);
     }
 }
 
@@ -950,19 +800,31 @@ __global__ __launch_bounds__(256) void wgrad_multi_reduce_kernel(MultiArgs a) {
     *(f32x4*)(J.dw + ((long)tap * J.cin + ci_start + ci) * J.cout + co_tile * 256 + co) = s;
 }
 
-template <int WM, int WN, int STAGES>
-int launch(const TnArgs& a, hipStream_t s) {
-    constexpr int LDS_BYTES = STAGES * TK * 128 * (WM + WN);
+// every kernel of this file: set the LDS attribute once, launch on the XCD-padded grid, check
+template <auto KERNEL, int THREADS, int LDS_BYTES, typename ARGS>
+int launch_kernel(const ARGS& a, int work_groups, hipStream_t s, const char* what) {
     static_assert(LDS_BYTES <= 160 * 1024, "LDS ring exceeds the 160 KiB of a CU");
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_tn_bf16_kernel<WM, WN, STAGES>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
+        (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
         attr_set = true;
     }
-    SL_LAUNCH_MAIN((wgrad_tn_bf16_kernel<WM, WN, STAGES>), dim3(xcd_grid(a.tiles * a.splits * a.groups)), dim3(64 * WM * WN),
-                       LDS_BYTES, s, a);
-    return sl_check_launch("sl_conv1d_wgrad(bf16)");
+    SL_LAUNCH_MAIN(KERNEL, dim3(xcd_grid(work_groups)), dim3(THREADS), LDS_BYTES, s, a);
+    return sl_check_launch(what);
+}
+
+template <int WM, int WN, int STAGES>
+int launch(const TnArgs& a, hipStream_t s) {
+    return launch_kernel<wgrad_tn_bf16_kernel<WM, WN, STAGES>, 64 * WM * WN, STAGES * TK * 128 * (WM + WN)>(
+        a, a.tiles * a.splits * a.groups, s, "sl_conv1d_wgrad(bf16)");
+}
+int launch_ilv(const TnArgs& a, hipStream_t s) {
+    return launch_kernel<wgrad_tn_ilv_kernel, 512, 2 * TK * 1024>(a, a.tiles * a.splits * a.groups, s,
+                                                                  "sl_conv1d_wgrad(bf16, interleaved)");
+}
+int launch_ilv32(const TnArgs& a, hipStream_t s) {
+    return launch_kernel<wgrad_tn_ilv32_kernel, 512, 4 * 32 * 1024>(a, a.tiles * a.splits * a.groups, s,
+                                                                    "sl_conv1d_wgrad(bf16, interleaved, 4-slot ring)");
 }
 
 struct WCfg {
@@ -1227,14 +1089,7 @@ int wgrad_multi_bf16(const sl_wgrad_job* jobs, int n_jobs, void* ws, size_t ws_b
         return SL_ERR_WORKSPACE_TOO_SMALL;
     }
     a.slots = (float*)ws;
-    constexpr int LDS_BYTES = 2 * TK * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_tn_ilv_multi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-        attr_set = true;
-    }
-    SL_LAUNCH_MAIN(wgrad_tn_ilv_multi_kernel, dim3(xcd_grid(a.workers)), dim3(512), LDS_BYTES, s, a);
-    rc = sl_check_launch("sl_conv1d_wgrad_multi");
+    rc = launch_kernel<wgrad_tn_ilv_multi_kernel, 512, 2 * TK * 1024>(a, a.workers, s, "sl_conv1d_wgrad_multi");
     if (rc != SL_OK) return rc;
     hipLaunchKernelGGL(wgrad_multi_reduce_kernel, dim3(64, a.total_tiles), dim3(256), 0, s, a);
     return sl_check_launch("sl_conv1d_wgrad_multi(reduce)");
