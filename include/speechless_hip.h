@@ -419,6 +419,27 @@ int sl_asg_align(const float* logq, const float* trans, const float* init, const
                  const int32_t* input_len, int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- ASG forced alignment of long recordings: sl_asg_align beyond 511 graphemes.  Arguments, their order and every rule
+ *      (states, stay / move, the strict-> compare with a tie that stays, three separately rounded fp32 adds and no multiply,
+ *      end state L-1 at T_b-1, infeasible rows -- L = 0, T_b = 0, L > T_b or a score of -inf: score -inf and the whole row -1 --,
+ *      -1 past T_b, the clamping of label_len, input_len and label values, -inf entries of trans / init that never give a
+ *      NaN) are those of sl_asg_align above; score and path are bit for bit what it returns where both accept the shape, and
+ *      bit for bit the float32 restatement everywhere.
+ * Limits: 2 <= k <= 64, 1 <= l_max <= 8191, SL_ERR_UNSUPPORTED otherwise; t_out is limited by the workspace only.  A null
+ * pointer (the workspace included) is SL_ERR_INVALID_ARGUMENT, a workspace below the size asked for
+ * SL_ERR_WORKSPACE_TOO_SMALL; all of these are refused on the host before any launch, and nothing is written.
+ * One work-group per recording, 8 states per lane = 512 per wave, the waves chosen from l_max:
+ *      l_max   1..512   513..1024   1025..2048   2049..4096   4097..8191
+ *      waves      1         2            4            8           16
+ * workspace: sl_asg_align_long_workspace_bytes(batch, t_out, l_max) bytes = batch * t_out * 64 * waves: the backpointers (ONE
+ * bit per state and frame; state s at bit (s >> 3) & 63 of 64-bit word (s >> 9) * 8 + (s & 7) of its frame's row) always go to
+ * HBM.  Monotonic in t_out and l_max, 0 for arguments out of range.  All work on the caller's stream, no allocation, no
+ * synchronisation. */
+size_t sl_asg_align_long_workspace_bytes(int batch, int t_out, int l_max);
+int sl_asg_align_long(const float* logq, const float* trans, const float* init, const int32_t* labels,
+                      const int32_t* label_len, const int32_t* input_len, int32_t* path, float* score, int batch, int t_out,
+                      int k, int l_max, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- CTC beam search, optionally scored by an n-gram language model: the device twin of sl_host_ctc_beam_search
  *      (include/speechless_host.h; speechless/net.py:444-451).  The host decoder is the specification: for the same
  *      inputs the result is the same search, step for step --

@@ -155,6 +155,9 @@ SIGNATURES = {
     # logq, trans, init, labels, label_len, input_len, path, score
     "sl_asg_align": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                              c_int, c_void_p, c_size_t, c_void_p]),
+    "sl_asg_align_long_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "sl_asg_align_long": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                  c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "sl_edit_distance_supported": (c_int, [c_int, c_int]),
     "sl_edit_distance": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),

@@ -1,10 +1,10 @@
-"""Result types of forced alignment (Wav2Letter.alignment_batch / positional_label_batch under CTC, asg_alignment_batch /
-asg_positional_label_batch under ASG).
+"""Result types of forced alignment (Wav2Letter.alignment_batch / positional_label_batch / align_recording under CTC,
+asg_alignment_batch / asg_positional_label_batch / asg_align_recording under ASG).
 
 `PositionalLabel` is the reference's word-timing label (speechless/labeled_example.py:32-60): `(word, (start, end))`
 sections, which LabeledExampleFromFile.sections() (:219-234) uses to cut long recordings.  `CtcAlignment` is one
 utterance's Viterbi alignment (include/speechless_hip.h, sl_ctc_align) turned into character and word frame ranges;
-`AsgAlignment` is the same for the ASG criterion (sl_asg_align), whose path runs over the run-length-encoded label."""
+`AsgAlignment` is the same for the ASG criterion (sl_asg_align / sl_asg_align_long), whose path runs over the run-length-encoded label."""
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -109,7 +109,7 @@ class CtcAlignment(_WordTimings):
 
 
 def cut_sections(alignment, max_frames: int) -> List[Tuple[str, Tuple[int, int]]]:
-    """Cuts an aligned recording (Wav2Letter.align_recording) into sections of whole words, (text, (first, end)) in output
+    """Cuts an aligned recording (Wav2Letter.align_recording, or asg_align_recording) into sections of whole words, (text, (first, end)) in output
     frames: what LabeledExampleFromFile.sections() (labeled_example.py:219-234) needs to turn a long recording into utterances.
     Greedy: a section takes words while its last word's end - its first word's first <= max_frames; a single word longer
     than that is a section by itself.  The cut between two sections lies at the midpoint (integer floor) of the gap between
@@ -174,15 +174,27 @@ class AsgAlignment(_WordTimings):
         # first character takes the letter's range and the one or two others take the mark's
         self.character_frames = []  # type: List[Tuple[int, int]]
         if self.feasible:
-            positions = self.frame_grapheme_positions
+            # one linear pass: the path's runs of equal positions, then per grapheme the number of its runs and where its
+            # only one lies (a long recording has thousands of graphemes over tens of thousands of frames)
+            positions = self.frame_grapheme_positions.reshape(-1)
+            n = len(counts)
+            starts = np.concatenate([[0], np.flatnonzero(positions[1:] != positions[:-1]) + 1]) if positions.size else \
+                np.zeros(0, dtype=np.int64)
+            ends = np.concatenate([starts[1:], [positions.size]])
+            values = positions[starts]
+            mine = (values >= 0) & (values < n)
+            runs = np.bincount(values[mine], minlength=n)
+            first = np.full(n, -1, dtype=np.int64)
+            last = np.full(n, -1, dtype=np.int64)
+            first[values[mine][::-1]] = starts[mine][::-1]  # (reversed: the earliest run of a grapheme is written last)
+            last[values[mine][::-1]] = ends[mine][::-1]
             end = 0
             for i, (count, _) in enumerate(counts):
-                frames = np.flatnonzero(positions == i)
-                if frames.size == 0 or frames[0] != end or frames[-1] + 1 - frames[0] != frames.size:
+                if runs[i] != 1 or first[i] != end:
                     raise ValueError("alignment path does not pass grapheme {} of {!r} in one run behind grapheme {}".format(
                         i, label, i - 1))
-                end = int(frames[-1]) + 1
-                self.grapheme_frames.append((int(frames[0]), end))
+                end = int(last[i])
+                self.grapheme_frames.append((int(first[i]), end))
                 self.character_frames.extend([self.grapheme_frames[-1]] * count)
         self.word_frames = _word_frames(label, self.character_frames) if self.feasible else []
 

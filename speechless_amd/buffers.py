@@ -396,11 +396,13 @@ class _Buffers:
 
 
 class _LongAlignBuffers:
-    """Tensors of Engine.ctc_align_long, which aligns a logq tensor handed to it and so belongs to no (batch, frames) buffer
-    set: labels, lengths, the path / score results and the backpointer workspace of sl_ctc_align_long, grown only."""
+    """Tensors of Engine.ctc_align_long / asg_align_long (an engine has one criterion, so one of the two), which align a logq
+    tensor handed to them and so belong to no (batch, frames) buffer set: labels, lengths, the path / score results and the
+    backpointer workspace of sl_ctc_align_long / sl_asg_align_long (workspace_query), grown only."""
 
-    def __init__(self, device):
+    def __init__(self, device, workspace_query="sl_ctc_align_long_workspace_bytes"):
         self.device = device
+        self.workspace_query = workspace_query
         self.labels = self.label_len = self.input_len = self.score = self.path = self.ws = None
 
     def ensure(self, batch, t_out, l_max):
@@ -412,8 +414,8 @@ class _LongAlignBuffers:
             self.score = torch.zeros((batch,), dtype=torch.float32, device=dev)
         if self.path is None or self.path.numel() < batch * t_out:
             self.path = torch.zeros((batch * t_out,), dtype=torch.int32, device=dev)
-        need = lib().raw("sl_ctc_align_long_workspace_bytes")(batch, t_out, self.labels.shape[1])
+        need = lib().raw(self.workspace_query)(batch, t_out, self.labels.shape[1])
         if self.ws is None or self.ws.numel() < need:
-            self.ws = None  # (free the old one first: at the limit a recording's backpointers take 4 KB per frame)
+            self.ws = None  # (free the old one first: at the limit a recording's backpointers take 4 KB (ASG: 1 KB) per frame)
             self.ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
         return need

@@ -13,7 +13,7 @@ HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csr
 CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "misc.hip", "spectrogram.hip", "conv_chain_bf16.hip",
            "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip",
-           "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_beam.hip"]
+           "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
 # f16x3 parity path (csrc/common.h: SL_MFMA16; only the fp32 / plane-output instantiations, about a third of the bf16 build)
 F16_VARIANTS = {"conv_nt_f16": "conv_nt_bf16.hip", "wgrad_tn_f16": "wgrad_tn_bf16.hip"}
@@ -42,8 +42,10 @@ def _newest_source_mtime():
 # went through memory on every expansion of the per-frame sequential path)
 # (ctc_align_long.hip: 16 states, their columns and the 17 backtrace dwords per thread are register arrays; scratch there puts
 # memory traffic inside the per-frame barrier interval of up to 16 waves)
+# (asg_align_long.hip: 8 states, their columns and scores and the 32 backtrace dwords per thread are register arrays indexed by
+# unrolled constants; scratch there is the same traffic inside the same barrier interval)
 NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
-              "ctc_align_long.hip", "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_beam.hip"}
+              "ctc_align_long.hip", "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip"}
 
 
 def _scratch_users(remarks):
@@ -63,8 +65,10 @@ def _scratch_users(remarks):
 # (v_pk_mul_f32 out of the SLP vectorizer) costs such a wave more than the two scalar instructions it replaces
 # ctc_beam.hip: the host decoder rounds lm_weight * delta and the add separately (no FMA may form)
 # asg_align.hip: every add of the recurrence is rounded on its own (it has no multiply; the flag states the contract)
+# asg_align_long.hip: the same three separately rounded adds, bit for bit what asg_align.hip returns
 # asg_beam.hip: lm_weight * delta is rounded before it is added (sl_asg_beam_search is defined bit for bit)
 FILE_FLAGS = {"ctc.hip": ["-fno-slp-vectorize"], "ctc_beam.hip": ["-ffp-contract=off"], "asg_align.hip": ["-ffp-contract=off"],
+              "asg_align_long.hip": ["-ffp-contract=off"],
               "asg_beam.hip": ["-ffp-contract=off"]}
 
 

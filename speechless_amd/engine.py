@@ -213,7 +213,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.dropout_seed = 0
         self._dropout_steps = 0
         self.cur = None
-        self._long_align = None  # buffers._LongAlignBuffers of ctc_align_long, on first use
+        self._long_align = None  # buffers._LongAlignBuffers of ctc_align_long / asg_align_long, on first use
+        self._long_viterbi = None  # tensors of asg_viterbi_long, on first use
         self.timeline = None
         self.kernel_timeline = None  # (set of tags, list of (tag, start, stop)): see _around
         self._side_stream = None
@@ -1145,6 +1146,84 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                      la.input_len.data_ptr(), path.data_ptr(), la.score.data_ptr(), batch, t_out, k, la.labels.shape[1],
                      la.ws.data_ptr(), need, self._stream())
         return path.view(batch, t_out).cpu().numpy(), la.score.cpu().numpy()
+
+    def asg_align_long(self, logq, label_batch, label_lengths, prediction_lengths):
+        """asg_align() beyond 511 graphemes, on a given (B, T', K) fp32 logq tensor in HBM (forward_long's) and the engine's
+        asg_trans / asg_init: one sl_asg_align_long launch (include/speechless_hip.h; encoded labels of up to
+        longform.ASG_ALIGN_MAX_LABEL graphemes).  Does not touch the current buffer set.  label_batch: int (B, Lmax) padded
+        with anything; lengths: (B,) or (B, 1).  Returns (paths int32 (B, T') numpy, scores float32 (B,) numpy) as asg_align
+        does."""
+        from . import longform
+        from .buffers import _LongAlignBuffers
+        self._require_asg("asg_align_long()")
+        k = self.grapheme_set_size
+        if logq.dim() != 3 or logq.shape[2] != k or logq.dtype != torch.float32 or not logq.is_cuda:
+            raise ValueError("logq must be a float32 (B, T', {}) tensor on the device".format(k))
+        logq = logq.contiguous()
+        batch, t_out = int(logq.shape[0]), int(logq.shape[1])
+        labels = np.asarray(label_batch, dtype=np.int32)
+        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
+        in_len = np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)
+        if labels.ndim != 2 or labels.shape[0] != batch or lab_len.shape[0] != batch or in_len.shape[0] != batch:
+            raise ValueError("label batch must be (B, Lmax) with B label lengths and B prediction lengths")
+        if labels.shape[1] > longform.ASG_ALIGN_MAX_LABEL:
+            raise ValueError("labels of {} graphemes: ASG forced alignment takes at most {} (sl_asg_align_long)".format(
+                labels.shape[1], longform.ASG_ALIGN_MAX_LABEL))
+        for i in range(batch):
+            if not 0 <= lab_len[i] <= labels.shape[1]:
+                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
+            row = labels[i, :lab_len[i]]
+            if row.size and (row.min() < 0 or row.max() >= k):
+                raise ValueError("label {} holds an index outside [0, {})".format(i, k))
+        if self._long_align is None:
+            self._long_align = _LongAlignBuffers(self.device, "sl_asg_align_long_workspace_bytes")
+        la = self._long_align
+        need = la.ensure(batch, t_out, max(int(labels.shape[1]), 1))
+        la.labels.zero_()
+        la.labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
+        la.label_len.copy_(torch.from_numpy(lab_len))
+        la.input_len.copy_(torch.from_numpy(in_len))
+        path = la.path[:batch * t_out]
+        trans, init = self._asg_views(self.asg_params)
+        self._launch("asg_align_long", "sl_asg_align_long", logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                     la.labels.data_ptr(), la.label_len.data_ptr(), la.input_len.data_ptr(), path.data_ptr(),
+                     la.score.data_ptr(), batch, t_out, k, la.labels.shape[1], la.ws.data_ptr(), need, self._stream())
+        return path.view(batch, t_out).cpu().numpy(), la.score.cpu().numpy()
+
+    def asg_viterbi_long(self, logq):
+        """asg_viterbi() on a given (B, T', K) fp32 logq tensor in HBM (forward_long's), over all of its frames: one
+        sl_asg_viterbi launch whose workspace is sized for that T' (its backpointers spill there, so T' has no limit but
+        memory).  Does not touch the current buffer set.  Returns (list of index lists with repeats merged as asg_viterbi
+        merges them, per-frame paths (B, T') numpy)."""
+        self._require_asg("asg_viterbi_long()")
+        k = self.grapheme_set_size
+        if logq.dim() != 3 or logq.shape[2] != k or logq.dtype != torch.float32 or not logq.is_cuda:
+            raise ValueError("logq must be a float32 (B, T', {}) tensor on the device".format(k))
+        batch, t_out = int(logq.shape[0]), int(logq.shape[1])
+        if t_out == 0:
+            return [[] for _ in range(batch)], np.zeros((batch, 0), dtype=np.int32)
+        logq = logq.contiguous()
+        dev = self.device
+        need = self.lib.raw("sl_asg_viterbi_workspace_bytes")(batch, t_out, k)
+        lv = self._long_viterbi
+        if lv is None or lv["path"].numel() < batch * t_out or lv["score"].shape[0] != batch or lv["ws"].numel() < need:
+            self._long_viterbi = lv = None  # (free the old tensors first)
+            self._long_viterbi = lv = {"path": torch.zeros((batch * t_out,), dtype=torch.int32, device=dev),
+                                       "score": torch.zeros((batch,), dtype=torch.float32, device=dev),
+                                       "lens": torch.zeros((batch,), dtype=torch.int32, device=dev),
+                                       "ws": torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)}
+        lv["lens"].fill_(t_out)
+        path = lv["path"][:batch * t_out]
+        trans, init = self._asg_views(self.asg_params)
+        self._launch("asg_viterbi_long", "sl_asg_viterbi", logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                     lv["lens"].data_ptr(), path.data_ptr(), lv["score"].data_ptr(), batch, t_out, k, lv["ws"].data_ptr(),
+                     lv["ws"].numel(), self._stream())
+        paths = path.view(batch, t_out).cpu().numpy()
+        decoded = []
+        for row in paths:
+            row = row[row >= 0]
+            decoded.append([int(g) for g in row[np.concatenate([[True], row[1:] != row[:-1]])]] if row.size else [])
+        return decoded, paths
 
     def asg_align(self, label_batch, label_lengths, prediction_lengths):
         """ctc_align() for the ASG criterion: the best segmentation of the (run-length-encoded) labels over the frames under

@@ -1,4 +1,5 @@
-"""Windows over a long recording (Engine.forward_long, Wav2Letter.predict_recording / align_recording): pure Python.
+"""Windows over a long recording (Engine.forward_long, Wav2Letter.predict_recording / align_recording / asg_align_recording):
+pure Python.
 
 The engine zero-pads every layer at the edges of a batch row; the reference's "same" padding (net.py:304-305) does so at the
 recording's true edges only.  A window cut out of a recording therefore computes WRONG frames next to its interior edges: an
@@ -10,6 +11,7 @@ from collections import namedtuple
 
 DEFAULT_WINDOW = 8000             # input frames per window: the longest batch row the engine is exercised at (8 x 8000)
 ALIGN_MAX_LABEL = 8191            # sl_ctc_align_long: letters per label (16 383 lattice states)
+ASG_ALIGN_MAX_LABEL = 8191        # sl_asg_align_long: ENCODED graphemes per label (a run of two or three equal letters is two)
 GREEDY_DECODE_MAX_FRAMES = 38144  # sl_greedy_decode: output frames per recording ((t_out + 256) ints in 150 KB of LDS)
 
 

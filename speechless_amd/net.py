@@ -744,11 +744,16 @@ class Wav2Letter:
 
     def predict_recording(self, spectrogram_or_example, window_input_frames=None):
         """Greedy transcript of ONE recording of any length (a (T, F) spectrogram as predict_batch_greedily takes them, or an
-        example): Engine.forward_long over windows, one sl_greedy_decode over the stitched probabilities."""
-        if self.criterion == "asg":
-            raise ValueError("criterion='asg': predict_recording decodes the CTC way (blank = K - 1); not supported")
+        example): Engine.forward_long over windows, one sl_greedy_decode over the stitched probabilities -- under
+        criterion='asg' one sl_asg_viterbi over the stitched logq (Engine.asg_viterbi_long: no limit on the frames, its
+        backpointers go to the workspace), decoded as predict_batch_greedily decodes."""
         spectrogram = self._recording_spectrogram(spectrogram_or_example, "predict_recording")
         engine = self.eval_engine
+        frames = spectrogram.shape[0] // self.input_to_prediction_length_ratio
+        if self.criterion == "asg":
+            _, logq = engine.forward_long(spectrogram, window_input_frames)
+            decoded = engine.asg_viterbi_long(logq[:, :frames])[0][0]
+            return self.grapheme_encoding.decode_graphemes(decoded, merge_repeated=False)
         probs, _ = engine.forward_long(spectrogram, window_input_frames)
         decoded = engine.greedy_decode_long(probs[:, :spectrogram.shape[0] // self.input_to_prediction_length_ratio])[0]
         return self.grapheme_encoding.decode_graphemes(decoded, merge_repeated=False)
@@ -777,6 +782,37 @@ class Wav2Letter:
         """positional_label_batch for ONE recording of any length (align_recording): its word timings in seconds, None where
         the label cannot be aligned or has no words."""
         alignment = self.align_recording(example, window_input_frames)  # (first: it refuses what it cannot align)
+        seconds = self._seconds_per_input_step(example, seconds_per_input_step)
+        return alignment.positional_label(self.input_to_prediction_length_ratio * seconds)
+
+    def asg_align_recording(self, example, window_input_frames=None):
+        """asg_alignment_batch for ONE recording of any length and a label of up to longform.ASG_ALIGN_MAX_LABEL ENCODED
+        graphemes (a run of two or three equal letters is two): Engine.forward_long over windows, then one sl_asg_align_long
+        launch over the stitched logq and the engine's scores.  Returns an alignment.AsgAlignment (frames = output frames);
+        alignment.cut_sections cuts it into utterances.  (Named like asg_alignment_batch: align_recording keeps refusing
+        an ASG net.)"""
+        from . import longform
+        from .alignment import AsgAlignment
+        if self.criterion != "asg":
+            raise ValueError("asg_align_recording / asg_positional_label_of_recording need a net built with criterion='asg' "
+                             "(a CTC net aligns with align_recording / positional_label_of_recording)")
+        spectrogram = self._recording_spectrogram(example, "asg_align_recording")
+        enc = self.grapheme_encoding
+        encoded = enc.encode(example.label)
+        if len(encoded) > longform.ASG_ALIGN_MAX_LABEL:
+            raise ValueError("a label of {} encoded graphemes: asg_align_recording takes at most {} (sl_asg_align_long)".format(
+                len(encoded), longform.ASG_ALIGN_MAX_LABEL))
+        engine = self.eval_engine
+        _, logq = engine.forward_long(spectrogram, window_input_frames)
+        labels = np.asarray(encoded, dtype=np.int32).reshape(1, -1)
+        paths, scores = engine.asg_align_long(logq, labels, [len(encoded)],
+                                              [spectrogram.shape[0] // self.input_to_prediction_length_ratio])
+        return AsgAlignment.from_path(example.label, encoded, enc.asg_twice, enc.asg_thrice, scores[0], paths[0])
+
+    def asg_positional_label_of_recording(self, example, seconds_per_input_step=None, window_input_frames=None):
+        """asg_positional_label_batch for ONE recording of any length (asg_align_recording): its word timings in seconds,
+        None where the label cannot be aligned or has no words."""
+        alignment = self.asg_align_recording(example, window_input_frames)  # (first: it refuses what it cannot align)
         seconds = self._seconds_per_input_step(example, seconds_per_input_step)
         return alignment.positional_label(self.input_to_prediction_length_ratio * seconds)
 
