@@ -11,7 +11,7 @@ LIB_PATH = PACKAGE_DIR / "libspeechless_hip.so"
 HOST_LIB_PATH = PACKAGE_DIR / "libspeechless_host.so"  # plain C++ helpers of the host input pipeline (no HIP)
 HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csrc_host" / "beam_search.cpp"]
 CXX = os.environ.get("CXX", "g++")
-SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "misc.hip", "spectrogram.hip", "conv_chain_bf16.hip",
+SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "ctc_long.hip", "misc.hip", "spectrogram.hip", "conv_chain_bf16.hip",
            "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip",
            "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 
 
 def _newest_source_mtime():
-    files = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "lds_dma.h", CSRC / "lattice.h", CSRC / "beam_lm.h", PACKAGE_DIR.parent / "include" / "speechless_hip.h"]
+    files = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "lds_dma.h", CSRC / "lattice.h", CSRC / "beam_lm.h", CSRC / "ctc_shared.h", PACKAGE_DIR.parent / "include" / "speechless_hip.h"]
     return max(f.stat().st_mtime for f in files)
 
 
@@ -44,8 +44,11 @@ def _newest_source_mtime():
 # memory traffic inside the per-frame barrier interval of up to 16 waves)
 # (asg_align_long.hip: 8 states, their columns and scores and the 32 backtrace dwords per thread are register arrays indexed by
 # unrolled constants; scratch there is the same traffic inside the same barrier interval)
+# (ctc_long.hip: up to 4 lattice states in doubles, two chunks of 8 frames' emissions and the list builder's ranks per thread are
+# register arrays indexed by unrolled constants; scratch there is memory traffic inside the per-frame barrier interval of 16 waves)
 NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
-              "ctc_align_long.hip", "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip"}
+              "ctc_align_long.hip", "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
+              "ctc_long.hip"}
 
 
 def _scratch_users(remarks):

@@ -20,16 +20,15 @@
 //                         writes d(loss)/d(logits) straight into the halo'd gradient tensor of output_conv.
 //   greedy_decode_kernel: one work-group per utterance: argmax (first max wins), merge repeats, drop blank, compact.
 #include "common.h"
+#include "ctc_shared.h"
 
 #include <type_traits>
 
 namespace {
 
-// The lattice lives in LOG2 units: v_exp_f32 / v_log_f32 are base-2 natively, so a 3-way log-sum-exp is 3 + 1 raw
-// transcendentals instead of 4 range-reduced libm calls on the 500-step sequential critical path.  The arguments are
-// <= 0 (exp2) and in [1,3] (log2), so the raw instructions need no denormal / range fix-ups.
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
+// The lattice lives in LOG2 units (LOG2E, LN2: ctc_shared.h): v_exp_f32 / v_log_f32 are base-2 natively, so a 3-way log-sum-exp
+// is 3 + 1 raw transcendentals instead of 4 range-reduced libm calls on the 500-step sequential critical path.  The arguments
+// are <= 0 (exp2) and in [1,3] (log2), so the raw instructions need no denormal / range fix-ups.
 
 __device__ __forceinline__ float lse3_2(float a, float b, float c) {
     const float m = fmaxf(a, fmaxf(b, c));
@@ -44,17 +43,6 @@ __device__ __forceinline__ double lse3_2d(double a, double b, double c) {
     const double m = fmax(a, fmax(b, c));
     if (m == -INFINITY) return -INFINITY;
     return m + log2(exp2(a - m) + exp2(b - m) + exp2(c - m));
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // one wave per frame, lane = class (k <= 64): a frame's logits are one coalesced 4*k-byte read; the four reductions
@@ -1437,8 +1425,6 @@ __global__ __launch_bounds__(256) void greedy_decode_kernel(const float* __restr
     if (tid == 0) out_len[b] = total;
 }
 
-__host__ int lattice_sp(int l_max) { return ((2 * l_max + 1) + 63) / 64 * 64; }
-
 // which lattice sl_ctc_loss_grad runs (sl_ctc_select), and what the repair pass behind it redoes: the utterances the lattice
 // or the gradient kernel flagged, all of them (tests), or none (measurement).  The probability-domain lattices take labels
 // with 2 * l_max + 1 <= 512 and k <= 63; beyond that every variant runs the log-domain lattice (per call at 32 x 500 frames:
@@ -1475,7 +1461,7 @@ __host__ const CtcVariant* ctc_variant_row(int variant) {
 int g_ctc_variant = 0;  // always a row of the table (sl_ctc_select)
 
 struct CtcLayout {
-    size_t log_alpha, log_beta, cls, lin_alpha, lin_beta, dump, ea, eb, logz2, zint, flags, tickets, total;
+    size_t log_alpha, log_beta, cls, lin_alpha, lin_beta, dump, ea, eb, logz2, zint, flags, tickets, long_dump, total;
 };
 __host__ CtcLayout ctc_layout(int batch, int t_out, int l_max) {
     CtcLayout w;
@@ -1503,6 +1489,8 @@ __host__ CtcLayout ctc_layout(int batch, int t_out, int l_max) {
     w.zint = take((size_t)batch * sizeof(int32_t));
     w.flags = take((size_t)batch * sizeof(int32_t));
     w.tickets = take((size_t)batch * ((t_out + 7) / 8) * sizeof(int32_t));  // one done slot per gradient work-group
+    // the long-label path (ctc_long.hip) uses log_alpha / log_beta in doubles, cls, logz2, zint and this; nothing for <= 511
+    w.long_dump = take(l_max > SL_CTC_SHORT_MAX_LABEL ? ctc_long_dump_bytes(batch) : 0);
     w.total = off;
     return w;
 }
@@ -1527,7 +1515,7 @@ extern "C" int sl_softmax_logq(const float* logits, float* probs, float* logq, i
 }
 
 extern "C" size_t sl_ctc_workspace_bytes(int batch, int t_out, int l_max) {
-    if (batch <= 0 || t_out <= 0 || l_max < 0) return 0;
+    if (batch <= 0 || t_out <= 0 || l_max < 0 || l_max > SL_CTC_MAX_LABEL) return 0;
     // log-domain alpha + beta lattices and the class position lists (pos[l_max] | start[k + 1], k <= 64) per utterance;
     // when the labels fit the wave lattice: its double lattices, per-frame exponents, log2 Z and repair flags as well
     // MONOTONIC in l_max: labels beyond the wave lattice's 255 graphemes drop its double lattices from the layout, so the
@@ -1548,11 +1536,15 @@ extern "C" int sl_ctc_loss_grad(const float* probs, const float* logq, const int
                                 float grad_scale, void* workspace, size_t workspace_bytes, void* stream) {
     SL_CHECK_ARG(batch > 0 && t_out > 0 && k > 1 && k <= 64, "sl_ctc_loss_grad: need batch,t_out > 0 and 1 < k <= 64");
     SL_CHECK_ARG(l_max >= 1, "sl_ctc_loss_grad: l_max must be >= 1 (pad the label batch to width 1 for empty labels)");
-    const int sp = lattice_sp(l_max);
-    if (2 * l_max + 1 > 1024) {
-        sl_set_error("sl_ctc_loss_grad: label length %d > 511 unsupported (one lattice state per thread)", l_max);
+    if (l_max > SL_CTC_MAX_LABEL) {
+        sl_set_error("sl_ctc_loss_grad: l_max %d > %d unsupported (two lattices in doubles per utterance, LDS of the gradient kernel)",
+                     l_max, SL_CTC_MAX_LABEL);
         return SL_ERR_UNSUPPORTED;
     }
+    SL_CHECK_ARG(probs != nullptr && logq != nullptr && labels != nullptr && label_len != nullptr && input_len != nullptr &&
+                     loss != nullptr && dlogits != nullptr && workspace != nullptr,
+                 "sl_ctc_loss_grad: null pointer");
+    const int sp = lattice_sp(l_max);
     const CtcLayout w = ctc_layout(batch, t_out, l_max);
     if (workspace_bytes < w.total) {
         sl_set_error("sl_ctc_loss_grad: workspace too small");
@@ -1560,6 +1552,11 @@ extern "C" int sl_ctc_loss_grad(const float* probs, const float* logq, const int
     }
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)workspace;
+    if (l_max > SL_CTC_SHORT_MAX_LABEL)  // 512 .. 2047 letters: the whole batch on the kernels of ctc_long.hip (no sl_ctc_select)
+        return ctc_long_loss_grad(probs, logq, labels, label_len, input_len, loss, dlogits, batch, t_out, k, l_max, g_row0,
+                                  g_row_stride, (long)g_batch_stride, dtype == SL_F32 ? 1 : 0, eps, grad_scale,
+                                  (double*)(base + w.log_alpha), (double*)(base + w.log_beta), (int32_t*)(base + w.cls),
+                                  (float*)(base + w.logz2), (int32_t*)(base + w.zint), (double*)(base + w.long_dump), s);
     float* alpha = (float*)(base + w.log_alpha);
     float* beta = (float*)(base + w.log_beta);
     int32_t* cls = (int32_t*)(base + w.cls);

@@ -798,6 +798,13 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
 
     # ------------------------------------------------------------------ loss + backward
 
+    def _check_label_width(self, width):
+        """the CTC loss takes label batches of up to longform.CTC_LOSS_MAX_LABEL columns (the ASG loss states its own limit)"""
+        from . import longform
+        if self.criterion == "ctc" and width > longform.CTC_LOSS_MAX_LABEL:
+            raise ValueError("label batch of {} columns: the CTC loss takes at most CTC_LOSS_MAX_LABEL = {} letters per label".format(
+                int(width), longform.CTC_LOSS_MAX_LABEL))
+
     def set_labels(self, label_batch, label_lengths, prediction_lengths):
         """label_batch: int (B,Lmax) padded with anything (reference pads -1); lengths: (B,) or (B,1)."""
         buf = self.cur
@@ -813,6 +820,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             if row.size and (row.min() < 0 or row.max() >= top):
                 raise ValueError("label {} holds an index outside [0, {}){}".format(
                     i, top, "" if self.criterion == "asg" else " (blank is {})".format(k - 1)))
+        self._check_label_width(labels.shape[1])
         l_max = max(int(labels.shape[1]), 1)
         if labels.shape[1] == 0:
             labels = np.zeros((buf.batch, 1), dtype=np.int32)
@@ -831,6 +839,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         buf.ensure_backward(self)
         if labels_dev.dim() != 2 or labels_dev.shape[0] != buf.batch or labels_dev.shape[1] < 1:
             raise ValueError("label batch must be (B, Lmax >= 1)")
+        self._check_label_width(labels_dev.shape[1])
         buf.ensure_ctc(self, int(labels_dev.shape[1]))
         buf.labels = labels_dev
         buf.label_len = label_len_dev

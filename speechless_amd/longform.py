@@ -12,6 +12,7 @@ from collections import namedtuple
 DEFAULT_WINDOW = 8000             # input frames per window: the longest batch row the engine is exercised at (8 x 8000)
 ALIGN_MAX_LABEL = 8191            # sl_ctc_align_long: letters per label (16 383 lattice states)
 ASG_ALIGN_MAX_LABEL = 8191        # sl_asg_align_long: ENCODED graphemes per label (a run of two or three equal letters is two)
+CTC_LOSS_MAX_LABEL = 2047         # sl_ctc_loss_grad: letters per label (4095 lattice states; two lattices in doubles per utterance)
 GREEDY_DECODE_MAX_FRAMES = 38144  # sl_greedy_decode: output frames per recording ((t_out + 256) ints in 150 KB of LDS)
 
 
