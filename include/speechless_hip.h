@@ -293,29 +293,33 @@ int sl_output_softmax(const void* x, const void* w, const float* bias, float* pr
  * checks every frame's posteriors against 1, and an utterance that lost mass to underflow is redone in the log domain --
  * in doubles since round 6: as accurate as the lattice it replaces -- by the last work-group of the same launch (no further
  * launches; none of the regimes of a training run -- near-uniform start, blank collapse, a net that has learnt its labels
- * -- needs it; alignments with next to no slack, labels filling > 90 % of the frames, can).  Labels beyond 255 graphemes go through the
- * log-domain lattice kernel (one thread per lattice state, LDS row exchange + barrier per frame).  Results agree to fp32
- * round-off.
+ * -- needs it; alignments with next to no slack, labels filling > 90 % of the frames, can).  Labels beyond 255 graphemes, and
+ * k = 64 at any label length, go through the log-domain lattice in doubles of csrc/ctc_long.hip (two or four lattice states per
+ * thread, LDS edge exchange + barrier per frame).  Both meet the same bounds against a float64 lattice: loss 1e-5 relative,
+ * every gradient entry within 1e-4 * grad_scale.
  *
  * Limits: batch, t_out > 0, 2 <= k <= 64, 1 <= l_max <= 2047 (4095 lattice states).  l_max > 2047 is SL_ERR_UNSUPPORTED with a
  * message that names l_max and 2047, before anything is launched; a null pointer is SL_ERR_INVALID_ARGUMENT, a workspace below
  * sl_ctc_workspace_bytes() SL_ERR_WORKSPACE_TOO_SMALL.  The cap is 2047 and not the aligners' 8191 because (a) the loss keeps TWO
- * full lattices per utterance, alpha and beta, in doubles beyond 511 letters: 64 KiB per frame at 4095 states (8 utterances of
+ * full lattices per utterance, alpha and beta, in doubles beyond 255 letters: 64 KiB per frame at 4095 states (8 utterances of
  * 4000 frames: 2.1 GB), and (b) the gradient kernel's LDS -- labels, class lists and one occupancy row per wave, 6 * l_max + 321
  * words -- is 50.4 KB at 2047, inside the default 64 KB limit.
- * A batch goes wholly to the kernels its l_max (the width of the label batch) selects:
+ * A batch goes wholly to the kernels its l_max (the width of the label batch) and k select:
  *     l_max        lattice kernel                                   rows                  gradient kernel
  *     1 .. 255     ctc_lattice_helped_kernel (sl_ctc_select: 0)     linear, hi words      ctc_grad_kernel<8, 1> (+ repair)
- *     256 .. 511   ctc_lattice_kernel, one state per thread         log2, fp32            ctc_grad_kernel<4|8|16, 0>
- *     512 .. 1023  ctc_long_lattice_kernel<2>, 2 states per thread  log2, doubles         ctc_long_grad_kernel
+ *     256 .. 1023  ctc_long_lattice_kernel<2>, 2 states per thread  log2, doubles         ctc_long_grad_kernel
  *     1024 .. 2047 ctc_long_lattice_kernel<4>, 4 states per thread  log2, doubles         ctc_long_grad_kernel
- * (k = 64 sends l_max <= 255 to the second row.)  Up to 511 nothing differs from what it was: same launches, same bytes.  The
- * long-label kernels (csrc/ctc_long.hip) keep the lattice values in doubles and take only each step's log2 of a sum in [1, 3]
- * in fp32; loss and gradient meet the bounds of the short path against the float64 oracle (CTC section).  The
- * sl_ctc_select variants do not apply beyond 511 letters: there is one long-label path, whatever is selected.
+ * (k = 64, which the wave lattice does not take, sends l_max <= 255 to the second row as well.)  With l_max <= 255 and k <= 63
+ * nothing differs from what it was: same launches, same bytes.  The kernels of csrc/ctc_long.hip keep the lattice values in
+ * doubles and take only each step's log2 of a sum in [1, 3] in fp32; loss and gradient meet the bounds of the wave lattice
+ * against the float64 oracle (CTC section).  Until this rule, 256 .. 511 letters and k = 64 ran ctc_lattice_kernel
+ * (one state per thread, rows in fp32 log2 units) with ctc_grad_kernel<4|8|16, 0>: up to 3e-3 absolute from the float64 gradient
+ * on labels with little slack.  sl_ctc_select(1) still runs it, for every l_max <= 511 (measurement and tests); no other variant
+ * changes what runs beyond the wave lattice, and none applies beyond 511 letters.
  * sl_ctc_workspace_bytes: with sp = (2 * l_max + 1 rounded up to 64) it is 2 * batch * t_out * sp * 8 bytes of log-domain rows
  * + batch * (l_max + 65) * 4 of class lists + (l_max <= 255: the wave lattice's rows, exponents and dump rows) + per-utterance
- * words and done slots + (l_max >= 512: 4 KiB per utterance where lanes beyond a row's end store), every part rounded up to
+ * words and done slots + (l_max >= 256: 4 KiB per utterance where the lanes of ctc_long.hip beyond a row's end store; up to 255
+ * the wave lattice's dump rows serve, so these sizes are what they always were), every part rounded up to
  * 256 bytes; monotonic in batch, t_out and l_max over 0 .. 2047 (a workspace sized for l_max serves every narrower batch), 0 for
  * non-positive sizes and beyond 2047; 64-bit throughout.
  */
@@ -332,7 +336,8 @@ int sl_ctc_loss_grad(const float* probs, const float* logq, const int32_t* label
  * every lattice lane's emissions into 48 contiguous bytes of LDS per frame (three wide LDS reads per frame instead of five, no
  * staging work in the lattice wave) with / without the repair pass.  8 / 9 (the lattice on a pair of waves) are retired: they,
  * and every value not named here, are refused with SL_ERR_INVALID_ARGUMENT and leave the setting as it was.  Process-wide; not for concurrent use with sl_ctc_loss_grad.
- * Label batches wider than 511 (csrc/ctc_long.hip) are not affected by it. */
+ * Label batches wider than 511 are not affected by it; of what the wave lattice does not take below that (256 .. 511 letters,
+ * k = 64) only variant 1 changes the kernels: the fp32 log-domain lattice instead of the doubles of csrc/ctc_long.hip. */
 int sl_ctc_select(int variant);
 
 /* ---- greedy decode (net.py:452-454 tf.nn.ctc_greedy_decoder, merge_repeated=True; numpy twin

@@ -1427,8 +1427,9 @@ __global__ __launch_bounds__(256) void greedy_decode_kernel(const float* __restr
 
 // which lattice sl_ctc_loss_grad runs (sl_ctc_select), and what the repair pass behind it redoes: the utterances the lattice
 // or the gradient kernel flagged, all of them (tests), or none (measurement).  The probability-domain lattices take labels
-// with 2 * l_max + 1 <= 512 and k <= 63; beyond that every variant runs the log-domain lattice (per call at 32 x 500 frames:
-// 108 vs 132 us; at 8 x 4000 frames 556 vs 912).  The numbers are fixed: profiles, HISTORY.md and tools refer to them, and
+// with 2 * l_max + 1 <= 512 and k <= 63; beyond that variant 1 runs the fp32 log-domain lattice of this file (up to 511 letters;
+// per call at 32 x 500 frames: 108 vs 132 us; at 8 x 4000 frames 556 vs 912) and every other one the double log-domain
+// lattice of ctc_long.hip.  The numbers are fixed: profiles, HISTORY.md and tools refer to them, and
 // 8 / 9 (the lattice on a pair of waves: DESIGN.md section 6) stay retired.
 #ifndef SL_CTC_DEFAULT_WAVE
 // sl_ctc_select(0): 10 = the lattice wave with its helper wave (round 6: 92.4 -> 88.0 us per call at 32 x 500, 502 -> 471 us at
@@ -1479,7 +1480,8 @@ __host__ CtcLayout ctc_layout(int batch, int t_out, int l_max) {
     const bool wave = 2 * l_max + 1 <= 64 * WNS;
     w.lin_alpha = take(wave ? rows * 64 * WNS * sizeof(uint32_t) : 0);  // a float, or the high word of a double, per state
     w.lin_beta = take(wave ? rows * 64 * WNS * sizeof(uint32_t) : 0);
-    w.dump = take(wave ? (size_t)2 * batch * 64 * WNS * sizeof(uint32_t) : 0);
+    const size_t wave_dump_bytes = wave ? (size_t)2 * batch * 64 * WNS * sizeof(uint32_t) : 0;
+    w.dump = take(wave_dump_bytes);
     // one exponent per lane and block of 16 (double) / 8 (float) steps: (t_out / 16 + 1) * 64 resp. (t_out / 8 + 1) * 64 per
     // utterance are read and written.  (The retired wave-pair lattice kept 128 per block of 16, the same size.)
     const size_t eblocks = (size_t)batch * (t_out / 8 + 2) * 64;
@@ -1489,8 +1491,11 @@ __host__ CtcLayout ctc_layout(int batch, int t_out, int l_max) {
     w.zint = take((size_t)batch * sizeof(int32_t));
     w.flags = take((size_t)batch * sizeof(int32_t));
     w.tickets = take((size_t)batch * ((t_out + 7) / 8) * sizeof(int32_t));  // one done slot per gradient work-group
-    // the long-label path (ctc_long.hip) uses log_alpha / log_beta in doubles, cls, logz2, zint and this; nothing for <= 511
-    w.long_dump = take(l_max > SL_CTC_SHORT_MAX_LABEL ? ctc_long_dump_bytes(batch) : 0);
+    // the double log-domain path (ctc_long.hip) uses log_alpha / log_beta in doubles, cls, logz2, zint and this.  There for every
+    // l_max: the layout does not know k, and k = 64 takes that path at any label length.  Where the layout holds the wave lattice's
+    // dump rows (l_max <= 255) they serve: the same purpose, the same 4 KB per utterance, and a call runs one lattice or the other
+    // -- so the workspace of the wave lattice's shapes is byte for byte what it was.
+    w.long_dump = wave_dump_bytes >= ctc_long_dump_bytes(batch) ? w.dump : take(ctc_long_dump_bytes(batch));
     w.total = off;
     return w;
 }
@@ -1552,7 +1557,13 @@ extern "C" int sl_ctc_loss_grad(const float* probs, const float* logq, const int
     }
     hipStream_t s = (hipStream_t)stream;
     char* base = (char*)workspace;
-    if (l_max > SL_CTC_SHORT_MAX_LABEL)  // 512 .. 2047 letters: the whole batch on the kernels of ctc_long.hip (no sl_ctc_select)
+    // which lattice: see sl_ctc_select
+    const CtcVariant* row = ctc_variant_row(g_ctc_variant);
+    const bool fits = 2 * l_max + 1 <= 64 * WNS && k <= 63;
+    // What the wave lattice does not take (256 .. 2047 letters, or 64 classes at any length): the whole batch on the double
+    // log-domain kernels of ctc_long.hip.  Only sl_ctc_select(1) still runs the fp32 log-domain lattice below, up to 511 letters
+    // (measurement and tests: 1e-4 .. 9e-3 absolute from the float64 gradient on labels with little slack).
+    if (l_max > SL_CTC_SHORT_MAX_LABEL || (!fits && row->variant != 1))
         return ctc_long_loss_grad(probs, logq, labels, label_len, input_len, loss, dlogits, batch, t_out, k, l_max, g_row0,
                                   g_row_stride, (long)g_batch_stride, dtype == SL_F32 ? 1 : 0, eps, grad_scale,
                                   (double*)(base + w.log_alpha), (double*)(base + w.log_beta), (int32_t*)(base + w.cls),
@@ -1561,9 +1572,6 @@ extern "C" int sl_ctc_loss_grad(const float* probs, const float* logq, const int
     float* beta = (float*)(base + w.log_beta);
     int32_t* cls = (int32_t*)(base + w.cls);
     int32_t* flags = (int32_t*)(base + w.flags);
-    // which lattice: see sl_ctc_select
-    const CtcVariant* row = ctc_variant_row(g_ctc_variant);
-    const bool fits = 2 * l_max + 1 <= 64 * WNS && k <= 63;
     const int lattice = fits ? row->lattice : LAT_LOG;
     const int frames_per_wg = 8;  // two frames per wave: 16000 frames -> 8000 waves in flight
     const size_t lds2 = (size_t)(2 * l_max + (k + 1)) * sizeof(int) + (size_t)(4 * 64 + 4 * l_max) * sizeof(float);

@@ -1,12 +1,13 @@
-// ctc_long.hip -- the CTC loss and gradient of ctc.hip for labels of 512 .. 2047 letters (1025 .. 4095 lattice states).
+// ctc_long.hip -- the CTC loss and gradient of ctc.hip for what its wave lattice does not take: labels of 256 .. 2047 letters
+// (513 .. 4095 lattice states), and 64 classes at any label length (l_max >= 1: a single wave of 64 threads up to 63 letters).
 //
-// Same semantics, arguments and outputs as the kernels of ctc.hip (sl_ctc_loss_grad dispatches on l_max, host code only); the
-// tuned kernels there hold a lattice row in one wave or one state per thread and stop at 511 letters.  Generalised from that
+// Same semantics, arguments and outputs as the kernels of ctc.hip (sl_ctc_loss_grad dispatches on l_max and k, host code only);
+// the wave lattice there holds a row of up to 511 states in one wave and has a lane per class for 63 classes and the blank's sum.  Generalised from that
 // file's repair pass (repair_lattices + ctc_grad_frames<8, 4>: a log-domain lattice in doubles, several states per thread, and
 // the gradient pass that reads such rows), as kernels of their own:
 //   ctc_long_lattice_kernel<NS> : grid (B, 3) like ctc_lattice_kernel.  Work-group (b,0) runs alpha forwards, (b,1) beta
 //                         backwards at the same time, (b,2) builds the per-class position lists.  Up to 1024 threads, each
-//                         owning NS CONSECUTIVE states (NS = 2: l_max 512 .. 1023, NS = 4: 1024 .. 2047) in registers; only the
+//                         owning NS CONSECUTIVE states (NS = 2: l_max up to 1023, NS = 4: 1024 .. 2047) in registers; only the
 //                         states at a thread's edge cross threads (alpha: one value up, beta: two values down), through
 //                         double-buffered LDS rows with one LDS-only barrier per frame.  Emissions are fetched a chunk of 8
 //                         frames ahead.  Rows in log2 units, doubles, -inf padding up to the row stride lattice_sp(l_max).

@@ -695,3 +695,18 @@ def test_ctc_random_regimes_against_the_float64_oracle():
                          capture_output=True, text=True, cwd=str(root), timeout=900)
     assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
     assert "all 15 cases passed" in res.stdout and "the repair pass ran in 0 case(s)" in res.stdout
+
+
+def test_ctc_mid_random_regimes():
+    """tools/fuzz_ctc.py --mid, eight cases: K of 5, 29, 63 or 64, labels of 200 .. 511 letters that fill 50 .. 100 % of their
+    frames, two regimes per utterance -- what the wave lattice does not take below 512 letters, on the double log-domain
+    lattice: the same bounds and the same pass line.  (Seed 25: its eight cases hold every one of the four class counts and two
+    utterances with at most two frames of slack.)"""
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parent.parent
+    res = subprocess.run([sys.executable, str(root / "tools" / "fuzz_ctc.py"), "--mid", "--cases", "8", "--seed", "25"],
+                         capture_output=True, text=True, cwd=str(root), timeout=900)
+    assert res.returncode == 0, res.stdout[-1500:] + res.stderr[-1500:]
+    assert "all 8 cases passed" in res.stdout and "the repair pass ran in 0 case(s)" in res.stdout

@@ -4,8 +4,9 @@ labels from empty to the longest the frames allow (and a few that do not fit), a
 near-uniform, sharp random, blank collapse, a learnt alignment of varying strength (optionally of a partly different
 transcript), and half-and-half mixtures of two of these along the time axis.  Per case: loss and gradient against the oracle,
 and whether the repair pass had to run (default variant vs the probability-domain lattice alone).
+--mid: what the wave lattice does not take below 512 letters (draw_mid_case: 200 .. 511 letters, up to 64 classes).
 
-    python tools/fuzz_ctc.py [--cases 40] [--seed 0]"""
+    python tools/fuzz_ctc.py [--cases 40] [--seed 0] [--tight | --mid]"""
 import argparse
 import sys
 from pathlib import Path
@@ -76,6 +77,33 @@ def draw_case(rng, kinds=("uniform", "sharp", "collapse", "learnt", "wrong"), ti
     return k, t, input_len, lab_len, labels_list, logits, desc
 
 
+def draw_mid_case(rng):
+    """the next case of the --mid stream, a generator of its own (draw_case's streams are replayed by seed and index elsewhere
+    and must not move by a draw): K of 5, 29, 63 (the last the wave lattice takes) or 64, one to three labels of 200 .. 511
+    letters that fill 50 .. 100 % of their frames -- 100 %: as many frames as letters and adjacent repeats, no slack at all; at
+    most 900 frames -- and two regimes per utterance, one in each half.  Same tuple as draw_case."""
+    kinds = ["uniform", "sharp", "collapse", "learnt", "wrong"]
+    k = int(rng.choice([5, 29, 63, 64]))
+    b = int(rng.randint(1, 4))
+    lab_len = [int(rng.randint(200, 512)) for _ in range(b)]
+    labels_list = [list(rng.randint(0, k - 1, size=n)) for n in lab_len]
+    input_len = []
+    for lab in labels_list:
+        need = len(lab) + sum(1 for a, c in zip(lab, lab[1:]) if a == c)
+        input_len.append(int(max(need, min(900, int(need / rng.uniform(0.5, 1.0))))))
+    t = max(input_len)
+    logits = np.zeros((b, t, k), dtype=np.float32)
+    desc = []
+    for i in range(b):
+        a, c = rng.choice(kinds), rng.choice(kinds)
+        la = regime_logits(rng, labels_list[i], input_len[i], k, a)
+        h = input_len[i] // 2
+        la[h:] = regime_logits(rng, labels_list[i], input_len[i], k, c)[h:]
+        logits[i, :input_len[i]] = la
+        desc.append(a + "|" + c)
+    return k, t, input_len, lab_len, labels_list, logits, desc
+
+
 def replay_case(seed, index):
     """case `index` of `python tools/fuzz_ctc.py --seed <seed>` (the stream is replayed on the host up to it)"""
     rng = np.random.RandomState(seed)
@@ -90,6 +118,8 @@ def main():
     ap.add_argument("--cases", type=int, default=40)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--tight", action="store_true", help="labels filling 60 .. 100 %% of the frames, two regimes per utterance")
+    ap.add_argument("--mid", action="store_true", help="200 .. 511 letters filling 50 .. 100 %% of the frames, K of 5, 29, 63, 64, "
+                    "two regimes per utterance: the double log-domain lattice below 512 letters (the oracle reads the kernel's probabilities)")
     ap.add_argument("--helped", action="store_true", help="the lattice wave with a helper wave (sl_ctc_select 10 / 11)")
     args = ap.parse_args()
     from oracle import w2l_oracle as o
@@ -101,17 +131,21 @@ def main():
     repaired = 0
     worst_loss = worst_grad = 0.0
     for case in range(args.cases):
-        k, t, input_len, lab_len, labels_list, logits, desc = draw_case(rng, kinds, tight=args.tight)
+        k, t, input_len, lab_len, labels_list, logits, desc = draw_mid_case(rng) if args.mid else draw_case(rng, kinds, tight=args.tight)
         b = logits.shape[0]
         labels = o.pack_label_batch([l if l else [-1] for l in labels_list])
-        ref_p = o.softmax(logits.astype(np.float64))
+        lib.call("sl_ctc_select", 10 if args.helped else 0)
+        probs, loss, dl = run_ctc_kernel(lib, logits, labels, lab_len, input_len)
+        if args.mid:  # no wave lattice and no repair pass here; a second call must give the same bytes
+            _, loss2, dl2 = run_ctc_kernel(lib, logits, labels, lab_len, input_len)
+            assert loss.tobytes() == loss2.tobytes() and dl.tobytes() == dl2.tobytes(), (case, desc)
+        else:
+            lib.call("sl_ctc_select", 11 if args.helped else 2)
+            _, loss2, dl2 = run_ctc_kernel(lib, logits, labels, lab_len, input_len)
+        lib.call("sl_ctc_select", 0)
+        ref_p = probs.astype(np.float64) if args.mid else o.softmax(logits.astype(np.float64))
         ref_loss, ref_dp = o.ctc_batch_cost(ref_p, labels, input_len, lab_len)
         ref_dl = o.softmax_backward(ref_p, ref_dp)
-        lib.call("sl_ctc_select", 10 if args.helped else 0)
-        _, loss, dl = run_ctc_kernel(lib, logits, labels, lab_len, input_len)
-        lib.call("sl_ctc_select", 11 if args.helped else 2)
-        _, loss2, dl2 = run_ctc_kernel(lib, logits, labels, lab_len, input_len)
-        lib.call("sl_ctc_select", 0)
         needed_repair = not (np.array_equal(loss, loss2, equal_nan=True) and np.array_equal(dl, dl2, equal_nan=True))
         repaired += int(needed_repair)
         fin = np.isfinite(ref_loss)
