@@ -391,7 +391,8 @@ int sl_ctc_align_long(const float* logq, const int32_t* labels, const int32_t* l
  *   numerator    a_0(0) = g0(l_0) + e_0(l_0), a_0(s > 0) = -inf;
  *                a_t(s) = e_t(l_s) + LSE(a_{t-1}(s) + g(l_s, l_s), a_{t-1}(s-1) + g(l_{s-1}, l_s));   N = a_{T_b-1}(L-1)
  *   denominator  d_0(j) = g0(j) + e_0(j);   d_t(j) = e_t(j) + LSE_i(d_{t-1}(i) + g(i, j));   Z = LSE_j d_{T_b-1}(j)
- *   loss[b] = Z - N >= 0.  Adjacent equal labels need no special rule.
+ *   loss[b] = Z - N, >= 0 for a label without equal neighbours (what AsgGraphemeEncoding produces).  Adjacent equal labels
+ *   need no special rule, but there N counts one letter sequence once per way of cutting the joint run, and may exceed Z.
  * Gradients of grad_scale * sum_b loss[b], with G_t(j) = (denominator posterior - numerator posterior) of letter j at frame
  * t, xi the posteriors of a pair of letters at frames t-1, t, p = probs and r = p / (p + eps):
  *   dlogits_t(j) = grad_scale * (G_t(j) r_t(j) - p_t(j) sum_i G_t(i) r_t(i)), w.r.t. the PRE-softmax logits, written like
