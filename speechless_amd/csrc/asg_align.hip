@@ -9,10 +9,11 @@
 // lane gathers the column of each of its states and the two scores it ever needs, g(l_s, l_s) and g(l_{s-1}, l_s), once.  Per
 // frame: the highest state of the lane below arrives by one DPP wave_shr:1 move, every state takes stay = d(s) + g(l_s, l_s)
 // and move = d(s-1) + g(l_{s-1}, l_s), keeps the larger (stay on a tie) and adds its emission -- three separately rounded
-// adds and an exact max: there is no multiply, so no FMA can form.  The compare of state j of every lane IS the frame's
-// backpointer word j (a 64-bit lane mask): one bit per state and frame, rows of NS words = 8*NS bytes, state s at bit s / NS
-// of word s % NS.  Emissions come from LDS: the wave stages CH frames of logq rows (k <= 64 floats, one coalesced read per
-// frame) while it works on the previous CH frames.
+// adds and an exact max: there is no multiply, so no FMA can form (asg_frame of lattice.h, which asg_align_long.hip runs too). 
+// The compare of state j of every lane IS the frame's backpointer word j (a 64-bit lane mask): one bit per state and frame, rows
+// of NS words = 8*NS bytes, state s at bit s / NS of word s % NS.  Emissions come from LDS: the wave stages ALIGN_CH frames of
+// logq rows (k <= 64 floats, one coalesced read per frame) while it works on the previous ALIGN_CH frames (EmissionStager of
+// lattice.h).
 //   BP_LDS = 1: the T' rows fit the work-group's LDS (config 3: 500 frames x 16 bytes) and the backtrace reads them there.
 //   BP_LDS = 0: rows go to the workspace in HBM; the backtrace copies windows of BT_W frames into LDS, the next window's
 //   loads in flight while the current one is resolved (lattice.h, as ctc_align.hip does).
@@ -24,12 +25,9 @@
 
 namespace {
 
-constexpr int CH = 16;  // frames of logq per LDS staging chunk
-constexpr int LDS_MAX = 160 * 1024;
-
 __host__ __device__ constexpr int row_bytes(int ns) { return 8 * ns; }  // ns lane masks of 64 bits
 
-// LDS: [logq chunk CH x 64 floats][final scores 64*NS floats][backpointer rows: T' rows (BP_LDS) or two windows of BT_W rows]
+// LDS: [logq chunk ALIGN_CH x 64 floats][final scores 64*NS floats][backpointer rows: T' rows (BP_LDS) or two windows of BT_W rows]
 template <int NS, bool BP_LDS>
 __global__ __launch_bounds__(64) void asg_align_kernel(const float* __restrict__ logq, const float* __restrict__ trans,
                                                         const float* __restrict__ init, const int32_t* __restrict__ labels,
@@ -40,7 +38,7 @@ __global__ __launch_bounds__(64) void asg_align_kernel(const float* __restrict__
     constexpr int R = row_bytes(NS);
     extern __shared__ float smem[];
     float* em = smem;
-    float* fin = em + CH * 64;
+    float* fin = em + ALIGN_CH * 64;
     uint8_t* rows = (uint8_t*)(fin + 64 * NS);
 
     const int b = blockIdx.x;
@@ -57,62 +55,30 @@ __global__ __launch_bounds__(64) void asg_align_kernel(const float* __restrict__
         return;
     }
 
-    // per-lane states: the emission column, the stay score and the score of the move into the state.  A state beyond the
-    // label stays at -inf for good (-inf + 0, and a move that adds -inf)
+    // per-lane states: lane l holds states l*NS .. l*NS + NS - 1 with their emission column, stay score and move score (lattice.h)
     int col[NS];
     float gs[NS], ga[NS], d[NS];
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        const int s = lane * NS + j;
-        col[j] = 0;
-        gs[j] = 0.f;
-        ga[j] = -INFINITY;
-        d[j] = -INFINITY;
-        if (s < L) {
-            const int c = clamp_label(lab[s], k);
-            col[j] = c;
-            gs[j] = trans[c * k + c];
-            if (s > 0) ga[j] = trans[clamp_label(lab[s - 1], k) * k + c];
-        }
-    }
+    asg_states_init<NS>(col, gs, ga, lab, lane * NS, L, k, trans);
     const float* lq = logq + (long)b * t_out * k;
-    if (lane == 0) d[0] = init[col[0]] + lq[col[0]];  // frame 0: only state 0
+    // frame 0: only state 0 is open (here and not in a helper: see asg_states_init)
+#pragma unroll
+    for (int j = 0; j < NS; ++j) d[j] = lane * NS + j == 0 ? init[col[0]] + lq[col[0]] : -INFINITY;
 
-    const bool col_on = lane < k;
-    float pre[CH];
-#pragma unroll
-    for (int f = 0; f < CH; ++f) {  // chunks start at frame 1
-        const int t = 1 + f < T ? 1 + f : T - 1;
-        pre[f] = col_on ? lq[(long)t * k + lane] : 0.f;
-    }
+    EmissionStager<64> stg;
+    stg.prefetch(lq, 1, T, k, 0, lane);  // chunks start at frame 1
     uint64_t* bp_rows = BP_LDS ? (uint64_t*)rows : (uint64_t*)(bp_hbm + (long)b * t_out * R);
-    for (int t0 = 1; t0 < T; t0 += CH) {
+    for (int t0 = 1; t0 < T; t0 += ALIGN_CH) {
         __syncthreads();
-#pragma unroll
-        for (int f = 0; f < CH; ++f) em[f * 64 + lane] = pre[f];
+        stg.store(em, 0, lane);
         __syncthreads();
-        if (t0 + CH < T) {
+        if (t0 + ALIGN_CH < T) stg.prefetch(lq, t0 + ALIGN_CH, T, k, 0, lane);
+        const int nf = T - t0 < ALIGN_CH ? T - t0 : ALIGN_CH;
 #pragma unroll
-            for (int f = 0; f < CH; ++f) {
-                const int t = t0 + CH + f < T ? t0 + CH + f : T - 1;
-                pre[f] = col_on ? lq[(long)t * k + lane] : 0.f;
-            }
-        }
-        const int nf = T - t0 < CH ? T - t0 : CH;
-#pragma unroll
-        for (int f = 0; f < CH; ++f) {
+        for (int f = 0; f < ALIGN_CH; ++f) {
             if (f >= nf) continue;  // (wave-uniform; a break keeps the loop from unrolling)
-            const float* e = em + f * 64;
             const float lo = dpp_float_from_lower_lane(d[NS - 1], -INFINITY);  // state lane*NS - 1
             uint64_t word[NS];
-#pragma unroll
-            for (int j = NS - 1; j >= 0; --j) {  // descending: d[j-1] still holds frame t-1
-                const float stay = d[j] + gs[j];
-                const float move = (j >= 1 ? d[j - 1] : lo) + ga[j];
-                const bool mv = move > stay;
-                word[j] = __ballot(mv);
-                d[j] = (mv ? move : stay) + e[col[j]];
-            }
+            asg_frame<NS>(col, gs, ga, d, em + f * 64, lo, word);
             if (lane == 0) {
                 uint64_t* row = bp_rows + (long)(t0 + f) * NS;
 #pragma unroll
@@ -163,7 +129,7 @@ __global__ __launch_bounds__(64) void asg_align_kernel(const float* __restrict__
 }
 
 size_t align_lds_bytes(int ns, bool bp_lds, int t_out) {
-    return (size_t)(CH * 64 + 64 * ns) * sizeof(float) + (size_t)(bp_lds ? t_out : 2 * BT_W) * row_bytes(ns);
+    return (size_t)(ALIGN_CH * 64 + 64 * ns) * sizeof(float) + (size_t)(bp_lds ? t_out : 2 * BT_W) * row_bytes(ns);
 }
 
 int states_per_lane(int l_max) { return l_max <= 64 ? 1 : (l_max <= 128 ? 2 : (l_max <= 256 ? 4 : 8)); }
@@ -174,7 +140,8 @@ int launch_align(const float* logq, const float* trans, const float* init, const
                  hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)asg_align_kernel<NS, BP_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)asg_align_kernel<NS, BP_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   ALIGN_LDS_MAX);
         attr_set = true;
     }
     hipLaunchKernelGGL((asg_align_kernel<NS, BP_LDS>), dim3(batch), dim3(64), align_lds_bytes(NS, BP_LDS, t_out), s, logq, trans,
@@ -187,7 +154,7 @@ int launch_align(const float* logq, const float* trans, const float* init, const
 extern "C" size_t sl_asg_align_workspace_bytes(int batch, int t_out, int l_max) {
     if (batch <= 0 || t_out <= 0 || l_max < 1 || l_max > 511) return 0;
     const int ns = states_per_lane(l_max);
-    return align_lds_bytes(ns, true, t_out) <= (size_t)LDS_MAX ? 0 : (size_t)batch * t_out * row_bytes(ns);
+    return align_lds_bytes(ns, true, t_out) <= (size_t)ALIGN_LDS_MAX ? 0 : (size_t)batch * t_out * row_bytes(ns);
 }
 
 extern "C" int sl_asg_align(const float* logq, const float* trans, const float* init, const int32_t* labels,

@@ -13,23 +13,23 @@
 // frame.  Every barrier is uniform: all trip counts depend on the recording only, and both infeasible-row exits are taken by the
 // whole work-group (the first before any barrier, the second on a score every thread reads from the same LDS word).  Per state
 // and frame: stay = d(s) + g(l_s, l_s), move = d(s-1) + g(l_{s-1}, l_s), the larger (stay on a tie) plus the emission -- three
-// separately rounded adds, no multiply.  Emissions come from LDS: the work-group stages CH frames of logq rows (k <= 64 floats)
-// once for all waves while the next CH frames are in flight in registers.
+// separately rounded adds, no multiply: asg_frame of lattice.h, the very step of asg_align.hip.  Emissions come from LDS: the
+// work-group stages ALIGN_CH frames of logq rows (k <= 64 floats) once for all waves while the next ALIGN_CH frames are in flight
+// in registers (EmissionStager of lattice.h, with all NW waves at work).
 // Backpointers: ONE bit per state and frame.  The ballot of state j's compare over a wave IS 64-bit word 8 w + j of the frame's
 // row (state s at bit (s >> 3) & 63 of word (s >> 9) * 8 + (s & 7)); a row = 64 NW bytes, lanes 0 .. 7 of each wave store the
 // wave's 64 bytes in one coalesced store to the workspace in HBM.
 // Backtrace: wave 0 (the other waves only keep the barriers uniform).  The path drops at most one state per frame, so a window
 // of BT_W = 64 frames whose top frame is at state s touches states [s - 64, s] only, and the window below it [s - 128, s]: the
 // words of at most two neighbouring waves, 32 contiguous dwords of each row (all 16 with one wave).  That band of the NEXT window
-// is loaded into registers before the current window is resolved out of LDS, so no step of the T'-long chain waits on a
-// dependent HBM load.  Lane t - w0 keeps frame t's state: one coalesced store per window.
+// is loaded into registers (load_band / store_band of lattice.h) before the current window is resolved out of LDS, so no step of
+// the T'-long chain waits on a dependent HBM load.  Lane t - w0 keeps frame t's state: one coalesced store per window.
 #include <math.h>
 
 #include "lattice.h"
 
 namespace {
 
-constexpr int CH = 16;          // frames of logq per LDS staging chunk
 constexpr int NS = 8;           // states per thread
 constexpr int WAVE_DW = 2 * NS; // backpointer dwords of a wave per frame
 constexpr int L_LIMIT = 8191;
@@ -39,10 +39,10 @@ struct LongBand {
     static constexpr int DW = NW == 1 ? WAVE_DW : 2 * WAVE_DW;  // dwords of a row that two windows below a state can touch
 };
 
-// LDS: [logq chunk CH x 64 floats][boundary slots 2 x 16][end score][backtrace windows 2 x BT_W x band dwords]
+// LDS: [logq chunk ALIGN_CH x 64 floats][boundary slots 2 x 16][end score][backtrace windows 2 x BT_W x band dwords]
 template <int NW>
 struct LongLds {
-    float em[CH * 64];
+    float em[ALIGN_CH * 64];
     float edge[2][16];
     float fin;
     uint32_t win[2][BT_W * LongBand<NW>::DW];
@@ -50,21 +50,6 @@ struct LongLds {
 
 // first wave of the band that holds [s - 128, s]: the wave of s and the one below it
 __device__ __forceinline__ int band_wave(int s) { return (s >> 9) > 0 ? (s >> 9) - 1 : 0; }
-
-// rows w*BT_W .. min(T, w*BT_W + BT_W) - 1, dwords base .. base + BAND - 1 of each (row_dw dwords per row), into registers
-template <int BAND>
-__device__ __forceinline__ void load_band(uint32_t (&wreg)[BAND], const uint32_t* bp_utt, int row_dw, int w, int T, int base,
-                                          int lane) {
-    const int w0 = w * BT_W;
-    const int rows = T - w0 < BT_W ? T - w0 : BT_W;
-#pragma unroll
-    for (int m = 0; m < BAND; ++m) {
-        const int i = m * 64 + lane;  // i = row * BAND + c
-        const int row = i / BAND;
-        const int c = i - row * BAND;
-        wreg[m] = (row < rows && base + c < row_dw) ? bp_utt[(long)(w0 + row) * row_dw + base + c] : 0u;
-    }
-}
 
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void asg_align_long_kernel(const float* __restrict__ logq, const float* __restrict__ trans,
@@ -75,9 +60,7 @@ __global__ __launch_bounds__(64 * NW) void asg_align_long_kernel(const float* __
                                                                  float* __restrict__ score, uint32_t* __restrict__ bp_hbm,
                                                                  int t_out, int k, int l_max) {
     constexpr int NT = 64 * NW;   // threads
-    constexpr int PRE = CH / NW;  // staged logq values per thread and chunk (CH * 64 / NT)
     constexpr int BAND = LongBand<NW>::DW;
-    static_assert(CH % NW == 0, "a chunk is staged by whole rounds of the work-group");
     __shared__ LongLds<NW> lds;
 
     const int b = blockIdx.x;
@@ -96,67 +79,38 @@ __global__ __launch_bounds__(64 * NW) void asg_align_long_kernel(const float* __
         return;
     }
 
-    // per-thread states: the emission column, the stay score and the score of the move into the state.  A state beyond the
-    // label stays at -inf for good (-inf + 0, and a move that adds -inf)
+    // per-thread states: thread i holds states 8 i .. 8 i + 7 with their emission column, stay score and move score (lattice.h)
     int col[NS];
     float gs[NS], ga[NS], d[NS];
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        const int s = tid * NS + j;
-        col[j] = 0;
-        gs[j] = 0.f;
-        ga[j] = -INFINITY;
-        d[j] = -INFINITY;
-        if (s < L) {
-            const int c = clamp_label(lab[s], k);
-            col[j] = c;
-            gs[j] = trans[c * k + c];
-            if (s > 0) ga[j] = trans[clamp_label(lab[s - 1], k) * k + c];
-        }
-    }
+    asg_states_init<NS>(col, gs, ga, lab, tid * NS, L, k, trans);
     const float* lq = logq + (long)b * t_out * k;
-    if (tid == 0) d[0] = init[col[0]] + lq[col[0]];  // frame 0: only state 0
+    // frame 0: only state 0 is open (here and not in a helper: see asg_states_init)
+#pragma unroll
+    for (int j = 0; j < NS; ++j) d[j] = tid * NS + j == 0 ? init[col[0]] + lq[col[0]] : -INFINITY;
     if (tid < 32) lds.edge[tid >> 4][tid & 15] = -INFINITY;  // frame 0: nothing at any wave's highest state but -inf
 
-    float pre[PRE];
-#pragma unroll
-    for (int m = 0; m < PRE; ++m) {  // chunks start at frame 1
-        const int i = m * NT + tid;  // frame i >> 6 of the chunk, class i & 63
-        const int t = 1 + (i >> 6) < T ? 1 + (i >> 6) : T - 1;
-        pre[m] = (i & 63) < k ? lq[(long)t * k + (i & 63)] : 0.f;
-    }
+    EmissionStager<NT> stg;
+    stg.prefetch(lq, 1, T, k, wave, lane);  // chunks start at frame 1
     constexpr int row_dw = WAVE_DW * NW;
     uint32_t* bp_utt = bp_hbm + (long)b * t_out * row_dw;
-    for (int t0 = 1; t0 < T; t0 += CH) {
+    for (int t0 = 1; t0 < T; t0 += ALIGN_CH) {
         // (the barrier that ended the previous chunk's last frame: every wave is done with the old rows)
-#pragma unroll
-        for (int m = 0; m < PRE; ++m) lds.em[m * NT + tid] = pre[m];
+        stg.store(lds.em, wave, lane);
         __syncthreads();
-        if (t0 + CH < T) {
+        if (t0 + ALIGN_CH < T) stg.prefetch(lq, t0 + ALIGN_CH, T, k, wave, lane);
+        const int nf = T - t0 < ALIGN_CH ? T - t0 : ALIGN_CH;
 #pragma unroll
-            for (int m = 0; m < PRE; ++m) {
-                const int i = m * NT + tid;
-                const int t = t0 + CH + (i >> 6) < T ? t0 + CH + (i >> 6) : T - 1;
-                pre[m] = (i & 63) < k ? lq[(long)t * k + (i & 63)] : 0.f;
-            }
-        }
-        const int nf = T - t0 < CH ? T - t0 : CH;
-#pragma unroll
-        for (int f = 0; f < CH; ++f) {
+        for (int f = 0; f < ALIGN_CH; ++f) {
             if (f >= nf) continue;  // (uniform over the work-group; a break keeps the loop from unrolling)
             const int t = t0 + f;
-            const float* e = lds.em + f * 64;
             float lo = dpp_float_from_lower_lane(d[NS - 1], -INFINITY);  // state NS tid - 1
             if (NW > 1 && lane == 0 && wave > 0) lo = lds.edge[(t + 1) & 1][wave - 1];  // written after frame t - 1
+            uint64_t word[NS];
+            asg_frame<NS>(col, gs, ga, d, lds.em + f * 64, lo, word);
             uint64_t keep = 0;  // lane j < NS keeps word j of the wave
 #pragma unroll
-            for (int j = NS - 1; j >= 0; --j) {  // descending: d[j-1] still holds frame t-1
-                const float stay = d[j] + gs[j];
-                const float move = (j >= 1 ? d[j - 1] : lo) + ga[j];
-                const bool mv = move > stay;
-                const uint64_t word = __ballot(mv);
-                if (lane == j) keep = word;
-                d[j] = (mv ? move : stay) + e[col[j]];
+            for (int j = 0; j < NS; ++j) {
+                if (lane == j) keep = word[j];
             }
             if (NW > 1 && lane == 63) lds.edge[t & 1][wave] = d[NS - 1];
             if (lane < NS) ((uint64_t*)(bp_utt + (long)t * row_dw))[wave * NS + lane] = keep;
@@ -184,16 +138,15 @@ __global__ __launch_bounds__(64 * NW) void asg_align_long_kernel(const float* __
     uint32_t wreg[BAND];
     int wave_cur = band_wave(s), wave_next = 0;
     if (wave == 0) {
-        load_band<BAND>(wreg, bp_utt, row_dw, nwin - 1, T, wave_cur * WAVE_DW, lane);
-#pragma unroll
-        for (int m = 0; m < BAND; ++m) lds.win[(nwin - 1) & 1][m * 64 + lane] = wreg[m];
+        load_band(wreg, bp_utt, row_dw, nwin - 1, T, wave_cur * WAVE_DW, lane);
+        store_band(wreg, lds.win[(nwin - 1) & 1], lane);
     }
     for (int w = nwin - 1; w >= 0; --w) {
         const int w0 = w * BT_W;
         const int w1 = T - w0 < BT_W ? T : w0 + BT_W;
         if (wave == 0 && w > 0) {  // s is the state at frame w1 - 1: the window below stays within [s - 128, s]
             wave_next = band_wave(s);
-            load_band<BAND>(wreg, bp_utt, row_dw, w - 1, T, wave_next * WAVE_DW, lane);
+            load_band(wreg, bp_utt, row_dw, w - 1, T, wave_next * WAVE_DW, lane);
         }
         __syncthreads();
         if (wave == 0) {
@@ -208,8 +161,7 @@ __global__ __launch_bounds__(64 * NW) void asg_align_long_kernel(const float* __
             }
             if (w0 + lane < w1) prow[w0 + lane] = mine;
             if (w > 0) {
-#pragma unroll
-                for (int m = 0; m < BAND; ++m) lds.win[(w - 1) & 1][m * 64 + lane] = wreg[m];
+                store_band(wreg, lds.win[(w - 1) & 1], lane);
                 wave_cur = wave_next;
             }
         }

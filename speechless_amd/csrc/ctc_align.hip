@@ -8,9 +8,10 @@
 // holds states l*NJ .. l*NJ + NJ - 1; NJ = 4 / 8 / 16 for S = 2L+1 <= 256 / 512 / 1024, as ctc_grad_kernel<NJ, ...> picks
 // by l_max).  Per frame: the highest state of the lane below arrives by one DPP wave_shr:1 move (a lane's first state
 // is a blank, which never skips), every state takes max(stay, s-1, s-2) with the tie rule and adds its emission (one
-// exact max chain + ONE rounded add: no FMA can form), and the 2-bit backpointers of the lane's NJ states -- one byte /
-// short / dword -- are stored as one row of 16*NJ bytes per frame in which state s sits at bits 2s.  Emissions come from LDS: the wave stages CH frames of logq rows (k <= 64
-// floats, one coalesced read per frame) while it works on the previous CH frames.
+// exact max chain + ONE rounded add: no FMA can form -- ctc_frame of lattice.h, which ctc_align_long.hip runs too), and the 2-bit
+// backpointers of the lane's NJ states -- one byte / short / dword -- are stored as one row of 16*NJ bytes per frame in which
+// state s sits at bits 2s.  Emissions come from LDS: the wave stages ALIGN_CH frames of logq rows (k <= 64 floats, one coalesced
+// read per frame) while it works on the previous ALIGN_CH frames (EmissionStager of lattice.h).
 //   BP_LDS = 1: the T' rows fit the work-group's LDS (config 3: 500 frames x 128 bytes) and the backtrace reads them there.
 //   BP_LDS = 0: rows go to the workspace in HBM; the backtrace copies windows of BT_W frames (the whole rows: contiguous
 //   bytes) into LDS, the next window's loads in flight while the current one is resolved, so that no frame of the T'-long
@@ -20,9 +21,6 @@
 #include "lattice.h"
 
 namespace {
-
-constexpr int CH = 16;  // frames of logq per LDS staging chunk
-constexpr int LDS_MAX = 160 * 1024;
 
 template <int NJ>
 struct BpWord;
@@ -35,7 +33,7 @@ struct BpWord<16> { typedef uint32_t T; };
 
 __host__ __device__ constexpr int row_bytes(int nj) { return 16 * nj; }  // 64 lanes x 2 bits x nj states
 
-// LDS: [logq chunk CH x 64 floats][final scores 64*NJ floats][backpointer rows: T' rows (BP_LDS) or two windows of BT_W rows]
+// LDS: [logq chunk ALIGN_CH x 64 floats][final scores 64*NJ floats][backpointer rows: T' rows (BP_LDS) or two windows of BT_W rows]
 template <int NJ, bool BP_LDS>
 __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__ logq, const int32_t* __restrict__ labels,
                                                         const int32_t* __restrict__ label_len,
@@ -46,16 +44,14 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
     constexpr int R = row_bytes(NJ);
     extern __shared__ float smem[];
     float* em = smem;
-    float* fin = em + CH * 64;
+    float* fin = em + ALIGN_CH * 64;
     uint8_t* rows = (uint8_t*)(fin + 64 * NJ);
 
     const int b = blockIdx.x;
     const int lane = threadIdx.x;
     const int blank = k - 1;
-    int L = label_len[b];
-    L = L < 0 ? 0 : (L > l_max ? l_max : L);
-    int T = input_len[b];
-    T = T < 0 ? 0 : (T > t_out ? t_out : T);
+    int L, T;
+    clamp_lengths(label_len, input_len, b, l_max, t_out, L, T);
     const int S = 2 * L + 1;
     const int32_t* lab = labels + (long)b * l_max;
     int32_t* prow = path + (long)b * t_out;
@@ -74,82 +70,34 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
         return;
     }
 
-    // per-lane lattice: label columns (as LDS float offsets) of the odd states, skip permissions
+    // per-lane lattice: lane l holds states l*NJ .. l*NJ + NJ - 1, at the virtual frame -1 (lattice.h)
     int col[NJ / 2];
     bool skip[NJ / 2];
-#pragma unroll
-    for (int q = 0; q < NJ / 2; ++q) {
-        const int s = lane * NJ + 2 * q + 1;
-        const int pos = (s - 1) >> 1;
-        int c = blank;
-        bool sk = false;
-        if (s < S) {
-            c = lab[pos];
-            c = c < 0 ? 0 : (c > blank ? blank : c);
-            sk = pos >= 1 && lab[pos - 1] != lab[pos];
-        }
-        col[q] = c;
-        skip[q] = sk;
-    }
+    float d[NJ];
+    ctc_states_init<NJ>(col, skip, lab, lane * NJ, S, k);
     // delta of a virtual frame -1: state 0 at 0, the rest at -inf, so that frame 0 yields delta_0(0) = logq_0(blank) and
     // delta_0(1) = logq_0(l_0) exactly (0 + x == x) and every other state -inf
-    float d[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) d[j] = -INFINITY;
-    if (lane == 0) d[0] = 0.f;
+    for (int j = 0; j < NJ; ++j) d[j] = lane * NJ + j == 0 ? 0.f : -INFINITY;
 
     const float* lq = logq + (long)b * t_out * k;
-    const bool col_on = lane < k;
-    float pre[CH];
-#pragma unroll
-    for (int f = 0; f < CH; ++f) {
-        const int t = f < T ? f : T - 1;
-        pre[f] = col_on ? lq[(long)t * k + lane] : 0.f;
-    }
+    EmissionStager<64> stg;
+    stg.prefetch(lq, 0, T, k, 0, lane);
     Word* bp_lds = (Word*)rows + lane;
     Word* bp_g = (Word*)(bp_hbm + (long)b * t_out * R) + lane;
-    for (int t0 = 0; t0 < T; t0 += CH) {
+    for (int t0 = 0; t0 < T; t0 += ALIGN_CH) {
         __syncthreads();
-#pragma unroll
-        for (int f = 0; f < CH; ++f) em[f * 64 + lane] = pre[f];
+        stg.store(em, 0, lane);
         __syncthreads();
-        if (t0 + CH < T) {
+        if (t0 + ALIGN_CH < T) stg.prefetch(lq, t0 + ALIGN_CH, T, k, 0, lane);
+        const int nf = T - t0 < ALIGN_CH ? T - t0 : ALIGN_CH;
 #pragma unroll
-            for (int f = 0; f < CH; ++f) {
-                const int t = t0 + CH + f < T ? t0 + CH + f : T - 1;
-                pre[f] = col_on ? lq[(long)t * k + lane] : 0.f;
-            }
-        }
-        const int nf = T - t0 < CH ? T - t0 : CH;
-#pragma unroll
-        for (int f = 0; f < CH; ++f) {
+        for (int f = 0; f < ALIGN_CH; ++f) {
             if (f >= nf) continue;  // (wave-uniform; a break keeps the loop from unrolling)
             const float* e = em + f * 64;
-            const float eb = e[blank];
             // state lane*NJ - 1: s-1 of the lane's first state (even: never skips) and s-2 of its second
             const float lo1 = dpp_float_from_lower_lane(d[NJ - 1], -INFINITY);
-            uint32_t word = 0;
-#pragma unroll
-            for (int j = NJ - 1; j >= 0; --j) {  // descending: d[j-1], d[j-2] still hold frame t-1
-                const float p1 = j >= 1 ? d[j - 1] : lo1;
-                float best = d[j];
-                uint32_t bp = 0;
-                if (p1 > best) {
-                    best = p1;
-                    bp = 1;
-                }
-                if (j & 1) {
-                    const float p2 = j >= 2 ? d[j - 2] : lo1;
-                    if (skip[j >> 1] && p2 > best) {
-                        best = p2;
-                        bp = 2;
-                    }
-                    d[j] = best + e[col[j >> 1]];
-                } else {
-                    d[j] = best + eb;
-                }
-                word |= bp << (2 * j);
-            }
+            const uint32_t word = ctc_frame<NJ>(col, skip, d, e, e[blank], lo1);
             const int t = t0 + f;
             if (BP_LDS)
                 bp_lds[(long)t * (R / sizeof(Word))] = (Word)word;
@@ -200,16 +148,16 @@ __global__ __launch_bounds__(64) void ctc_align_kernel(const float* __restrict__
 
 template <int NJ, bool BP_LDS>
 size_t align_lds_bytes(int t_out) {
-    return (size_t)(CH * 64 + 64 * NJ) * sizeof(float) + (size_t)(BP_LDS ? t_out : 2 * BT_W) * row_bytes(NJ);
+    return (size_t)(ALIGN_CH * 64 + 64 * NJ) * sizeof(float) + (size_t)(BP_LDS ? t_out : 2 * BT_W) * row_bytes(NJ);
 }
 
 int states_per_lane(int l_max) { return 2 * l_max + 1 <= 256 ? 4 : (2 * l_max + 1 <= 512 ? 8 : 16); }
 
 bool bp_in_lds(int nj, int t_out) {
     switch (nj) {
-        case 4: return align_lds_bytes<4, true>(t_out) <= (size_t)LDS_MAX;
-        case 8: return align_lds_bytes<8, true>(t_out) <= (size_t)LDS_MAX;
-        default: return align_lds_bytes<16, true>(t_out) <= (size_t)LDS_MAX;
+        case 4: return align_lds_bytes<4, true>(t_out) <= (size_t)ALIGN_LDS_MAX;
+        case 8: return align_lds_bytes<8, true>(t_out) <= (size_t)ALIGN_LDS_MAX;
+        default: return align_lds_bytes<16, true>(t_out) <= (size_t)ALIGN_LDS_MAX;
     }
 }
 
@@ -218,7 +166,8 @@ int launch_align(const float* logq, const int32_t* labels, const int32_t* label_
                  float* score, void* workspace, int batch, int t_out, int k, int l_max, hipStream_t s) {
     static bool attr_set = false;
     if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)ctc_align_kernel<NJ, BP_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)ctc_align_kernel<NJ, BP_LDS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   ALIGN_LDS_MAX);
         attr_set = true;
     }
     const size_t lds = align_lds_bytes<NJ, BP_LDS>(t_out);

@@ -11,26 +11,28 @@
 // wave, double-buffered by frame parity (lane 63 of wave w writes slot [t & 1][w] after frame t, lane 0 of wave w + 1 reads it
 // in frame t + 1), which costs ONE work-group barrier per frame.  Every barrier is uniform: all trip counts depend on the
 // recording only.  Per state and frame: max(stay, s-1, s-2) with the strict-> tie rule and ONE rounded add (no multiply: nothing
-// to contract).  Emissions come from LDS: the work-group stages CH frames of logq rows (k <= 64 floats) once for all waves while
-// the next CH frames are in flight in registers.
-// Backpointers: 2 bits per state and frame, a thread's 16 states = one dword, a frame's row = 256 NW bytes stored coalesced to the
-// workspace in HBM (state s at bits 2 (s & 15) of dword s >> 4).
+// to contract) -- ctc_frame of lattice.h, the very step of ctc_align.hip.  Emissions come from LDS: the work-group stages
+// ALIGN_CH frames of logq rows (k <= 64 floats) once for all waves while the next ALIGN_CH frames are in flight in registers
+// (EmissionStager of lattice.h, with all NW waves at work).
+// Backpointers: 2 bits per state and frame, a thread's 16 states = one dword, a frame's row = 256 NW bytes stored coalesced to
+// the workspace in HBM (state s at bits 2 (s & 15) of dword s >> 4).
 // Backtrace: wave 0 (the other waves only keep the barriers uniform).  The path drops at most two states per frame, so a window
 // of BT_W = 64 frames whose top frame is at state s touches states [s - 128, s] only, and the window below it [s - 256, s]: 17
-// dwords of each row.  That band of the NEXT window is loaded into registers before the current window is resolved out of LDS, so
-// no step of the T'-long chain waits on a dependent HBM load.  Lane t - w0 keeps frame t's state: one coalesced store per window.
+// dwords of each row.  That band of the NEXT window is loaded into registers (load_band / store_band of lattice.h) before the
+// current window is resolved out of LDS, so no step of the T'-long chain waits on a dependent HBM load.  Lane t - w0 keeps frame
+// t's state: one coalesced store per window.
 #include "lattice.h"
 
 namespace {
 
-constexpr int CH = 16;       // frames of logq per LDS staging chunk
 constexpr int NJ = 16;       // lattice states per thread
 constexpr int BAND = 17;     // backpointer dwords of a row that two windows below a state can touch (2 * 2 * BT_W / NJ + 1)
 constexpr int L_LIMIT = 8191;
 
-// LDS: [logq chunk CH x 64 floats][boundary slots 2 x 16][reduction 16 ints][end scores 2][backtrace windows 2 x BT_W x BAND dwords]
+// LDS: [logq chunk ALIGN_CH x 64 floats][boundary slots 2 x 16][reduction 16 ints][end scores 2]
+//      [backtrace windows 2 x BT_W x BAND dwords]
 struct LongLds {
-    float em[CH * 64];
+    float em[ALIGN_CH * 64];
     float edge[2][16];
     int reps[16];
     float fin[2];
@@ -39,20 +41,6 @@ struct LongLds {
 
 __device__ __forceinline__ int band_base(int s) { return s > 256 ? (s - 256) >> 4 : 0; }  // first dword of [s - 256, s]
 
-// rows w*BT_W .. min(T, w*BT_W + BT_W) - 1, dwords base .. base + BAND - 1 of each (row_dw dwords per row), into registers
-__device__ __forceinline__ void load_band(uint32_t (&wreg)[BAND], const uint32_t* bp_utt, int row_dw, int w, int T, int base,
-                                          int lane) {
-    const int w0 = w * BT_W;
-    const int rows = T - w0 < BT_W ? T - w0 : BT_W;
-#pragma unroll
-    for (int m = 0; m < BAND; ++m) {
-        const int i = m * 64 + lane;  // i = row * BAND + c
-        const int row = i / BAND;
-        const int c = i - row * BAND;
-        wreg[m] = (row < rows && base + c < row_dw) ? bp_utt[(long)(w0 + row) * row_dw + base + c] : 0u;
-    }
-}
-
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void ctc_align_long_kernel(const float* __restrict__ logq, const int32_t* __restrict__ labels,
                                                                  const int32_t* __restrict__ label_len,
@@ -60,8 +48,6 @@ __global__ __launch_bounds__(64 * NW) void ctc_align_long_kernel(const float* __
                                                                  float* __restrict__ score, uint32_t* __restrict__ bp_hbm, int t_out,
                                                                  int k, int l_max) {
     constexpr int NT = 64 * NW;        // threads = dwords of a backpointer row
-    constexpr int PRE = CH / NW;       // staged logq values per thread and chunk (CH * 64 / NT)
-    static_assert(CH % NW == 0, "a chunk is staged by whole rounds of the work-group");
     __shared__ LongLds lds;
 
     const int b = blockIdx.x;
@@ -95,84 +81,36 @@ __global__ __launch_bounds__(64 * NW) void ctc_align_long_kernel(const float* __
         return;
     }
 
-    // per-thread lattice: label columns of the odd states, skip permissions
+    // per-thread lattice: thread i holds states 16 i .. 16 i + 15, at the virtual frame -1 (lattice.h)
     int col[NJ / 2];
     bool skip[NJ / 2];
-#pragma unroll
-    for (int q = 0; q < NJ / 2; ++q) {
-        const int s = tid * NJ + 2 * q + 1;
-        const int pos = (s - 1) >> 1;
-        int c = blank;
-        bool sk = false;
-        if (s < S) {
-            c = clamp_label(lab[pos], k);
-            sk = pos >= 1 && lab[pos - 1] != lab[pos];
-        }
-        col[q] = c;
-        skip[q] = sk;
-    }
+    float d[NJ];
+    ctc_states_init<NJ>(col, skip, lab, tid * NJ, S, k);
     // delta of a virtual frame -1: state 0 at 0, the rest at -inf, so that frame 0 yields delta_0(0) = logq_0(blank) and
     // delta_0(1) = logq_0(l_0) exactly (0 + x == x) and every other state -inf
-    float d[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) d[j] = -INFINITY;
-    if (tid == 0) d[0] = 0.f;
+    for (int j = 0; j < NJ; ++j) d[j] = tid * NJ + j == 0 ? 0.f : -INFINITY;
 
     const float* lq = logq + (long)b * t_out * k;
-    float pre[PRE];
-#pragma unroll
-    for (int m = 0; m < PRE; ++m) {
-        const int i = m * NT + tid;  // frame i >> 6 of the chunk, class i & 63
-        const int t = (i >> 6) < T ? (i >> 6) : T - 1;
-        pre[m] = (i & 63) < k ? lq[(long)t * k + (i & 63)] : 0.f;
-    }
+    EmissionStager<NT> stg;
+    stg.prefetch(lq, 0, T, k, wave, lane);
     const int row_dw = NT;
     uint32_t* bp_utt = bp_hbm + (long)b * t_out * row_dw;
-    for (int t0 = 0; t0 < T; t0 += CH) {
+    for (int t0 = 0; t0 < T; t0 += ALIGN_CH) {
         // (the barrier that ended the previous chunk's last frame: every wave is done with the old rows)
-#pragma unroll
-        for (int m = 0; m < PRE; ++m) lds.em[m * NT + tid] = pre[m];
+        stg.store(lds.em, wave, lane);
         __syncthreads();
-        if (t0 + CH < T) {
+        if (t0 + ALIGN_CH < T) stg.prefetch(lq, t0 + ALIGN_CH, T, k, wave, lane);
+        const int nf = T - t0 < ALIGN_CH ? T - t0 : ALIGN_CH;
 #pragma unroll
-            for (int m = 0; m < PRE; ++m) {
-                const int i = m * NT + tid;
-                const int t = t0 + CH + (i >> 6) < T ? t0 + CH + (i >> 6) : T - 1;
-                pre[m] = (i & 63) < k ? lq[(long)t * k + (i & 63)] : 0.f;
-            }
-        }
-        const int nf = T - t0 < CH ? T - t0 : CH;
-#pragma unroll
-        for (int f = 0; f < CH; ++f) {
+        for (int f = 0; f < ALIGN_CH; ++f) {
             if (f >= nf) continue;  // (uniform over the work-group; a break keeps the loop from unrolling)
             const int t = t0 + f;
             const float* e = lds.em + f * 64;
-            const float eb = e[blank];
             // state 16 tid - 1: s-1 of the thread's first state (even: never skips) and s-2 of its second
             float lo1 = dpp_float_from_lower_lane(d[NJ - 1], -INFINITY);
             if (NW > 1 && lane == 0 && wave > 0) lo1 = lds.edge[(t + 1) & 1][wave - 1];  // written after frame t - 1
-            uint32_t word = 0;
-#pragma unroll
-            for (int j = NJ - 1; j >= 0; --j) {  // descending: d[j-1], d[j-2] still hold frame t-1
-                const float p1 = j >= 1 ? d[j - 1] : lo1;
-                float best = d[j];
-                uint32_t bp = 0;
-                if (p1 > best) {
-                    best = p1;
-                    bp = 1;
-                }
-                if (j & 1) {
-                    const float p2 = j >= 2 ? d[j - 2] : lo1;
-                    if (skip[j >> 1] && p2 > best) {
-                        best = p2;
-                        bp = 2;
-                    }
-                    d[j] = best + e[col[j >> 1]];
-                } else {
-                    d[j] = best + eb;
-                }
-                word |= bp << (2 * j);
-            }
+            const uint32_t word = ctc_frame<NJ>(col, skip, d, e, e[blank], lo1);
             if (NW > 1 && lane == 63) lds.edge[t & 1][wave] = d[NJ - 1];
             bp_utt[(long)t * row_dw + tid] = word;
             __syncthreads();  // the frame's barrier: boundary slots written, and (last frame of a chunk) the rows read
@@ -196,8 +134,7 @@ __global__ __launch_bounds__(64 * NW) void ctc_align_long_kernel(const float* __
     int base_cur = band_base(s), base_next = 0;
     if (wave == 0) {
         load_band(wreg, bp_utt, row_dw, nwin - 1, T, base_cur, lane);
-#pragma unroll
-        for (int m = 0; m < BAND; ++m) lds.win[(nwin - 1) & 1][m * 64 + lane] = wreg[m];
+        store_band(wreg, lds.win[(nwin - 1) & 1], lane);
     }
     for (int w = nwin - 1; w >= 0; --w) {
         const int w0 = w * BT_W;
@@ -219,8 +156,7 @@ __global__ __launch_bounds__(64 * NW) void ctc_align_long_kernel(const float* __
             }
             if (w0 + lane < w1) prow[w0 + lane] = mine;
             if (w > 0) {
-#pragma unroll
-                for (int m = 0; m < BAND; ++m) lds.win[(w - 1) & 1][m * 64 + lane] = wreg[m];
+                store_band(wreg, lds.win[(w - 1) & 1], lane);
                 base_cur = base_next;
             }
         }

@@ -1026,6 +1026,43 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                      self.asg_adam_m.data_ptr(), self.asg_adam_v.data_ptr(), self.asg_params.numel(), self.adam_iterations,
                      self._lr_now(), self.beta_1, self.beta_2, self.adam_epsilon, self._stream())
 
+    def _align_labels(self, label_batch, label_lengths, batch, asg, in_len=None, max_letters=None, too_long_text=None):
+        """What the four forced aligners ask of a label batch: (B, Lmax) with B lengths (and, for a _long method, the B
+        prediction lengths in_len and at most max_letters letters, too_long_text being the error's text), every length
+        within the row, every index in [0, K - 1) under CTC, whose blank is K - 1, and in [0, K) under ASG.  Returns
+        (labels, lab_len), int32 numpy."""
+        labels = np.asarray(label_batch, dtype=np.int32)
+        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
+        if labels.ndim != 2 or labels.shape[0] != batch or lab_len.shape[0] != batch or \
+                (in_len is not None and in_len.shape[0] != batch):
+            raise ValueError("label batch must be (B, Lmax) with B lengths" if in_len is None else
+                             "label batch must be (B, Lmax) with B label lengths and B prediction lengths")
+        if max_letters is not None and labels.shape[1] > max_letters:
+            raise ValueError(too_long_text.format(labels.shape[1], max_letters))
+        end = self.grapheme_set_size if asg else self.grapheme_set_size - 1
+        for i in range(batch):
+            if not 0 <= lab_len[i] <= labels.shape[1]:
+                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
+            row = labels[i, :lab_len[i]]
+            if row.size and (row.min() < 0 or row.max() >= end):
+                raise ValueError("label {} holds an index outside [0, {})".format(i, end) +
+                                 ("" if asg else " (blank is {})".format(end)))
+        return labels, lab_len
+
+    @staticmethod
+    def _fill_align_labels(label_tensor, length_tensor, labels, lab_len):
+        """the aligners' label tensors (at least as wide as labels): zeros, the labels, their lengths"""
+        label_tensor.zero_()
+        label_tensor[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
+        length_tensor.copy_(torch.from_numpy(lab_len))
+
+    def _long_logq(self, logq):
+        """the logq argument of the _long aligners, checked -> (contiguous logq, B, T')"""
+        k = self.grapheme_set_size
+        if logq.dim() != 3 or logq.shape[2] != k or logq.dtype != torch.float32 or not logq.is_cuda:
+            raise ValueError("logq must be a float32 (B, T', {}) tensor on the device".format(k))
+        return logq.contiguous(), int(logq.shape[0]), int(logq.shape[1])
+
     def ctc_align(self, label_batch, label_lengths, prediction_lengths):
         """CTC forced alignment (Viterbi) of the labels on the current buffer set's logq -- the distribution ctc() sees --
         after forward().  label_batch: int (B, Lmax) padded with anything; lengths: (B,) or (B, 1).  Returns (paths int32
@@ -1035,22 +1072,10 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         if self.criterion == "asg":
             raise ValueError("criterion='asg': forced alignment runs over the CTC lattice (blank = K - 1); not supported")
         buf = self.cur
-        labels = np.asarray(label_batch, dtype=np.int32)
-        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
-        if labels.ndim != 2 or labels.shape[0] != buf.batch or lab_len.shape[0] != buf.batch:
-            raise ValueError("label batch must be (B, Lmax) with B lengths")
+        labels, lab_len = self._align_labels(label_batch, label_lengths, buf.batch, asg=False)
         k = self.grapheme_set_size
-        for i in range(buf.batch):
-            if not 0 <= lab_len[i] <= labels.shape[1]:
-                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
-            row = labels[i, :lab_len[i]]
-            if row.size and (row.min() < 0 or row.max() >= k - 1):
-                raise ValueError("label {} holds an index outside [0, {}) (blank is {})".format(i, k - 1, k - 1))
-        l_max = max(int(labels.shape[1]), 1)
-        buf.ensure_align(self, l_max)
-        buf.align_labels.zero_()
-        buf.align_labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
-        buf.align_label_len.copy_(torch.from_numpy(lab_len))
+        buf.ensure_align(self, max(int(labels.shape[1]), 1))
+        self._fill_align_labels(buf.align_labels, buf.align_label_len, labels, lab_len)
         self.set_input_lengths(prediction_lengths)
         path = buf._align_path_flat[:buf.batch * buf.t_out]
         self._launch("align", "sl_ctc_align", buf.logq.data_ptr(), buf.align_labels.data_ptr(), buf.align_label_len.data_ptr(),
@@ -1124,31 +1149,16 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         if self.criterion == "asg":
             raise ValueError("criterion='asg': forced alignment runs over the CTC lattice (blank = K - 1); not supported")
         k = self.grapheme_set_size
-        if logq.dim() != 3 or logq.shape[2] != k or logq.dtype != torch.float32 or not logq.is_cuda:
-            raise ValueError("logq must be a float32 (B, T', {}) tensor on the device".format(k))
-        logq = logq.contiguous()
-        batch, t_out = int(logq.shape[0]), int(logq.shape[1])
-        labels = np.asarray(label_batch, dtype=np.int32)
-        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
+        logq, batch, t_out = self._long_logq(logq)
         in_len = np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)
-        if labels.ndim != 2 or labels.shape[0] != batch or lab_len.shape[0] != batch or in_len.shape[0] != batch:
-            raise ValueError("label batch must be (B, Lmax) with B label lengths and B prediction lengths")
-        if labels.shape[1] > longform.ALIGN_MAX_LABEL:
-            raise ValueError("labels of {} letters: forced alignment takes at most {} (sl_ctc_align_long)".format(
-                labels.shape[1], longform.ALIGN_MAX_LABEL))
-        for i in range(batch):
-            if not 0 <= lab_len[i] <= labels.shape[1]:
-                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
-            row = labels[i, :lab_len[i]]
-            if row.size and (row.min() < 0 or row.max() >= k - 1):
-                raise ValueError("label {} holds an index outside [0, {}) (blank is {})".format(i, k - 1, k - 1))
+        labels, lab_len = self._align_labels(
+            label_batch, label_lengths, batch, asg=False, in_len=in_len, max_letters=longform.ALIGN_MAX_LABEL,
+            too_long_text="labels of {} letters: forced alignment takes at most {} (sl_ctc_align_long)")
         if self._long_align is None:
             self._long_align = _LongAlignBuffers(self.device)
         la = self._long_align
         need = la.ensure(batch, t_out, max(int(labels.shape[1]), 1))
-        la.labels.zero_()
-        la.labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
-        la.label_len.copy_(torch.from_numpy(lab_len))
+        self._fill_align_labels(la.labels, la.label_len, labels, lab_len)
         la.input_len.copy_(torch.from_numpy(in_len))
         path = la.path[:batch * t_out]
         self._launch("align_long", "sl_ctc_align_long", logq.data_ptr(), la.labels.data_ptr(), la.label_len.data_ptr(),
@@ -1166,31 +1176,16 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         from .buffers import _LongAlignBuffers
         self._require_asg("asg_align_long()")
         k = self.grapheme_set_size
-        if logq.dim() != 3 or logq.shape[2] != k or logq.dtype != torch.float32 or not logq.is_cuda:
-            raise ValueError("logq must be a float32 (B, T', {}) tensor on the device".format(k))
-        logq = logq.contiguous()
-        batch, t_out = int(logq.shape[0]), int(logq.shape[1])
-        labels = np.asarray(label_batch, dtype=np.int32)
-        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
+        logq, batch, t_out = self._long_logq(logq)
         in_len = np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)
-        if labels.ndim != 2 or labels.shape[0] != batch or lab_len.shape[0] != batch or in_len.shape[0] != batch:
-            raise ValueError("label batch must be (B, Lmax) with B label lengths and B prediction lengths")
-        if labels.shape[1] > longform.ASG_ALIGN_MAX_LABEL:
-            raise ValueError("labels of {} graphemes: ASG forced alignment takes at most {} (sl_asg_align_long)".format(
-                labels.shape[1], longform.ASG_ALIGN_MAX_LABEL))
-        for i in range(batch):
-            if not 0 <= lab_len[i] <= labels.shape[1]:
-                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
-            row = labels[i, :lab_len[i]]
-            if row.size and (row.min() < 0 or row.max() >= k):
-                raise ValueError("label {} holds an index outside [0, {})".format(i, k))
+        labels, lab_len = self._align_labels(
+            label_batch, label_lengths, batch, asg=True, in_len=in_len, max_letters=longform.ASG_ALIGN_MAX_LABEL,
+            too_long_text="labels of {} graphemes: ASG forced alignment takes at most {} (sl_asg_align_long)")
         if self._long_align is None:
             self._long_align = _LongAlignBuffers(self.device, "sl_asg_align_long_workspace_bytes")
         la = self._long_align
         need = la.ensure(batch, t_out, max(int(labels.shape[1]), 1))
-        la.labels.zero_()
-        la.labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
-        la.label_len.copy_(torch.from_numpy(lab_len))
+        self._fill_align_labels(la.labels, la.label_len, labels, lab_len)
         la.input_len.copy_(torch.from_numpy(in_len))
         path = la.path[:batch * t_out]
         trans, init = self._asg_views(self.asg_params)
@@ -1243,22 +1238,10 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         (include/speechless_hip.h).  Uses tensors of its own: no gradient buffers, labels of asg() untouched."""
         self._require_asg("asg_align()")
         buf = self.cur
-        labels = np.asarray(label_batch, dtype=np.int32)
-        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
-        if labels.ndim != 2 or labels.shape[0] != buf.batch or lab_len.shape[0] != buf.batch:
-            raise ValueError("label batch must be (B, Lmax) with B lengths")
+        labels, lab_len = self._align_labels(label_batch, label_lengths, buf.batch, asg=True)
         k = self.grapheme_set_size
-        for i in range(buf.batch):
-            if not 0 <= lab_len[i] <= labels.shape[1]:
-                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
-            row = labels[i, :lab_len[i]]
-            if row.size and (row.min() < 0 or row.max() >= k):
-                raise ValueError("label {} holds an index outside [0, {})".format(i, k))
-        l_max = max(int(labels.shape[1]), 1)
-        buf.ensure_align(self, l_max, "sl_asg_align_workspace_bytes")
-        buf.align_labels.zero_()
-        buf.align_labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
-        buf.align_label_len.copy_(torch.from_numpy(lab_len))
+        buf.ensure_align(self, max(int(labels.shape[1]), 1), "sl_asg_align_workspace_bytes")
+        self._fill_align_labels(buf.align_labels, buf.align_label_len, labels, lab_len)
         self.set_input_lengths(prediction_lengths)
         path = buf._align_path_flat[:buf.batch * buf.t_out]
         trans, init = self._asg_views(self.asg_params)

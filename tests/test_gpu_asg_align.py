@@ -7,6 +7,7 @@ import pytest
 from test_asg import asg_viterbi
 from test_asg_align import F32, NEG_INF, asg_align_reference, random_inputs
 from test_gpu_asg import K_ASG, asg_net, examples, toy_case, toy_engine
+from test_gpu_ctc_align import lds_limit
 
 pytestmark = pytest.mark.gpu
 
@@ -101,13 +102,9 @@ def test_lengths_beyond_the_tensors_are_clamped(hip_lib):
 
 def test_backpointers_on_either_side_of_the_lds_limit(hip_lib):
     """The smallest t_out whose backpointers (one bit per state and frame, 16 states: 8 bytes per frame) leave LDS, and the
-    frame count below it.  The limit lies below 20 000 frames, so t_out itself reaches the HBM side."""
+    frame count below it, so t_out itself reaches the HBM side."""
     query = hip_lib.raw("sl_asg_align_workspace_bytes")
-    lo, hi = 1, 20000
-    assert query(2, lo, 16) == 0 and query(2, hi, 16) > 0
-    while hi - lo > 1:  # (monotonic in t_out)
-        mid = (lo + hi) // 2
-        lo, hi = (mid, hi) if query(2, mid, 16) == 0 else (lo, mid)
+    lo, hi = lds_limit(query, 2, 16)  # (the limit lies below 20 000 frames)
     assert query(2, hi, 16) == 2 * hi * 8
     for t, in_hbm in ((lo, False), (hi, True)):
         refs, _, _ = align_and_check(hip_lib, np.random.RandomState(t), 30, t, [16, 11], [t, t // 2 + 1], l_max=16,
@@ -117,6 +114,19 @@ def test_backpointers_on_either_side_of_the_lds_limit(hip_lib):
     t = 2470
     assert query(2, 2400, 257) == 0 and query(2, t, 257) == 2 * t * 64
     align_and_check(hip_lib, np.random.RandomState(9), 30, t, [257, 40], [t, 300], l_max=257, expect_workspace=True)
+
+
+@pytest.mark.parametrize("l_max,ns", [(128, 2), (256, 4)])
+def test_two_and_four_states_per_lane_with_backpointers_in_hbm(hip_lib, l_max, ns):
+    """asg_align_kernel<2, false> and <4, false>, which the test above leaves out: the l_max ARGUMENT picks the states per lane
+    and the first t_out past the LDS limit (9953 / 4961 frames, taken from the query) sends the rows of ns words to HBM.  The
+    longest label over all frames beside a short row with few windows."""
+    query = hip_lib.raw("sl_asg_align_workspace_bytes")
+    _, t = lds_limit(query, 2, l_max)
+    assert query(2, t, l_max) == 2 * t * 8 * ns
+    refs, _, _ = align_and_check(hip_lib, np.random.RandomState(l_max), 30, t, [l_max, l_max // 3], [t, t // 16 + 1],
+                                 l_max=l_max, expect_workspace=True)
+    assert all(np.isfinite(score) for score, _ in refs)
 
 
 def test_minus_infinity_scores_close_paths_without_a_nan(hip_lib):

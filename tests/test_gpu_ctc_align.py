@@ -73,16 +73,19 @@ def fuzz_case(rng, k, t, b, l_hi, kinds, tight=False):
     return logits, labels_list, input_len
 
 
+FUZZ_KINDS = ("uniform", "sharp", "collapse", "learnt", "wrong")
+# (t_out, rows, longest label, tight) of the fuzz cases, in the order in which one seeded stream draws them; also run through
+# sl_ctc_align_long by test_gpu_ctc_align_long.py
+FUZZ_SHAPES = [(300, 6, 100, False), (300, 4, 255, True), (1000, 4, 250, False), (4000, 3, 511, False), (4000, 2, 120, False)]
+
+
 @pytest.mark.parametrize("k", [29, 64])
 def test_align_kernel_bit_exact_on_fuzz_regimes(hip_lib, k):
     """Backpointers in LDS (300 / 1000 frames) and in HBM (4000 frames), 4 / 8 / 16 states per lane, all five regimes,
     tight labels, and rows that cannot be aligned (too many labels, repeats without room for the blank, T = 0)."""
     rng = np.random.RandomState(11 + k)
-    kinds = ("uniform", "sharp", "collapse", "learnt", "wrong")
-    shapes = [(300, 6, 100, False), (300, 4, 255, True), (1000, 4, 250, False), (4000, 3, 511, False),
-              (4000, 2, 120, False)]
-    for t, b, l_hi, tight in shapes:
-        logits, labels_list, input_len = fuzz_case(rng, k, t, b, l_hi, kinds, tight)
+    for t, b, l_hi, tight in FUZZ_SHAPES:
+        logits, labels_list, input_len = fuzz_case(rng, k, t, b, l_hi, FUZZ_KINDS, tight)
         logq, paths, scores = run_align_kernel(hip_lib, logits, labels_list, input_len)
         check_against_restatement(logq, labels_list, input_len, paths, scores, k)
     # infeasible rows next to feasible ones; empty labels; T = 0; input lengths beyond t_out (clamped)
@@ -96,6 +99,46 @@ def test_align_kernel_bit_exact_on_fuzz_regimes(hip_lib, k):
     assert np.all(paths[2][:17] == 0) and np.all(paths[2][17:] == -1)
     assert scores[3] == 0 and np.all(paths[3] == -1)
     assert scores[4] == -np.inf and np.all(paths[4] == -1)
+    check_against_restatement(logq, labels_list, input_len, paths, scores, k)
+
+
+def lds_limit(query, rows, l_max, beyond=20000):
+    """(the largest t_out whose backpointer rows stay in LDS, the smallest whose rows go to the workspace in HBM) for `rows`
+    utterances at this l_max, from a workspace query (sl_ctc_align's or sl_asg_align's), which is monotonic in t_out"""
+    lo, hi = 1, beyond
+    assert query(rows, lo, l_max) == 0 and query(rows, hi, l_max) > 0
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if query(rows, mid, l_max) == 0 else (lo, mid)
+    return lo, hi
+
+
+@pytest.mark.parametrize("in_hbm", [False, True])
+@pytest.mark.parametrize("l_max,nj", [(127, 4), (128, 8), (255, 8), (256, 16), (511, 16)])
+def test_every_kernel_instantiation_on_either_side_of_the_lds_limit(hip_lib, l_max, nj, in_hbm):
+    """All six ctc_align_kernel<NJ, BP_LDS>, chosen by the l_max ARGUMENT (4 / 8 / 16 states per lane on either side of where
+    the count changes, and the longest label) and by t_out: a few hundred frames with the backpointers in LDS, and the first
+    t_out at which they leave it (2481 / 1233 / 609 frames: 39 / 20 / 10 backtrace windows, the last one partial).  Three rows:
+    the longest label over all frames, a label with zero slack (T = L + repeats), and a short row; two regimes per row."""
+    sys.path.insert(0, str(ROOT / "tools"))
+    from fuzz_ctc import regime_logits
+    query = hip_lib.raw("sl_ctc_align_workspace_bytes")
+    last_lds, first_hbm = lds_limit(query, 3, l_max)
+    assert query(3, first_hbm, l_max) == 3 * first_hbm * 16 * nj  # (rows of 16 * NJ bytes: the instantiation meant)
+    k = 64 if in_hbm else 29
+    t = first_hbm if in_hbm else min(last_lds, max(300, l_max + l_max // 8 + 30))
+    assert (query(3, t, l_max) > 0) == in_hbm
+    rng = np.random.RandomState(1000 * l_max + in_hbm)
+    labels_list = [[int(c) for c in rng.randint(0, k - 1, size=n)] for n in (l_max, min(l_max, t // 2), l_max // 3)]
+    tight = labels_list[1]
+    input_len = [t, len(tight) + sum(a == b for a, b in zip(tight, tight[1:])), t // 3 + 5]
+    logits = np.zeros((3, t, k), dtype=np.float32)
+    for i, (label, t_b) in enumerate(zip(labels_list, input_len)):
+        first, second = rng.choice(FUZZ_KINDS, size=2, replace=False)
+        logits[i, :t_b] = regime_logits(rng, label, t_b, k, first)
+        logits[i, t_b // 2:t_b] = regime_logits(rng, label, t_b, k, second)[t_b // 2:]
+    logq, paths, scores = run_align_kernel(hip_lib, logits, labels_list, input_len, l_max=l_max)
+    assert np.isfinite(scores).all()  # (every row can be aligned, the second one only just)
     check_against_restatement(logq, labels_list, input_len, paths, scores, k)
 
 

@@ -6,7 +6,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from test_gpu_ctc_align import check_against_restatement, fuzz_case, run_align_kernel
+from test_gpu_ctc_align import FUZZ_KINDS, FUZZ_SHAPES, check_against_restatement, fuzz_case, run_align_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -156,10 +156,8 @@ def test_long_align_agrees_with_the_one_wave_kernel(hip_lib, k):
     """The fuzz shapes of test_gpu_ctc_align.test_align_kernel_bit_exact_on_fuzz_regimes (l_max <= 511, 300 .. 4000 frames,
     backpointers of the one-wave kernel in LDS and in HBM): both kernels return the same bytes."""
     rng = np.random.RandomState(11 + k)
-    kinds = ("uniform", "sharp", "collapse", "learnt", "wrong")
-    shapes = [(300, 6, 100, False), (300, 4, 255, True), (1000, 4, 250, False), (4000, 3, 511, False), (4000, 2, 120, False)]
-    for t, b, l_hi, tight in shapes:
-        logits, labels_list, input_len = fuzz_case(rng, k, t, b, l_hi, kinds, tight)
+    for t, b, l_hi, tight in FUZZ_SHAPES:
+        logits, labels_list, input_len = fuzz_case(rng, k, t, b, l_hi, FUZZ_KINDS, tight)
         _, paths, scores, paths1, scores1 = run_long_kernel(hip_lib, logits, labels_list, input_len, one_wave=True)
         assert paths.tobytes() == paths1.tobytes() and scores.tobytes() == scores1.tobytes()
     # the infeasible / empty / clamped rows of that test
