@@ -523,7 +523,7 @@ int sl_ctc_beam_search(const float* probs, const int32_t* lengths, int batch, in
  * is absent or a mark; l once (asg_twice) or l twice (asg_thrice) otherwise (AsgGraphemeEncoding.decode_grapheme; a mark
  * behind the space writes spaces, each scoring an empty word as <unk> like any other).  For each written character in turn:
  *   state = expand(state, c);   a = lw * state.delta + a     (one multiply, then one add)
- * expand / expand_end are the CTC decoder's scorer in the arithmetic and operation order of ctc_beam.hip.  lm == NULL: no
+ * expand / expand_end are the CTC decoder's scorer in the arithmetic and operation order of csrc/beam_shared.h.  lm == NULL: no
  * scorer terms.  A grapheme that writes nothing leaves state and score alone.
  * Frame 0, every j:   a = g0(j) + e_0(j);   the scorer terms of j from the initial state;   source position 0.
  * Frame t > 0, every hypothesis i (last grapheme l, score s) and every j:

@@ -23,7 +23,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 
 
 def _newest_source_mtime():
-    files = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "lds_dma.h", CSRC / "lattice.h", CSRC / "beam_lm.h", CSRC / "ctc_shared.h", PACKAGE_DIR.parent / "include" / "speechless_hip.h"]
+    files = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "lds_dma.h", CSRC / "lattice.h", CSRC / "beam_shared.h", CSRC / "ctc_shared.h", PACKAGE_DIR.parent / "include" / "speechless_hip.h"]
     return max(f.stat().st_mtime for f in files)
 
 

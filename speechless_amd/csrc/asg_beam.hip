@@ -19,103 +19,47 @@
 //      back is the same node), its scorer state from the parent's state and cache (a trie step or a history shift), a free storage
 //      and -- with a language model -- its children's scores from the trie and n-gram tables in HBM (the only dependent
 //      global loads of a frame).
+// The storages' common fields, the node table, the scorer and the backtrace are beam_shared.h's.
 // Frames are staged in LDS CH at a time; the K x K transition scores and the start scores stay in LDS for the whole utterance.
 // The kernel uses no scratch (build.py NO_SCRATCH) and no float atomics; the only multiply is lm_weight * delta, rounded
 // before its add (-ffp-contract=off).
-#include "beam_lm.h"
+#include "beam_shared.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int WMAX = 128;  // beam width limit
-constexpr int KMAX = 64;   // graphemes: one lane each
-constexpr int CH = 16;     // frames per LDS staging chunk
-constexpr int NT = 256;    // threads of the work-group
-constexpr float NEG_INF = -__builtin_huge_valf();
+constexpr int NT = 256;  // threads of the work-group
 constexpr uint32_t ORD_NEG_INF = 0x007FFFFFu;  // ord(-inf)
 
 enum { C_NS, C_NNEW, C_NODES, C_ALL, C_PREFIX, C_NEED, C_EQ, C_OVER, C_TOP, C_COUNT, C_N };
 
-struct Lds {
+struct Lds : BeamStorages {  // cache[e][j]: the scorer's score behind each child of storage e, [k-2], [k-1]: see the head
     float cand[WMAX * KMAX];       // this frame's candidates, index i * 64 + j (the end: the totals)
     float g[(KMAX + 1) * KMAX];    // g[l * 64 + j]; row k: the start scores (the root's "last grapheme" is k)
-    float cache[WMAX][KMAX];       // per storage: the scorer's score behind each child, [k-2], [k-1]: see the head
     float frames[CH][KMAX];
     uint8_t cbt[WMAX * KMAX];      // candidate index of a winning merged extension -> the position it names, 0xFF
-    int hist[4][256];
-    // per storage
-    int node[WMAX], pnode[WMAX], label[WMAX], trie[WMAX], hlen[WMAX];
-    float lm[WMAX], score[WMAX];
-    uint32_t h[HMAX][WMAX];
+    int bins[4][256];              // the radix select's histograms, one per pass
     // per beam position
     int b_e[WMAX], b_l[WMAX], b_node[WMAX], b_ext[WMAX];
     float b_s[WMAX];
     // survivors of the frame
     unsigned long long skey[WMAX], sorted[WMAX];
-    int used[WMAX], freelist[WMAX];
     int wtie[4];
     int ctr[C_N];
 };
-
-struct St {  // scorer state of a prefix
-    float lm, score;
-    int trie, hlen;
-    uint32_t h[HMAX];
-};
-
-__device__ __forceinline__ St load_state(const Lds& S, int e) {
-    St s;
-    s.lm = S.lm[e];
-    s.score = S.score[e];
-    s.trie = S.trie[e];
-    s.hlen = S.hlen[e];
-#pragma unroll
-    for (int j = 0; j < HMAX; ++j) s.h[j] = S.h[j][e];
-    return s;
-}
-
-// the scorer's expand_state for one character (ctc_beam.hip: fill_cache and the new entry's state); returns the delta
-__device__ __forceinline__ float expand(const sl_beam_lm& lm, int nlab, St& s, int c) {
-    float ns;
-    if (c == lm.space_label) {
-        const uint32_t word = (uint32_t)trie_word(lm, s.trie);
-        const float d = ngram_score(lm, s.h, s.hlen, word);
-        float v = s.lm;
-        if (word != 0u) v += lm.valid_word_count_weight;
-        v += lm.word_count_weight;
-        ns = v + d;
-        s.lm = ns;
-        s.trie = 0;
-        advance(lm, s.h, &s.hlen, word);
-    } else {
-        const bool in = s.trie >= 0 && s.trie < lm.n_trie_nodes;
-        const float mu = in ? lm.trie_min[(size_t)s.trie * nlab + c] : lm.oov_score;
-        ns = mu + s.lm;
-        s.trie = in ? lm.trie_child[(size_t)s.trie * nlab + c] : -1;
-    }
-    const float delta = ns - s.score;
-    s.score = ns;
-    return delta;
-}
-
-__device__ __forceinline__ int lanes_below(uint64_t m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
+static_assert(sizeof(Lds) == 110392, "the LDS of a work-group: occupancy");
 
 __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ logq, const float* __restrict__ trans,
                                                       const float* __restrict__ init, const int32_t* __restrict__ input_len,
                                                       int t_out, int k, int W, int has_lm, sl_beam_lm lm,
                                                       int32_t* __restrict__ out, int32_t* __restrict__ out_len,
-                                                      float* __restrict__ score, uint8_t* __restrict__ ws, int64_t node_cap,
-                                                      int64_t hash_slots, int64_t ws_stride) {
+                                                      float* __restrict__ score, uint8_t* __restrict__ ws, BeamSizes sizes) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     Lds& S = *(Lds*)smem;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
-    int32_t* arena = (int32_t*)(ws + (size_t)b * ws_stride);
-    unsigned long long* hmap = (unsigned long long*)(ws + (size_t)b * ws_stride + (((size_t)node_cap * 4 + 7) & ~(size_t)7));
-    const uint64_t hmask = (uint64_t)hash_slots - 1;
+    const NodeTable nodes(ws, b, sizes);
     const int T = max(0, min(input_len[b], t_out));
     const int nchar = k - 2;  // characters; k - 2 = asg_twice, k - 1 = asg_thrice
     const float lw = lm.lm_weight;
@@ -126,20 +70,12 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
     if (tid < k) S.g[k * KMAX + tid] = init[tid];
     for (int q = tid; q < WMAX * KMAX / 4; q += NT) ((uint32_t*)S.cbt)[q] = 0xFFFFFFFFu;
     if (tid == 0) {
-        arena[0] = -1;
-        S.node[0] = 0;
-        S.pnode[0] = -1;
-        S.label[0] = k;
-        S.lm[0] = S.score[0] = 0.f;
-        S.trie[0] = 0;
-        S.hlen[0] = 1;
-        for (int j = 0; j < HMAX; ++j) S.h[j][0] = j == HMAX - 1 ? (uint32_t)lm.bos : 0u;
+        init_root(S, nodes.arena, k, lm.bos);
         S.b_e[0] = 0;
         S.b_l[0] = k;
         S.b_node[0] = 0;
         S.b_ext[0] = -1;
         S.b_s[0] = -0.f;
-        S.freelist[0] = 0;
         S.ctr[C_NODES] = 1;
         S.ctr[C_OVER] = 0;
     }
@@ -173,7 +109,7 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
             const float* src = logq + ((size_t)b * t_out + t) * k;
             for (int q = tid; q < nf * k; q += NT) S.frames[q / k][q % k] = src[q];
         }
-        for (int q = tid; q < 4 * 256; q += NT) (&S.hist[0][0])[q] = 0;
+        for (int q = tid; q < 4 * 256; q += NT) (&S.bins[0][0])[q] = 0;
         if (tid < WMAX) S.used[tid] = 0;
         if (tid == 0) S.ctr[C_NS] = S.ctr[C_NNEW] = S.ctr[C_ALL] = 0;
         __syncthreads();
@@ -241,7 +177,7 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
                     if (p == 0 || (o >> (shift + 8)) == prefix) {
                         const int bin = (int)((o >> shift) & 255u);
                         if (bin != cur && cnt) {
-                            atomicAdd(&S.hist[p][cur], cnt);
+                            atomicAdd(&S.bins[p][cur], cnt);
                             cnt = 0;
                         }
                         cur = bin;
@@ -249,13 +185,13 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
                     }
                 }
             }
-            if (cnt) atomicAdd(&S.hist[p][cur], cnt);
+            if (cnt) atomicAdd(&S.bins[p][cur], cnt);
             __syncthreads();
             if (wave == 0) {
                 int c[4], tot = 0;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    c[q] = S.hist[p][255 - 4 * lane - q];
+                    c[q] = S.bins[p][255 - 4 * lane - q];
                     tot += c[q];
                 }
                 int incl = tot;
@@ -358,43 +294,21 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
                 st = load_state(S, pe);
                 if (has_lm && (j < nchar || l < nchar)) {
                     // the state behind the characters grapheme j writes behind l (j, or l once / twice): its score is the
-                    // parent's cache[j]; what is left of expand() is the trie step, or at a space the history shift
+                    // parent's cache[j]
                     const int c = j < nchar ? j : l;
                     const int reps = j == k - 1 ? 2 : 1;
-                    for (int r = 0; r < reps; ++r) {
-                        if (c == lm.space_label) {
-                            advance(lm, st.h, &st.hlen, (uint32_t)trie_word(lm, st.trie));
-                            st.trie = 0;
-                        } else {
-                            const bool in = st.trie >= 0 && st.trie < lm.n_trie_nodes;
-                            st.trie = in ? lm.trie_child[(size_t)st.trie * nchar + c] : -1;
-                        }
-                    }
-                    st.score = S.cache[pe][j];
-                    if (c == lm.space_label) st.lm = st.score;
+                    const float behind = S.cache[pe][j];
+                    for (int r = 0; r < reps; ++r) step_into_child(lm, nchar, st, c, behind);
                 }
-                // canonical node id of (parent node, label): the hash map, or a fresh node
-                const uint32_t key = (uint32_t)(my_pn * KMAX + j + 1);
-                uint64_t slot = fmix32(key) & hmask;
-                int found = -1;
-                for (int64_t probe = 0; probe < hash_slots; ++probe) {
-                    const unsigned long long v = __hip_atomic_load(&hmap[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (v == 0ull) break;
-                    if ((uint32_t)(v >> 32) == key) {
-                        found = (int)(uint32_t)v;
-                        break;
-                    }
-                    slot = (slot + 1) & hmask;
-                }
+                // canonical node id of (parent node, label): the hash map, or a fresh node (an LDS counter: the threads
+                // that need one are any subset of the work-group)
+                const uint32_t key = node_key(my_pn, j);
+                uint64_t slot;
+                int found = nodes.find(key, slot);
                 if (found < 0) {
                     const int id = atomicAdd(&S.ctr[C_NODES], 1);
-                    if (id < node_cap) {
-                        const unsigned long long val = ((unsigned long long)key << 32) | (uint32_t)id;
-                        for (int64_t probe = 0; probe < hash_slots; ++probe) {
-                            if (atomicCAS(&hmap[slot], 0ull, val) == 0ull) break;
-                            slot = (slot + 1) & hmask;
-                        }
-                        arena[id] = (int32_t)(my_pn * KMAX + j);
+                    if (id < nodes.node_cap) {
+                        nodes.insert(slot, key, id, my_pn, j);
                         found = id;
                     } else {
                         S.ctr[C_OVER] = 1;
@@ -406,13 +320,7 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
         }
         __syncthreads();
         const int n_new = S.ctr[C_NNEW];
-        if (wave == 0) {  // the storages no survivor holds, in ascending order
-            const bool f0_ = lane < W && !S.used[lane];
-            const bool f1_ = lane + 64 < W && !S.used[lane + 64];
-            const uint64_t m0 = __ballot(f0_), m1 = __ballot(f1_);
-            if (f0_) S.freelist[lanes_below(m0)] = lane;
-            if (f1_) S.freelist[__popcll(m0) + lanes_below(m1)] = lane + 64;
-        }
+        if (wave == 0) build_freelist(S.used, W, S.freelist, lane);  // the storages no survivor holds
         if (tid < n && S.b_ext[tid] >= 0) S.cbt[S.b_ext[tid]] = 0xFF;
         __syncthreads();
         // phase B: the positions of the new beam, the new prefixes into free storages
@@ -422,12 +330,7 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
                 S.node[my_e] = my_node;
                 S.pnode[my_e] = my_pn;
                 S.label[my_e] = my_l;
-                S.lm[my_e] = st.lm;
-                S.score[my_e] = st.score;
-                S.trie[my_e] = st.trie;
-                S.hlen[my_e] = st.hlen;
-#pragma unroll
-                for (int j = 0; j < HMAX; ++j) S.h[j][my_e] = st.h[j];
+                store_state(S, my_e, st);
             }
             S.b_e[tid] = my_e;
             S.b_l[tid] = my_l;
@@ -443,19 +346,7 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
     if (T == 0) n = 0;
     if (tid < n) {
         float total = S.b_s[tid];
-        if (has_lm) {
-            St e = load_state(S, S.b_e[tid]);
-            float d = 0.f;
-            if (e.trie != 0) {  // a pending word (node 0 = the empty word)
-                const uint32_t word = (uint32_t)trie_word(lm, e.trie);
-                d += ngram_score(lm, e.h, e.hlen, word);
-                advance(lm, e.h, &e.hlen, word);
-            }
-            d += ngram_score(lm, e.h, e.hlen, (uint32_t)lm.eos);
-            const float lms = e.lm + d;
-            const float delta = lms - e.score;
-            total = lw * delta + total;
-        }
+        if (has_lm) total = lw * expand_end_delta(lm, load_state(S, S.b_e[tid])) + total;
         S.cand[tid] = total;
     }
     __syncthreads();
@@ -469,9 +360,7 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
                 best = v;
             }
         }
-        if (top >= 0) {
-            for (int c = S.b_node[top], step = 0; c > 0 && step <= T; ++step, c = arena[c] >> 6) ++count;
-        }
+        if (top >= 0) count = count_labels(nodes.arena, S.b_node[top], T, false);
         S.ctr[C_TOP] = top;
         S.ctr[C_COUNT] = count;
         if (score) score[b] = best;
@@ -480,15 +369,7 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
     const int count = min(S.ctr[C_COUNT], t_out);
     for (int i = count + tid; i < t_out; i += NT) row[i] = -1;
     if (tid == 0) {
-        if (S.ctr[C_TOP] >= 0) {
-            int pos = S.ctr[C_COUNT] - 1;
-            for (int c = S.b_node[S.ctr[C_TOP]], step = 0; c > 0 && step <= T; ++step) {
-                const int pp = arena[c];
-                if (pos >= 0 && pos < t_out) row[pos] = pp & (KMAX - 1);
-                --pos;
-                c = pp >> 6;
-            }
-        }
+        if (S.ctr[C_TOP] >= 0) write_labels(nodes.arena, S.b_node[S.ctr[C_TOP]], T, false, row, S.ctr[C_COUNT], t_out);
         out_len[b] = S.ctr[C_OVER] ? -1 : count;
     }
 }
@@ -496,62 +377,28 @@ __global__ __launch_bounds__(NT) void asg_beam_kernel(const float* __restrict__ 
 }  // namespace
 
 extern "C" size_t sl_asg_beam_search_workspace_bytes(int batch, int t_out, int k, int beam_width) {
-    if (batch <= 0 || t_out <= 0 || k < 2 || k > KMAX || beam_width < 1 || beam_width > WMAX) return 0;
-    if ((int64_t)t_out * beam_width + 1 >= ((int64_t)1 << 25)) return 0;
-    return (size_t)batch * beam_sizes_of(t_out, beam_width).stride;
+    return beam_workspace_bytes(batch, t_out, k, beam_width);
 }
 
 extern "C" int sl_asg_beam_search(const float* logq, const float* trans, const float* init, const int32_t* input_len, int batch,
                                   int t_out, int k, int beam_width, const sl_beam_lm* lm, int32_t* out, int32_t* out_len,
                                   float* score, void* workspace, size_t workspace_bytes, void* stream) {
-    SL_CHECK_ARG(batch > 0 && t_out > 0, "sl_asg_beam_search: need batch, t_out > 0");
+    static const BeamWords words = {"sl_asg_beam_search", "t_out", "grapheme", "characters"};
     SL_CHECK_ARG(logq && trans && init && input_len && out && out_len && workspace, "sl_asg_beam_search: null pointer");
-    if (k < 2 || k > KMAX) {
-        sl_set_error("sl_asg_beam_search: k = %d outside 2 <= k <= %d (one lane per grapheme)", k, KMAX);
-        return SL_ERR_UNSUPPORTED;
-    }
-    if (beam_width < 1 || beam_width > WMAX) {
-        sl_set_error("sl_asg_beam_search: beam width %d outside [1, %d]", beam_width, WMAX);
-        return SL_ERR_UNSUPPORTED;
-    }
-    if ((int64_t)t_out * beam_width + 1 >= ((int64_t)1 << 25)) {
-        sl_set_error("sl_asg_beam_search: t_out * beam_width = %lld too large (node ids are 25-bit)",
-                     (long long)t_out * beam_width);
-        return SL_ERR_UNSUPPORTED;
-    }
-    sl_beam_lm none = {};
-    none.order = 1;
-    none.space_label = -1;
-    if (lm) {
-        SL_CHECK_ARG(k > 2, "sl_asg_beam_search: a language model needs at least one character beside the two repeat marks");
-        SL_CHECK_ARG(lm->trie_child && lm->trie_min && lm->trie_word && lm->ngrams && lm->n_trie_nodes > 0,
-                     "sl_asg_beam_search: incomplete language model tables");
-        SL_CHECK_ARG(lm->ngram_slots >= 1 && (lm->ngram_slots & (lm->ngram_slots - 1)) == 0,
-                     "sl_asg_beam_search: ngram_slots must be a power of two");
-        SL_CHECK_ARG(lm->space_label >= -1 && lm->space_label < k - 2, "sl_asg_beam_search: space label outside the characters");
-        if (lm->order < 1 || lm->order > HMAX + 1) {
-            sl_set_error("sl_asg_beam_search: language model order %d outside [1, %d]", lm->order, HMAX + 1);
-            return SL_ERR_UNSUPPORTED;
-        }
-    }
-    const size_t need = sl_asg_beam_search_workspace_bytes(batch, t_out, k, beam_width);
-    if (workspace_bytes < need) {
-        sl_set_error("sl_asg_beam_search: workspace too small (%zu < %zu)", workspace_bytes, need);
-        return SL_ERR_WORKSPACE_TOO_SMALL;
-    }
+    const int rc = beam_check_args(words, batch, t_out, k, beam_width, lm, k - 2);
+    if (rc != SL_OK) return rc;
+    SL_CHECK_ARG(!lm || k > 2, "sl_asg_beam_search: a language model needs at least one character beside the two repeat marks");
     const hipStream_t s = (hipStream_t)stream;
-    const BeamSizes z = beam_sizes_of(t_out, beam_width);
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute((const void*)asg_beam_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(Lds));
         attr_set = true;
     }
-    if (hipMemsetAsync(workspace, 0, need, s) != hipSuccess) {  // the hash maps start empty
-        sl_set_error("sl_asg_beam_search: workspace clear failed");
-        return SL_ERR_LAUNCH_FAILED;
-    }
+    const int ws_rc = beam_clear_workspace(words.fn, workspace, workspace_bytes,
+                                           beam_workspace_bytes(batch, t_out, k, beam_width), s);
+    if (ws_rc != SL_OK) return ws_rc;
     hipLaunchKernelGGL(asg_beam_kernel, dim3(batch), dim3(NT), sizeof(Lds), s, logq, trans, init, input_len, t_out, k,
-                       beam_width, lm ? 1 : 0, lm ? *lm : none, out, out_len, score, (uint8_t*)workspace, z.node_cap,
-                       z.hash_slots, z.stride);
-    return sl_check_launch("sl_asg_beam_search");
+                       beam_width, lm ? 1 : 0, lm ? *lm : beam_lm_none(), out, out_len, score, (uint8_t*)workspace,
+                       beam_sizes_of(t_out, beam_width));
+    return sl_check_launch(words.fn);
 }

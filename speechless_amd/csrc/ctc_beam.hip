@@ -20,16 +20,15 @@
 //      children's scores from the flat trie and n-gram tables in HBM (the only dependent global loads of a frame).
 // Frames are staged in LDS CH at a time and normalised there (log(p + eps) - logsumexp, the host's operation order).
 // The kernel uses no scratch (build.py NO_SCRATCH): every per-lane array is indexed with compile-time indices.
-#include "beam_lm.h"  // the scorer pieces shared with asg_beam.hip: n-gram lookup, advance, trie_word, ord / unord, HMAX
+// From beam_shared.h it takes the limits, the n-gram look-up, advance, trie_word, ord / unord, the workspace layout and the
+// host-side checks.  Its storages, its hash-map look-up and insert, its backtrace and its scorer arithmetic (fill_cache, phase
+// A of step 4, the end of the utterance) are still written out here, in the operation order that beam_shared.h states at
+// expand(): moving this kernel onto the header's BeamStorages / NodeTable / St cost it 1 % of its time.
+#include "beam_shared.h"
 
 #pragma clang fp contract(off)  // lm_weight * delta + previous is two roundings on the host
 
 namespace {
-
-constexpr int WMAX = 128;  // beam width limit
-constexpr int KMAX = 64;   // classes: one lane each
-constexpr int CH = 16;     // frames per LDS staging chunk
-constexpr float NEG_INF = -__builtin_huge_valf();
 
 __device__ __forceinline__ float log_d(float x) { return (float)log((double)x); }
 __device__ __forceinline__ float exp_d(float x) { return (float)exp((double)x); }
@@ -50,10 +49,6 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
         v = o < v ? o : v;
     }
     return v;
-}
-
-__device__ __forceinline__ int lanes_below(uint64_t m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
 
 struct Lds {
@@ -501,62 +496,29 @@ __global__ __launch_bounds__(64) void ctc_beam_kernel(const float* __restrict__ 
 }  // namespace
 
 extern "C" size_t sl_ctc_beam_search_workspace_bytes(int batch, int t_max, int k, int beam_width) {
-    if (batch <= 0 || t_max <= 0 || k < 2 || k > KMAX || beam_width < 1 || beam_width > WMAX) return 0;
-    if ((int64_t)t_max * beam_width + 1 >= ((int64_t)1 << 25)) return 0;
-    return (size_t)batch * beam_sizes_of(t_max, beam_width).stride;
+    return beam_workspace_bytes(batch, t_max, k, beam_width);
 }
 
 extern "C" int sl_ctc_beam_search(const float* probs, const int32_t* lengths, int batch, int t_max, int k, int blank,
                                   int beam_width, int merge_repeated, float eps, const sl_beam_lm* lm, int32_t* out,
                                   int32_t* out_len, float* log_prob, void* workspace, size_t workspace_bytes,
                                   void* stream) {
-    SL_CHECK_ARG(batch > 0 && t_max > 0, "sl_ctc_beam_search: need batch, t_max > 0");
+    static const BeamWords words = {"sl_ctc_beam_search", "t_max", "class", "alphabet"};
     SL_CHECK_ARG(probs && lengths && out && out_len && workspace, "sl_ctc_beam_search: null pointer");
     SL_CHECK_ARG(blank >= 0 && blank < k, "sl_ctc_beam_search: blank %d outside [0, %d)", blank, k);
-    if (k < 2 || k > KMAX) {
-        sl_set_error("sl_ctc_beam_search: k = %d outside 2 <= k <= %d (one lane per class)", k, KMAX);
+    const int rc = beam_check_args(words, batch, t_max, k, beam_width, lm, k - 1);
+    if (rc != SL_OK) return rc;
+    if (lm && blank != k - 1) {
+        sl_set_error("sl_ctc_beam_search: with a language model the blank must be the last class (k - 1)");
         return SL_ERR_UNSUPPORTED;
-    }
-    if (beam_width < 1 || beam_width > WMAX) {
-        sl_set_error("sl_ctc_beam_search: beam width %d outside [1, %d]", beam_width, WMAX);
-        return SL_ERR_UNSUPPORTED;
-    }
-    if ((int64_t)t_max * beam_width + 1 >= ((int64_t)1 << 25)) {
-        sl_set_error("sl_ctc_beam_search: t_max * beam_width = %lld too large (node ids are 25-bit)",
-                     (long long)t_max * beam_width);
-        return SL_ERR_UNSUPPORTED;
-    }
-    sl_beam_lm none = {};
-    none.order = 1;
-    none.space_label = -1;
-    if (lm) {
-        SL_CHECK_ARG(lm->trie_child && lm->trie_min && lm->trie_word && lm->ngrams && lm->n_trie_nodes > 0,
-                     "sl_ctc_beam_search: incomplete language model tables");
-        SL_CHECK_ARG(lm->ngram_slots >= 1 && (lm->ngram_slots & (lm->ngram_slots - 1)) == 0,
-                     "sl_ctc_beam_search: ngram_slots must be a power of two");
-        SL_CHECK_ARG(lm->space_label >= -1 && lm->space_label < k - 1, "sl_ctc_beam_search: space label outside the alphabet");
-        if (blank != k - 1) {
-            sl_set_error("sl_ctc_beam_search: with a language model the blank must be the last class (k - 1)");
-            return SL_ERR_UNSUPPORTED;
-        }
-        if (lm->order < 1 || lm->order > HMAX + 1) {
-            sl_set_error("sl_ctc_beam_search: language model order %d outside [1, %d]", lm->order, HMAX + 1);
-            return SL_ERR_UNSUPPORTED;
-        }
-    }
-    const size_t need = sl_ctc_beam_search_workspace_bytes(batch, t_max, k, beam_width);
-    if (workspace_bytes < need) {
-        sl_set_error("sl_ctc_beam_search: workspace too small (%zu < %zu)", workspace_bytes, need);
-        return SL_ERR_WORKSPACE_TOO_SMALL;
     }
     const hipStream_t s = (hipStream_t)stream;
+    const int ws_rc = beam_clear_workspace(words.fn, workspace, workspace_bytes,
+                                           beam_workspace_bytes(batch, t_max, k, beam_width), s);
+    if (ws_rc != SL_OK) return ws_rc;
     const BeamSizes z = beam_sizes_of(t_max, beam_width);
-    if (hipMemsetAsync(workspace, 0, need, s) != hipSuccess) {  // the hash maps start empty
-        sl_set_error("sl_ctc_beam_search: workspace clear failed");
-        return SL_ERR_LAUNCH_FAILED;
-    }
     hipLaunchKernelGGL(ctc_beam_kernel, dim3(batch), dim3(64), 0, s, probs, lengths, t_max, k, blank, beam_width,
-                       merge_repeated ? 1 : 0, eps, lm ? 1 : 0, lm ? *lm : none, out, out_len, log_prob, (uint8_t*)workspace,
-                       z.node_cap, z.hash_slots, z.stride);
-    return sl_check_launch("sl_ctc_beam_search");
+                       merge_repeated ? 1 : 0, eps, lm ? 1 : 0, lm ? *lm : beam_lm_none(), out, out_len, log_prob,
+                       (uint8_t*)workspace, z.node_cap, z.hash_slots, z.stride);
+    return sl_check_launch(words.fn);
 }

@@ -182,23 +182,16 @@ def _to_device(array, dtype, device):
                                                                             torch.int32: np.int32}[dtype])).to(device)
 
 
-class GpuCtcBeamSearchDecoder:
-    """CtcBeamSearchDecoder on the GPU (ctc_beam.hip): the same search and the same results, one wave per utterance.
-    The language model's tables are exported from the host scorer and uploaded once.  Limits: at most 64 classes,
-    beam width 1..128, language-model order <= 6 (BeamSearchLimitError, a ValueError, otherwise)."""
+class _GpuBeamSearchDecoder:
+    """What the two GPU decoders share: the limits, the uploaded scorer tables, the workspace, and the call itself."""
 
-    def __init__(self, allowed_characters, language_model=None, beam_width=DEFAULT_BEAM_WIDTH, merge_repeated=False,
-                 kenlm_weight=KENLM_WEIGHT, word_count_weight=WORD_COUNT_WEIGHT,
-                 valid_word_count_weight=VALID_WORD_COUNT_WEIGHT, epsilon=1e-8, threads=8, device="cuda:0"):
+    def __init__(self, allowed_characters, n_classes, language_model, beam_width, kenlm_weight, word_count_weight,
+                 valid_word_count_weight, device):
         import torch
         from . import _lib as hip
         self.allowed_characters = list(allowed_characters)
-        k = len(self.allowed_characters) + 1
-        _check_gpu_limits(k, beam_width, language_model)
+        _check_gpu_limits(n_classes, beam_width, language_model)
         self.beam_width = beam_width
-        self.merge_repeated = merge_repeated
-        self.epsilon = epsilon
-        self.threads = threads  # unused: kept so that the constructor matches CtcBeamSearchDecoder's
         self.language_model = language_model
         self.device = torch.device(device)
         self._hip = hip
@@ -213,52 +206,69 @@ class GpuCtcBeamSearchDecoder:
     def from_kenlm_directory(cls, kenlm_directory, allowed_characters, **kw):
         return cls(allowed_characters, NGramLanguageModel(find_arpa(kenlm_directory)), **kw)
 
+    def _lengths(self, prediction_lengths, b, device):
+        import torch
+        lengths = _to_device(prediction_lengths, torch.int32, device).reshape(-1)
+        if lengths.numel() != b:
+            raise ValueError("{} lengths for a batch of {}".format(lengths.numel(), b))
+        return lengths
+
+    def _run(self, entry, scores, b, t, k, *args_before_lm):
+        """entry(*args_before_lm, lm, out, out_len, score, workspace, workspace bytes, stream) on the device of `scores`, the
+        (B, T', K) tensor; returns (list of index lists, scores (B,) numpy)."""
+        import torch
+        lib = self._hip.lib()
+        need = lib.raw(entry + "_workspace_bytes")(b, t, k, self.beam_width)
+        if need == 0:
+            raise BeamSearchLimitError("the GPU beam search cannot take a ({}, {}, {}) batch at beam width {}".format(
+                b, t, k, self.beam_width))
+        device = scores.device
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != device:
+            self._workspace = torch.empty((need,), dtype=torch.uint8, device=device)
+        out = torch.empty((b, t), dtype=torch.int32, device=device)
+        out_len = torch.empty((b,), dtype=torch.int32, device=device)
+        score = torch.empty((b,), dtype=torch.float32, device=device)
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream().cuda_stream
+            lib.call(entry, *args_before_lm, ctypes.byref(self._lm) if self._lm is not None else None, out.data_ptr(),
+                     out_len.data_ptr(), score.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), stream)
+        out, out_len, score = out.cpu().numpy(), out_len.cpu().numpy(), score.cpu().numpy()
+        if (out_len < 0).any():
+            raise RuntimeError(entry + ": node arena overflow")
+        return [list(map(int, out[i, :out_len[i]])) for i in range(b)], score
+
+
+class GpuCtcBeamSearchDecoder(_GpuBeamSearchDecoder):
+    """CtcBeamSearchDecoder on the GPU (ctc_beam.hip): the same search and the same results, one wave per utterance.
+    The language model's tables are exported from the host scorer and uploaded once.  Limits: at most 64 classes,
+    beam width 1..128, language-model order <= 6 (BeamSearchLimitError, a ValueError, otherwise)."""
+
+    def __init__(self, allowed_characters, language_model=None, beam_width=DEFAULT_BEAM_WIDTH, merge_repeated=False,
+                 kenlm_weight=KENLM_WEIGHT, word_count_weight=WORD_COUNT_WEIGHT,
+                 valid_word_count_weight=VALID_WORD_COUNT_WEIGHT, epsilon=1e-8, threads=8, device="cuda:0"):
+        characters = list(allowed_characters)
+        super().__init__(characters, len(characters) + 1, language_model, beam_width, kenlm_weight, word_count_weight,
+                         valid_word_count_weight, device)
+        self.merge_repeated = merge_repeated
+        self.epsilon = epsilon
+        self.threads = threads  # unused: kept so that the constructor matches CtcBeamSearchDecoder's
+
     def decode(self, probabilities, prediction_lengths):
         """probabilities: (B, T', K) numpy array or float32 tensor on the GPU (used in place); prediction_lengths: (B,)
         numbers, numpy or tensor.  Returns (list of index lists, log-probabilities (B,) numpy), as CtcBeamSearchDecoder."""
         import torch
-        if isinstance(probabilities, torch.Tensor):
-            probs = probabilities
-            if probs.device.type != "cuda":
-                probs = probs.to(self.device)
-            probs = probs.to(torch.float32).contiguous()
-        else:
-            probs = torch.from_numpy(np.ascontiguousarray(probabilities, dtype=np.float32)).to(self.device)
+        probs = _to_device(probabilities, torch.float32, self.device)
         if probs.dim() != 3:
             raise ValueError("probabilities must be (B, T', K)")
         b, t, k = probs.shape
         if k != len(self.allowed_characters) + 1:
             raise ValueError("{} classes for an alphabet of {} characters + blank".format(k, len(self.allowed_characters)))
-        if isinstance(prediction_lengths, torch.Tensor):
-            lengths = prediction_lengths.reshape(-1).to(device=probs.device, dtype=torch.int32).contiguous()
-        else:
-            lengths = torch.from_numpy(np.ascontiguousarray(np.asarray(prediction_lengths).reshape(-1),
-                                                            dtype=np.int32)).to(probs.device)
-        if lengths.numel() != b:
-            raise ValueError("{} lengths for a batch of {}".format(lengths.numel(), b))
-        lib = self._hip.lib()
-        need = lib.raw("sl_ctc_beam_search_workspace_bytes")(b, t, k, self.beam_width)
-        if need == 0:
-            raise BeamSearchLimitError("the GPU beam search cannot take a ({}, {}, {}) batch at beam width {}".format(
-                b, t, k, self.beam_width))
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != probs.device:
-            self._workspace = torch.empty((need,), dtype=torch.uint8, device=probs.device)
-        out = torch.empty((b, t), dtype=torch.int32, device=probs.device)
-        out_len = torch.empty((b,), dtype=torch.int32, device=probs.device)
-        log_prob = torch.empty((b,), dtype=torch.float32, device=probs.device)
-        with torch.cuda.device(probs.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            lib.call("sl_ctc_beam_search", probs.data_ptr(), lengths.data_ptr(), b, t, k, k - 1, self.beam_width,
-                     1 if self.merge_repeated else 0, self.epsilon,
-                     ctypes.byref(self._lm) if self._lm is not None else None, out.data_ptr(), out_len.data_ptr(),
-                     log_prob.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), stream)
-        out, out_len, log_prob = out.cpu().numpy(), out_len.cpu().numpy(), log_prob.cpu().numpy()
-        if (out_len < 0).any():
-            raise RuntimeError("sl_ctc_beam_search: node arena overflow")
-        return [list(map(int, out[i, :out_len[i]])) for i in range(b)], log_prob
+        lengths = self._lengths(prediction_lengths, b, probs.device)
+        return self._run("sl_ctc_beam_search", probs, b, t, k, probs.data_ptr(), lengths.data_ptr(), b, t, k, k - 1,
+                         self.beam_width, 1 if self.merge_repeated else 0, self.epsilon)
 
 
-class GpuAsgBeamSearchDecoder:
+class GpuAsgBeamSearchDecoder(_GpuBeamSearchDecoder):
     """The ASG beam search on the GPU (asg_beam.hip; definition: include/speechless_hip.h, sl_asg_beam_search): a max search
     over grapheme prefixes under emissions + transition scores, scored by the n-gram model when there is one.  The graphemes
     are the allowed characters and the two repeat marks (AsgGraphemeEncoding); the scorer is built over the characters, and
@@ -267,27 +277,13 @@ class GpuAsgBeamSearchDecoder:
 
     def __init__(self, allowed_characters, language_model=None, beam_width=DEFAULT_BEAM_WIDTH, kenlm_weight=KENLM_WEIGHT,
                  word_count_weight=WORD_COUNT_WEIGHT, valid_word_count_weight=VALID_WORD_COUNT_WEIGHT, device="cuda:0"):
-        self.allowed_characters = list(allowed_characters)
-        self.grapheme_set_size = len(self.allowed_characters) + 2
-        _check_gpu_limits(self.grapheme_set_size, beam_width, language_model)
-        if language_model is not None and not self.allowed_characters:
+        characters = list(allowed_characters)
+        self.grapheme_set_size = len(characters) + 2
+        _check_gpu_limits(self.grapheme_set_size, beam_width, language_model)  # (first, as ever: the base's comes too late)
+        if language_model is not None and not characters:
             raise BeamSearchLimitError("a language model needs at least one character beside the two repeat marks")
-        import torch
-        from . import _lib as hip
-        self.beam_width = beam_width
-        self.language_model = language_model
-        self.device = torch.device(device)
-        self._hip = hip
-        self._tables = None
-        self._lm = None
-        self._workspace = None
-        if language_model is not None:
-            self._tables, self._lm = _upload_scorer(hip, self.allowed_characters, language_model, kenlm_weight,
-                                                    word_count_weight, valid_word_count_weight, self.device)
-
-    @classmethod
-    def from_kenlm_directory(cls, kenlm_directory, allowed_characters, **kw):
-        return cls(allowed_characters, NGramLanguageModel(find_arpa(kenlm_directory)), **kw)
+        super().__init__(characters, self.grapheme_set_size, language_model, beam_width, kenlm_weight, word_count_weight,
+                         valid_word_count_weight, device)
 
     def decode(self, logq, trans, init, prediction_lengths):
         """logq: (B, T', K) emissions, trans: (K, K) [from][to], init: (K,) -- numpy arrays or float32 tensors on the GPU
@@ -305,25 +301,6 @@ class GpuAsgBeamSearchDecoder:
         if tuple(trans.shape) != (k, k) or tuple(init.shape) != (k,):
             raise ValueError("ASG scores must have shapes ({0}, {0}) and ({0},), not {1} and {2}".format(
                 k, tuple(trans.shape), tuple(init.shape)))
-        lengths = _to_device(prediction_lengths, torch.int32, logq.device).reshape(-1)
-        if lengths.numel() != b:
-            raise ValueError("{} lengths for a batch of {}".format(lengths.numel(), b))
-        lib = self._hip.lib()
-        need = lib.raw("sl_asg_beam_search_workspace_bytes")(b, t, k, self.beam_width)
-        if need == 0:
-            raise BeamSearchLimitError("the GPU beam search cannot take a ({}, {}, {}) batch at beam width {}".format(
-                b, t, k, self.beam_width))
-        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != logq.device:
-            self._workspace = torch.empty((need,), dtype=torch.uint8, device=logq.device)
-        out = torch.empty((b, t), dtype=torch.int32, device=logq.device)
-        out_len = torch.empty((b,), dtype=torch.int32, device=logq.device)
-        score = torch.empty((b,), dtype=torch.float32, device=logq.device)
-        with torch.cuda.device(logq.device):
-            stream = torch.cuda.current_stream().cuda_stream
-            lib.call("sl_asg_beam_search", logq.data_ptr(), trans.data_ptr(), init.data_ptr(), lengths.data_ptr(), b, t, k,
-                     self.beam_width, ctypes.byref(self._lm) if self._lm is not None else None, out.data_ptr(),
-                     out_len.data_ptr(), score.data_ptr(), self._workspace.data_ptr(), self._workspace.numel(), stream)
-        out, out_len, score = out.cpu().numpy(), out_len.cpu().numpy(), score.cpu().numpy()
-        if (out_len < 0).any():
-            raise RuntimeError("sl_asg_beam_search: node arena overflow")
-        return [list(map(int, out[i, :out_len[i]])) for i in range(b)], score
+        lengths = self._lengths(prediction_lengths, b, logq.device)
+        return self._run("sl_asg_beam_search", logq, b, t, k, logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
+                         lengths.data_ptr(), b, t, k, self.beam_width)

@@ -9,8 +9,8 @@ NEG_INF = F("-inf")
 
 
 class TableScorer:
-    """expand / expand_end of the CTC decoder's scorer (ctc_beam.hip: fill_cache, the new entry's state, the end of the
-    utterance) in float32, one rounded operation per line.  state = (lm, score, trie node, history tuple, history length)."""
+    """expand / expand_end of the CTC decoder's scorer (csrc/beam_shared.h: expand, step_into_child,
+    expand_end_delta) in float32, one rounded operation per line.  state = (lm, score, trie node, history tuple, history length)."""
 
     def __init__(self, tables):
         self.child, self.mu, self.word = tables["trie_child"], tables["trie_min"], tables["trie_word"]

@@ -130,8 +130,9 @@ def fill_cache(e, lm, n_labels):
             e.cache[m] = f32(lm.min_unigram(e.trie, m) + e.lm)
 
 
-def batched_beam_search(probs, beam_width, merge, lm=None, eps=1e-8):
-    """One utterance, (T, k) probabilities; blank = k - 1.  Returns (labels, log_prob)."""
+def batched_beam_search(probs, beam_width, merge, lm=None, eps=1e-8, stats=None):
+    """One utterance, (T, k) probabilities; blank = k - 1.  Returns (labels, log_prob).  stats: a dict whose "returns" counts
+    the new beam entries that the map already knew (prefixes that had left the beam)."""
     t_len, k = probs.shape
     blank, n_labels = k - 1, k - 1
     arena = [-1]
@@ -231,6 +232,8 @@ def batched_beam_search(probs, beam_width, merge, lm=None, eps=1e-8):
             par = br[i]
             c = Entry()
             key = (par.node, ind)
+            if stats is not None:
+                stats["returns"] += key in ids
             if key not in ids:
                 ids[key] = len(arena)
                 arena.append(key)

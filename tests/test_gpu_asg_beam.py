@@ -64,6 +64,20 @@ def test_restatement_parity_plain_and_toy_language_model(toy_lm, beam_width, wei
         assert merges >= 1 and returns >= 1, (merges, returns)
 
 
+@pytest.mark.parametrize("t_max, beam_width, seed", [(5, 2, 5), (8, 3, 6)])
+def test_smallest_node_table_with_returning_prefixes(toy_lm, t_max, beam_width, seed):
+    """k = 5 and 11 / 25 nodes at most: hash maps of 32 / 64 slots (the floor is 16), whose probe chains wrap, with prefixes
+    that leave the beam and return (the seeds were chosen on the restatement for that, with and without the model); a row of
+    one frame and a row of none beside them: the root alone, and the backtrace of a one-node arena."""
+    characters = list("at ")
+    logq, trans, init = random_case(seed, 5, t_max, len(characters) + 2)
+    for lm in (None, toy_lm):
+        want, _, merges, returns = assert_bits(characters, lm, None, beam_width, logq, trans, init,
+                                               [t_max, 1, 0, t_max - 1, t_max])
+        assert merges >= 1 and returns >= 1, (merges, returns)
+        assert len(want[1]) == 1 and want[2] == []
+
+
 @pytest.mark.parametrize("k", [30, 64])
 def test_class_counts_with_an_order_4_model(order4_lm, k):
     logq, trans, init = random_case(3, 2, 40, k)

@@ -72,6 +72,36 @@ def test_plain_and_toy_language_model(toy_lm, beam_width, weights):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("t_max, beam_width, seeds", [(5, 2, (12, 0, 49)), (8, 3, (0, 0, 10))])
+def test_smallest_node_table(toy_lm, tmp_path, t_max, beam_width, seeds):
+    """11 / 25 nodes at most: hash maps of 32 / 64 slots (the floor is 16), whose probe chains wrap, with prefixes that leave
+    the beam and return (the seeds were chosen for that on the CPU restatement of the kernel, test_beam_search_batched.py, which
+    counts them; asserted below); a row of one frame and a row of none beside them: the root alone, and the backtrace of a
+    one-node arena.  k = 5 without a model and with a 12-word bigram model over the same four characters; the toy model at its
+    own alphabet (k = 9, the smallest that spells its words: for a word it cannot spell the HOST scorer leaves trie nodes at a
+    minimum of FLT_MAX behind, and is no reference then)."""
+    from test_beam_search_batched import batched_beam_search, flat_lm
+    from speechless_amd.decoder import NGramLanguageModel
+    from speechless_amd.synthetic_lm import write_synthetic_arpa
+    small = list("cat ")
+    write_synthetic_arpa(tmp_path / "lm.arpa", small, 12, order=2, seed=3)
+    lengths = [t_max, 1, 0, t_max - 1, t_max]
+    models = ((small, None), (small, NGramLanguageModel(tmp_path / "lm.arpa")), (ALPHABET, toy_lm))
+    for seed, (alphabet, lm) in zip(seeds, models):
+        probs = softmax_rows(np.random.RandomState(seed).randn(5, t_max, len(alphabet) + 1) * 2.5)
+        for merge in (False, True):
+            host, gpu = decoders(alphabet, lm, beam_width=beam_width, merge_repeated=merge)
+            got = assert_same(host, gpu, probs, lengths)
+            assert len(got[1]) <= 1 and got[2] == []
+            stats = {"returns": 0}
+            for b, length in enumerate(lengths):
+                restated, _ = batched_beam_search(probs[b, :length], beam_width, merge, flat_lm(host) if lm else None,
+                                                  stats=stats)
+                assert restated == got[b]
+            assert stats["returns"] >= 1, (seed, merge)
+
+
+@pytest.mark.gpu
 def test_generated_order4_language_model_batch(order4_lm):
     rng = np.random.RandomState(3)
     b, t = 32, 500
