@@ -11,7 +11,7 @@ LIB_PATH = PACKAGE_DIR / "libspeechless_hip.so"
 HOST_LIB_PATH = PACKAGE_DIR / "libspeechless_host.so"  # plain C++ helpers of the host input pipeline (no HIP)
 HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csrc_host" / "beam_search.cpp"]
 CXX = os.environ.get("CXX", "g++")
-SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "ctc_long.hip", "misc.hip", "spectrogram.hip", "conv_chain_bf16.hip",
+SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "ctc_long.hip", "misc.hip", "optimizer.hip", "spectrogram.hip", "conv_chain_bf16.hip",
            "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip",
            "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the

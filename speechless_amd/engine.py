@@ -1016,15 +1016,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
     def asg_adam_step(self):
         """Adam on the two ASG tables with the step's hyper-parameters and iteration count (adam_iterations already counts
         this step): one sl_adam_step launch over [g | g0].  Another rule: the same launch of its flat kernel."""
-        if self.optimizer != "adam":
-            self._launch("opt:{}:asg".format(self.optimizer), "sl_optimizer_step", self.asg_params.data_ptr(),
-                         self.asg_grads.data_ptr(), self.asg_adam_m.data_ptr(),
-                         self.asg_adam_v.data_ptr() if self.opt_slots == 2 else None, self.asg_params.numel(), self._opt_rule(),
-                         None, 0.0, self._stream())
-            return
-        self._launch("adam:asg", "sl_adam_step", self.asg_params.data_ptr(), self.asg_grads.data_ptr(),
-                     self.asg_adam_m.data_ptr(), self.asg_adam_v.data_ptr(), self.asg_params.numel(), self.adam_iterations,
-                     self._lr_now(), self.beta_1, self.beta_2, self.adam_epsilon, self._stream())
+        self._launch_adam_flat("adam:asg", (self.asg_params, self.asg_grads, self.asg_adam_m, self.asg_adam_v), 0,
+                               self.asg_params.numel(), self._stream(), clip=False)
 
     def _align_labels(self, label_batch, label_lengths, batch, asg, in_len=None, max_letters=None, too_long_text=None):
         """What the four forced aligners ask of a label batch: (B, Lmax) with B lengths (and, for a _long method, the B
@@ -1623,7 +1616,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.adam_iterations += 1
         st = self._stream()
         if not fused:
-            self._launch_adam_flat("adam", 0, self.param_numel, st)
+            self._launch_adam_flat("adam", self._state_buffers(), 0, self.param_numel, st)
             self._packed_dirty = True
             return
         if self._packed_dirty:
@@ -1655,25 +1648,31 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         rule.beta1, rule.beta2, rule.eps = self.beta_1, self.beta_2, self.adam_epsilon
         return rule
 
-    def _launch_adam_flat(self, tag, lo, hi, st):
-        """plain elementwise update on [lo, hi) of the flat buffers (the unfused step; a rank's slice under the sharded
-        optimizer).  tag: 'adam' / 'adam_shard:<b>'; another rule launches as 'opt:<rule>' / 'opt_shard:<rule>:<b>'"""
-        if self.optimizer != "adam":
+    def _state_buffers(self):
+        return (self.params, self.grads, self.adam_m, self.adam_v)
+
+    def _launch_update(self, tag, name, what, pre, post, st, clip=True):
+        """One launch of the update, flat or fused: the ONE place that tells Adam from the other rules.  tag and name are Adam's
+        ('adam...', 'sl_*adam_*'); another rule launches the same kernel family as 'opt:<rule>...' / 'opt_shard:<rule>...' through
+        'sl_*optimizer_*' with an sl_opt_rule where Adam passes (step, lr, beta_1, beta_2, epsilon).  Clipping: Adam's clipped twin
+        when there is any, else the original entry point with the arguments it always had; the other rules' entry points take
+        (None, 0) for none.  pre / post: the operand format's arguments in front of / behind the coefficients."""
+        clip = self._clip_args() if clip else None
+        if self.optimizer == "adam":
+            how = (self.adam_iterations, self._lr_now(), self.beta_1, self.beta_2, self.adam_epsilon)
+            name, clip = (name, ()) if clip is None else (name + "_clipped", clip)
+        else:
             kind, _, rest = tag.partition(":")
             tag = "{}:{}{}".format(kind.replace("adam", "opt"), self.optimizer, ":" + rest if rest else "")
-            clip = self._clip_args() or (None, 0.0)
-            self._launch(tag, "sl_optimizer_step", self.params[lo:hi].data_ptr(), self.grads[lo:hi].data_ptr(),
-                         self.adam_m[lo:hi].data_ptr(), self.adam_v[lo:hi].data_ptr() if self.opt_slots == 2 else None, hi - lo,
-                         self._opt_rule(), *clip, st)
-            return
-        what = (self.params[lo:hi].data_ptr(), self.grads[lo:hi].data_ptr(), self.adam_m[lo:hi].data_ptr(),
-                self.adam_v[lo:hi].data_ptr(), hi - lo, self.adam_iterations, self._lr_now(), self.beta_1, self.beta_2,
-                self.adam_epsilon)
-        clip = self._clip_args()
-        if clip is None:
-            self._launch(tag, "sl_adam_step", *what, st)
-        else:
-            self._launch(tag, "sl_adam_step_clipped", *what, *clip, st)
+            name, how, clip = name.replace("adam", "optimizer"), (self._opt_rule(),), clip or (None, 0.0)
+        self._launch(tag, name, *what, *pre, *how, *post, *clip, st)
+
+    def _launch_adam_flat(self, tag, buffers, lo, hi, st, clip=True):
+        """plain elementwise update on [lo, hi) of `buffers` = (parameters, gradients, first and second state slot: None for a
+        one-slot rule): the unfused step, a rank's slice under the sharded optimizer, the ASG tables (clip=False).
+        tag: 'adam' / 'adam_shard:<b>' / 'adam:asg'"""
+        what = [t[lo:hi].data_ptr() if t is not None else None for t in buffers]
+        self._launch_update(tag, "sl_adam_step", (*what, hi - lo), (), (), st, clip)
 
     # ------------------------------------------------------------------ gradient norm (clipnorm, track_grad_norm)
 
@@ -1768,46 +1767,25 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         return table
 
     def _adam_layers(self, layers, st):
-        """Fused Adam + bf16 operand repack of the given layers on stream st (self.adam_iterations already counts
-        this step): ONE launch for all of them (sl_adam_pack_layers), 16 layers per call at most."""
+        """Fused update + operand repack of the given layers on stream st (self.adam_iterations already counts this step):
+        ONE launch for all of them (sl_*adam_pack_layers; another rule: sl_*optimizer_pack_layers), 16 layers per call at
+        most."""
+        # per operand format: the entry point's prefix and its arguments in front of / behind the rule's coefficients
+        # (bf16x3: the [w_hi | w_hi | w_lo] operand rows are rewritten in the same pass, layer 0's pair view behind it)
+        if self.planes == 3 and self.x3_f16:
+            prefix, pre, post, pair = "sl_splitf16_", (), (self.w_scale,), False
+        elif self.planes == 3:
+            prefix, pre, post, pair = "sl_split3_", (), (), self.w_dgrad[0] is not None
+        else:
+            prefix, pre, post, pair = "sl_", (self.dtype_code,), (), False
         layers = list(layers)
         for lo in range(0, len(layers), 16):
             chunk = layers[lo:lo + 16]
-            table = self._adam_table(chunk)
-            if self.optimizer != "adam":
-                self._opt_layers(chunk, table, st)
-                continue
             tag = "adam:{}..{}".format(self.all_plans[chunk[0]].spec.name, self.all_plans[chunk[-1]].spec.name)
-            what = (self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(), self.adam_v.data_ptr(), table,
-                    len(chunk))
-            how = (self.adam_iterations, self._lr_now(), self.beta_1, self.beta_2, self.adam_epsilon)
-            clip = self._clip_args()  # None: the original entry points, with the arguments they always had
-            twin, clip = ("_clipped", clip) if clip is not None else ("", ())
-            if self.planes == 3 and self.x3_f16:
-                self._launch(tag, "sl_splitf16_adam_pack_layers" + twin, *what, *how, self.w_scale, *clip, st)
-            elif self.planes == 3:  # bf16x3: the [w_hi | w_hi | w_lo] operand rows are rewritten in the same pass
-                self._launch(tag, "sl_split3_adam_pack_layers" + twin, *what, *how, *clip, st)
-                if 0 in chunk and self.w_dgrad[0] is not None:
-                    self._pack_pair_dgrad_x3(st)
-            else:
-                self._launch(tag, "sl_adam_pack_layers" + twin, *what, self.dtype_code, *how, *clip, st)
-
-    def _opt_layers(self, chunk, table, st):
-        """_adam_layers for a rule beside Adam: the same fused update + repack launch (sl_*optimizer_pack_layers), no second
-        state pointer for a one-slot rule"""
-        tag = "opt:{}:{}..{}".format(self.optimizer, self.all_plans[chunk[0]].spec.name, self.all_plans[chunk[-1]].spec.name)
-        what = (self.params.data_ptr(), self.grads.data_ptr(), self.adam_m.data_ptr(),
-                self.adam_v.data_ptr() if self.opt_slots == 2 else None, table, len(chunk))
-        rule = self._opt_rule()
-        clip = self._clip_args() or (None, 0.0)  # (None, 0: the entry points launch the instantiation without clipping)
-        if self.planes == 3 and self.x3_f16:
-            self._launch(tag, "sl_splitf16_optimizer_pack_layers", *what, rule, self.w_scale, *clip, st)
-        elif self.planes == 3:
-            self._launch(tag, "sl_split3_optimizer_pack_layers", *what, rule, *clip, st)
-            if 0 in chunk and self.w_dgrad[0] is not None:
+            what = [t.data_ptr() if t is not None else None for t in self._state_buffers()]
+            self._launch_update(tag, prefix + "adam_pack_layers", (*what, self._adam_table(chunk), len(chunk)), pre, post, st)
+            if pair and 0 in chunk:
                 self._pack_pair_dgrad_x3(st)
-        else:
-            self._launch(tag, "sl_optimizer_pack_layers", *what, self.dtype_code, rule, *clip, st)
 
     def train_step(self, input_batch, label_batch, label_lengths, prediction_lengths, reducer=None):
         """One full optimisation step (forward, CTC, backward, [gradient all-reduce], Adam, weight repack).
@@ -1868,7 +1846,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         for b, (layers, (lo, hi)) in enumerate(plan):
             reducer.wait_next()
             slo, shi = reducer.shard_of(lo, hi)
-            self._launch_adam_flat("adam_shard:{}".format(b), slo, shi, st)
+            self._launch_adam_flat("adam_shard:{}".format(b), self._state_buffers(), slo, shi, st)
             reducer.gather_bucket(b, self.params)
         for layers, _ in plan:
             reducer.wait_next()

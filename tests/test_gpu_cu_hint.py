@@ -615,7 +615,7 @@ def test_chain_tile_rows_chooser_under_a_hint_is_bit_identical(hip_lib):
     [(1, 600 * 16384 + 5)],                                      # 601 chunks: more than the 512 work-groups of 64 CUs
 ])
 def test_squared_norm_under_hints_is_the_same_double(hip_lib, ranges):
-    """misc.hip sl_grad_sqnorm: the partial-sum grid is min(chunks, 8 x CUs) work-groups that stride over the 16384-float
+    """optimizer.hip sl_grad_sqnorm: the partial-sum grid is min(chunks, 8 x CUs) work-groups that stride over the 16384-float
     chunks; a chunk's partial and the order of the final sum do not depend on the grid, so the result must be the SAME double
     under 64 and 192 CUs as at 256, within 1e-12 of float64 (test_squared_norm_reduction_matches_float64_and_repeats_bit_for_bit).
     (1 << 20) + 5 floats are 65 chunks -- one work-group each under every setting; the last case has 601 chunks, which

@@ -154,20 +154,40 @@ def engine_state(eng):
         [w for w in eng.w_fwd + eng.w_dgrad if w is not None]
 
 
-@pytest.mark.parametrize("frozen", [0, 3])
+@pytest.mark.parametrize("frozen,clip", [pytest.param(0, False, id="0"), pytest.param(3, False, id="3"),
+                                         pytest.param(0, True, id="0-clip")])
 @pytest.mark.parametrize("dtype", ["bf16", "f32", "bf16x3", "f16x3"])
-@pytest.mark.parametrize("name", ["nesterov", "rmsprop", "adagrad", "adadelta", "adamax"])
-def test_fused_launch_equals_flat_launch_and_repack_bit_for_bit(name, dtype, frozen):
+@pytest.mark.parametrize("name", ["adam", "nesterov", "rmsprop", "adagrad", "adadelta", "adamax"])
+def test_fused_launch_equals_flat_launch_and_repack_bit_for_bit(name, dtype, frozen, clip):
     """two updates (the second from non-zero state): adam_step(fused=True) against adam_step(fused=False) + repack_weights();
-    masters, slots and both operand copies of every layer byte-identical"""
+    masters, slots and both operand copies of every layer byte-identical.  Six rules x four operand formats x (plain, clipped):
+    every instantiation of the fused kernel against the flat kernel's.
+
+    clip: both engines get clipnorm = half the norm n0 of the first backward (as ENGINE_CASES) and clipvalue = half the median
+    |g| of that backward.  The first update therefore runs with the factor clipnorm / n0 = 0.5 on the device, and of the scaled
+    elements 0.5 |g| those above the median exceed clipvalue = 0.5 median and are clamped, those below pass (the median counts
+    the exact zeros of dead channels, so more than half of the non-zero elements clamp: the counts are printed).  Asserted on
+    the first update; the second update's norm is whatever the first one left, and it is clipped with the same settings."""
     import torch
-    rule, hyper = CASES[name]
+    rule, hyper = dict(CASES, adam=("adam", {}))[name]
     case = make_case(b=2, t=64, seed=3)
-    engines = [make_engine(case, dtype, frozen_layer_count=frozen, **engine_kwargs(rule, hyper)) for _ in range(2)]
+    extra = {}
+    if clip:
+        _, n0, median = case_with_norm(2, 64, dtype)  # (the same case: make_case(b=2, t=64, seed=3))
+        extra = dict(clipnorm=0.5 * n0, clipvalue=0.5 * median)
+    engines = [make_engine(case, dtype, frozen_layer_count=frozen, **engine_kwargs(rule, hyper), **extra) for _ in range(2)]
     start = engines[0].params.clone()
-    for _ in range(2):
+    for it in range(2):
         for eng, fused in zip(engines, (True, False)):
             run_loss_and_grads(eng, case)
+            if clip and it == 0:
+                factor = float(eng._norm_out[1].item())
+                scaled = eng.grads.abs() * factor
+                print("fused" if fused else "flat", name, dtype, "clip factor", factor, "clipvalue", extra["clipvalue"],
+                      "clamped", int((scaled > extra["clipvalue"]).sum()), "of", int((scaled > 0).sum()), "non-zero")
+                assert factor < 1.0
+                assert bool((scaled > extra["clipvalue"]).any())
+                assert bool(((scaled > 0) & (scaled < extra["clipvalue"])).any())
             eng.adam_step(fused=fused)
             if not fused:
                 eng.repack_weights()
@@ -175,7 +195,7 @@ def test_fused_launch_equals_flat_launch_and_repack_bit_for_bit(name, dtype, fro
         for a, b in zip(engine_state(engines[0]), engine_state(engines[1])):
             assert torch.equal(a, b)
     assert not torch.equal(engines[0].params, start) and engines[0].adam_iterations == 2
-    assert (engines[0].adam_v is None) == (SLOTS[rule] == 1)
+    assert (engines[0].adam_v is None) == (dict(SLOTS, adam=2)[rule] == 1)
 
 
 # ------------------------------------------------------------------------------------------ 3. the engine's step
