@@ -127,11 +127,14 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     ((f32x4*)p)[i] = pv;
 }
 
-// Fused Adam + operand repack for ONE layer: a single pass over the layer's fp32 master weights / gradient / moments
-// [k][cin][cout] (+ the bias block that follows them) that also emits both device operand layouts
-//   w_fwd [cout][k][cin]   (32x64 tile transposed through LDS)   and   w_dgrad[cin][k-1-tap][cout]
+// Fused Adam + operand repack: a single pass over a layer's fp32 master weights / gradient / moments [k][cin][cout] (+ the
+// bias block that follows them) that also emits both device operand layouts
+//   w_fwd [cout][k][cin]   (tile transposed through LDS)   and   w_dgrad[cin][k-1-tap][cout]
 // 4 fp32 reads + 3 fp32 writes + 2 narrow writes per parameter instead of Adam (4r+3w) followed by pack (1r+2w).
-// grid (cout/64, cin/32, k + 1): z == k is the bias block (only y == 0 works there).
+// The unit of work is a TILE: 64 input channels x ADAM_CO_T output channels of one tap, so that a w_fwd run is 64 input
+// channels (a whole 128-byte line of a bf16 operand) and the fp32 runs are ADAM_CO_T * 4 bytes.  cin_pad is only a multiple of
+// 32 and cout_pad only of 64: the last tile of a row / column is cut (AdamTile::rows / cols), its spare lanes load the tile's
+// first vector again and store nothing.  After a layer's k * nci * nco weight tiles come its nco bias tiles (one row).
 // PLANES = 3 (bf16x3, T = unsigned short): the operand rows are [w_hi | w_hi | w_lo], w_hi = bf16(w), w_lo = bf16(w - w_hi).
 // FMT (PLANES = 3 only): 0 = bf16 planes, 1 = fp16 planes of wscale * w (f16x3: wscale a power of two, see split3.hip)
 template <int FMT>
@@ -148,71 +151,139 @@ __device__ __forceinline__ u32x2 pack_lo4(float a0, float a1, float a2, float a3
     auto lo = [](float v) { return v - bf16_bits_to_f32(f32_to_bf16_bits(v)); };
     return (u32x2){pack_bf16x2(lo(a0), lo(a1)), pack_bf16x2(lo(a2), lo(a3))};
 }
+constexpr int ADAM_CI_T = 64;                 // input channels of a tile: one w_fwd run
+constexpr int ADAM_CO_T = 128;                // output channels of a tile: 512-byte fp32 runs, 256-byte w_dgrad runs
+constexpr int ADAM_NV = ADAM_CO_T / 4;        // 16-byte vectors in a tile row
+constexpr int ADAM_RPP = 256 / ADAM_NV;       // tile rows one pass of the 256 threads covers
+constexpr int ADAM_N = ADAM_CI_T / ADAM_RPP;  // passes = 16-byte loads per thread and stream
+constexpr int ADAM_TN = ADAM_CO_T / 16;       // passes of the transposed store (16 threads per 64-channel run)
+
+// p, g, m and v are read once and written once per step, with nothing for a cache to keep: nontemporal.  The operand copies,
+// which the next forward reads, keep the default policy.  (profiles/adam_copy_bw_ab.json: the larger of the two gains)
+__device__ __forceinline__ f32x4 stream_load4(const float* a) { return __builtin_nontemporal_load((const f32x4*)a); }
+__device__ __forceinline__ void stream_store4(float* a, const f32x4 x) { __builtin_nontemporal_store(x, (f32x4*)a); }
+
+// every trainable layer in ONE launch: the small layers' updates (0.46 M parameters each, 8 us per launch of pure
+// latency) ride along with the big ones.  blockIdx.x is a tile id through all layers; the table maps it to its layer.
+struct AdamTable {
+    int n;
+    int tile_begin[SL_ADAM_MAX_LAYERS + 1];
+    long offset[SL_ADAM_MAX_LAYERS];  // first weight of the layer in the flat fp32 buffers
+    void* wf[SL_ADAM_MAX_LAYERS];
+    void* wd[SL_ADAM_MAX_LAYERS];
+    int k[SL_ADAM_MAX_LAYERS], cin[SL_ADAM_MAX_LAYERS], cout[SL_ADAM_MAX_LAYERS];
+};
+
+// one tile, the same in every thread of the work-group
+struct AdamTile {
+    int k, cin, cout;
+    int tap;         // == k: a bias tile (one row of `cols` floats behind the weights, no operand copy)
+    int ci0, co0;    // the tile's first input / output channel
+    int rows, cols;  // what of the 64 x ADAM_CO_T tile the layer has: 32 or 64 rows (bias: 1); a multiple of 64 columns
+    long base;       // the tile's first element in the flat fp32 buffers
+    void *wf, *wd;
+};
+
+__device__ __forceinline__ AdamTile adam_tile(const AdamTable& t, const int id) {
+    int layer = 0;
+    while (layer + 1 < t.n && id >= t.tile_begin[layer + 1]) ++layer;
+    AdamTile tl;
+    tl.k = t.k[layer], tl.cin = t.cin[layer], tl.cout = t.cout[layer];
+    tl.wf = t.wf[layer], tl.wd = t.wd[layer];
+    const int nco = (tl.cout + ADAM_CO_T - 1) / ADAM_CO_T, nci = (tl.cin + ADAM_CI_T - 1) / ADAM_CI_T;
+    const int local = id - t.tile_begin[layer];  // co tile fastest, then ci tile, then tap; the nco bias tiles last (tap == k)
+    const int rest = local / nco;
+    tl.co0 = (local - rest * nco) * ADAM_CO_T;
+    tl.tap = rest / nci;
+    tl.ci0 = (rest - tl.tap * nci) * ADAM_CI_T;
+    tl.rows = tl.tap == tl.k ? 1 : min(ADAM_CI_T, tl.cin - tl.ci0);
+    tl.cols = min(ADAM_CO_T, tl.cout - tl.co0);
+    tl.base = t.offset[layer] + ((long)tl.tap * tl.cin + tl.ci0) * tl.cout + tl.co0;  // (bias: k * cin * cout + co0)
+    return tl;
+}
+
+// One tile: all of its loads first (ADAM_N 16-byte vectors per thread and stream), then the update, the fp32 stores and both
+// operand copies.  thread -> (row ty + n * ADAM_RPP, vector tx) of the tile.
 template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0, bool CLIP = false, int RULE = SL_OPT_ADAM>
-__device__ __forceinline__ void adam_pack_block(float (&tile)[32][65], float* __restrict__ p, const float* __restrict__ g,
-                                                float* __restrict__ m, float* __restrict__ v, T* __restrict__ wf,
-                                                T* __restrict__ wd, int k, int cin, int cout, float lr_t, float b1,
-                                                float b2, float eps, int bx, int by, int bz, float wscale = 1.f,
-                                                float gs = 1.f, float cv = 0.f) {
-    const int tap = bz;
-    const int co0 = bx * 64;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+__device__ __forceinline__ void adam_pack_tile(float (&lds)[ADAM_CI_T][ADAM_CO_T + 1], const AdamTile& tl,
+                                               float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                               float* __restrict__ v, float lr_t, float b1, float b2, float eps, float wscale,
+                                               float gs, float cv) {
     constexpr bool TWO = opt_two_slots(RULE);  // (a one-slot rule: v is NULL, neither read nor written)
-    auto adam4 = [&](long idx) {
-        if (!ADAM) return *(const f32x4*)(p + idx);  // pack only: the masters are already up to date
-        const f32x4 gv = *(const f32x4*)(g + idx);
-        f32x4 mv = *(f32x4*)(m + idx), vv = TWO ? *(f32x4*)(v + idx) : (f32x4){0.f, 0.f, 0.f, 0.f}, pv = *(f32x4*)(p + idx);
+    const bool bias = tl.tap == tl.k;
+    const int tx = threadIdx.x % ADAM_NV, ty = threadIdx.x / ADAM_NV;
+    // a lane outside a cut tile takes the tile's first vector (a valid address, a line its neighbours load anyway), so that the
+    // loads stay unconditional; it stores nothing.  (both are computed again behind the loads: kept in registers they cost the third work-group per CU)
+    auto in_tile = [&](int n) { return n * ADAM_RPP + ty < tl.rows && tx * 4 < tl.cols; };
+    auto index_of = [&](int n) { return tl.base + (in_tile(n) ? (long)(n * ADAM_RPP + ty) * tl.cout + tx * 4 : 0L); };
+    f32x4 pv[ADAM_N], gv[ADAM_N], mv[ADAM_N], vv[ADAM_N];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float pj = pv[j], mj = mv[j], vj = vv[j];
-            opt_element<RULE>(pj, CLIP ? clipped_grad(gv[j], gs, cv) : gv[j], mj, vj, lr_t, b1, b2, eps);
-            pv[j] = pj, mv[j] = mj, vv[j] = vj;
+    for (int n = 0; n < ADAM_N; ++n) {
+        const long idx = index_of(n);
+        if (ADAM) {
+            gv[n] = stream_load4(g + idx);
+            mv[n] = stream_load4(m + idx);
+            if (TWO) vv[n] = stream_load4(v + idx);
+            pv[n] = stream_load4(p + idx);
+        } else {
+            pv[n] = *(const f32x4*)(p + idx);  // pack only: the masters are already up to date (and just written)
         }
-        *(f32x4*)(m + idx) = mv;
-        if (TWO) *(f32x4*)(v + idx) = vv;
-        *(f32x4*)(p + idx) = pv;
-        return pv;
-    };
-    if (tap == k) {  // bias block: cout floats right behind the weights
-        if (by == 0 && ty == 0) adam4((long)k * cin * cout + co0 + tx * 4);
-        return;
     }
-    const int ci0 = by * 32;
+    T* const wd = (T*)tl.wd;
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int cil = ty + r * 16;
-        const long idx = ((long)tap * cin + ci0 + cil) * cout + co0 + tx * 4;
-        f32x4 pv = adam4(idx);
-        if (FMT == 1) pv = pv * wscale;  // (the operand copies hold wscale * w; the masters were written by adam4)
+    for (int n = 0; n < ADAM_N; ++n) {
+        const bool mine = in_tile(n);
+        f32x4 w = pv[n];
+        if (ADAM) {
+            f32x4 s0 = mv[n], s1 = TWO ? vv[n] : (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) tile[cil][tx * 4 + j] = pv[j];
-        if (wd) {
-            T* o = wd + ((long)(ci0 + cil) * k + (k - 1 - tap)) * (PLANES * cout) + co0 + tx * 4;
+            for (int j = 0; j < 4; ++j) {
+                float pj = w[j], mj = s0[j], vj = s1[j];
+                opt_element<RULE>(pj, CLIP ? clipped_grad(gv[n][j], gs, cv) : gv[n][j], mj, vj, lr_t, b1, b2, eps);
+                w[j] = pj, s0[j] = mj, s1[j] = vj;
+            }
+            if (mine) {
+                const long idx = index_of(n);
+                stream_store4(m + idx, s0);
+                if (TWO) stream_store4(v + idx, s1);
+                stream_store4(p + idx, w);
+            }
+        }
+        if (bias) continue;
+        if (FMT == 1) w = w * wscale;  // (the operand copies hold wscale * w; the masters are written above)
+        const int row = n * ADAM_RPP + ty;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) lds[row][tx * 4 + j] = w[j];
+        if (wd && mine) {
+            T* o = wd + ((long)(tl.ci0 + row) * tl.k + (tl.k - 1 - tl.tap)) * (PLANES * tl.cout) + tl.co0 + tx * 4;
             if (PLANES == 3) {
-                const u32x2 h = pack_hi4<FMT>(pv[0], pv[1], pv[2], pv[3]);
+                const u32x2 h = pack_hi4<FMT>(w[0], w[1], w[2], w[3]);
                 *(u32x2*)o = h;
-                *(u32x2*)(o + cout) = h;
-                *(u32x2*)(o + 2 * cout) = pack_lo4<FMT>(pv[0], pv[1], pv[2], pv[3]);
+                *(u32x2*)(o + tl.cout) = h;
+                *(u32x2*)(o + 2 * tl.cout) = pack_lo4<FMT>(w[0], w[1], w[2], w[3]);
             } else if (sizeof(T) == 2) {
-                *(u32x2*)o = (u32x2){pack_bf16x2(pv[0], pv[1]), pack_bf16x2(pv[2], pv[3])};
+                *(u32x2*)o = (u32x2){pack_bf16x2(w[0], w[1]), pack_bf16x2(w[2], w[3])};
             } else {
-                *(f32x4*)o = pv;
+                *(f32x4*)o = w;
             }
         }
     }
+    if (bias) return;  // (the same in every thread)
     __syncthreads();
-    // transposed store: 64 co rows x 32 ci; thread -> (co = threadIdx/8 + 32*r, ci4 = (threadIdx%8)*4)
+    // transposed store: ADAM_CO_T co rows x 64 ci; thread -> (co = threadIdx / 16 + 16 * n, ci4 = (threadIdx % 16) * 4)
+    T* const wf = (T*)tl.wf;
 #pragma unroll
-    for (int r = 0; r < 2; ++r) {
-        const int col = (threadIdx.x >> 3) + r * 32;
-        const int ci4 = (threadIdx.x & 7) * 4;
-        T* o = wf + ((long)(co0 + col) * k + tap) * (PLANES * cin) + ci0 + ci4;
-        const float a0 = tile[ci4][col], a1 = tile[ci4 + 1][col], a2 = tile[ci4 + 2][col], a3 = tile[ci4 + 3][col];
+    for (int n = 0; n < ADAM_TN; ++n) {
+        const int col = (threadIdx.x >> 4) + n * 16;
+        const int ci4 = (threadIdx.x & 15) * 4;
+        const float a0 = lds[ci4][col], a1 = lds[ci4 + 1][col], a2 = lds[ci4 + 2][col], a3 = lds[ci4 + 3][col];
+        if (col >= tl.cols || ci4 >= tl.rows) continue;
+        T* o = wf + ((long)(tl.co0 + col) * tl.k + tl.tap) * (PLANES * tl.cin) + tl.ci0 + ci4;
         if (PLANES == 3) {
             const u32x2 h = pack_hi4<FMT>(a0, a1, a2, a3);
             *(u32x2*)o = h;
-            *(u32x2*)(o + cin) = h;
-            *(u32x2*)(o + 2 * cin) = pack_lo4<FMT>(a0, a1, a2, a3);
+            *(u32x2*)(o + tl.cin) = h;
+            *(u32x2*)(o + 2 * tl.cin) = pack_lo4<FMT>(a0, a1, a2, a3);
         } else if (sizeof(T) == 2) {
             *(u32x2*)o = (u32x2){pack_bf16x2(a0, a1), pack_bf16x2(a2, a3)};
         } else {
@@ -221,59 +292,43 @@ __device__ __forceinline__ void adam_pack_block(float (&tile)[32][65], float* __
     }
 }
 
-// every trainable layer in ONE launch: the small layers' updates (0.46 M parameters each, 8 us per launch of pure
-// latency) ride along with the big ones.  blockIdx.x is a linear block id; the table maps it to (layer, x, y, z).
-struct AdamTable {
-    int n;
-    int block_begin[SL_ADAM_MAX_LAYERS + 1];
-    long offset[SL_ADAM_MAX_LAYERS];  // first weight of the layer in the flat fp32 buffers
-    void* wf[SL_ADAM_MAX_LAYERS];
-    void* wd[SL_ADAM_MAX_LAYERS];
-    int k[SL_ADAM_MAX_LAYERS], cin[SL_ADAM_MAX_LAYERS], cout[SL_ADAM_MAX_LAYERS];
-};
-
+// one work-group per tile
 template <typename T, bool ADAM = true, int PLANES = 1, int FMT = 0, bool CLIP = false, int RULE = SL_OPT_ADAM>
 __global__ __launch_bounds__(256) void adam_pack_multi_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                               float* __restrict__ m, float* __restrict__ v, AdamTable t,
                                                               float lr_t, float b1, float b2, float eps, float wscale = 1.f,
                                                               const float* __restrict__ gscale = nullptr, float cv = 0.f) {
-    __shared__ float tile[32][65];
-    int layer = 0;
-    while (layer + 1 < t.n && (int)blockIdx.x >= t.block_begin[layer + 1]) ++layer;
-    const int local = blockIdx.x - t.block_begin[layer];
-    const int k = t.k[layer], cin = t.cin[layer], cout = t.cout[layer];
-    const int nx = cout / 64, ny = cin / 32;
-    const int bx = local % nx, by = (local / nx) % ny, bz = local / (nx * ny);
-    const long off = t.offset[layer];
-    if (!ADAM && bz == k) return;  // (the bias block has no operand copy)
+    __shared__ float lds[ADAM_CI_T][ADAM_CO_T + 1];
+    const AdamTile tl = adam_tile(t, blockIdx.x);
+    if (!ADAM && tl.tap == tl.k) return;  // (the bias block has no operand copy)
     const float gs = (CLIP && gscale) ? *gscale : 1.f;
-    adam_pack_block<T, ADAM, PLANES, FMT, CLIP, RULE>(tile, p + off, ADAM ? g + off : nullptr, ADAM ? m + off : nullptr,
-                                                      (ADAM && opt_two_slots(RULE)) ? v + off : nullptr, (T*)t.wf[layer],
-                                                      (T*)t.wd[layer], k, cin, cout, lr_t, b1, b2, eps, bx, by, bz, wscale, gs,
-                                                      cv);
+    adam_pack_tile<T, ADAM, PLANES, FMT, CLIP, RULE>(lds, tl, p, g, m, v, lr_t, b1, b2, eps, wscale, gs, cv);
 }
 
 }  // namespace
 
-static int adam_table_from(const sl_adam_layer* layers, int n_layers, const char* who, AdamTable* t, int* blocks_out) {
+// the table of a call; *tiles_out: the grid of its launch
+static int adam_table_from(const sl_adam_layer* layers, int n_layers, const char* who, AdamTable* t, int* tiles_out) {
     t->n = n_layers;
-    int blocks = 0;
+    long tiles = 0;
     for (int i = 0; i < n_layers; ++i) {
         const sl_adam_layer& L = layers[i];
         SL_CHECK_ARG(L.w_fwd && L.k > 0 && L.cin_pad > 0 && L.cout_pad > 0 && L.cin_pad % 32 == 0 && L.cout_pad % 64 == 0 &&
                          L.offset >= 0 && L.offset % 4 == 0,
                      "%s: layer %d: need w_fwd, cin_pad %% 32 == 0, cout_pad %% 64 == 0, offset %% 4 == 0", who, i);
-        t->block_begin[i] = blocks;
+        t->tile_begin[i] = (int)tiles;
         t->offset[i] = L.offset;
         t->wf[i] = L.w_fwd;
         t->wd[i] = L.w_dgrad;
         t->k[i] = L.k;
         t->cin[i] = L.cin_pad;
         t->cout[i] = L.cout_pad;
-        blocks += (L.cout_pad / 64) * (L.cin_pad / 32) * (L.k + 1);
+        const long nco = (L.cout_pad + ADAM_CO_T - 1) / ADAM_CO_T, nci = (L.cin_pad + ADAM_CI_T - 1) / ADAM_CI_T;
+        tiles += nco * nci * L.k + nco;  // (+ the bias tiles)
+        SL_CHECK_ARG(tiles < (1L << 30), "%s: layer %d: too many tiles for one launch", who, i);
     }
-    t->block_begin[n_layers] = blocks;
-    *blocks_out = blocks;
+    t->tile_begin[n_layers] = (int)tiles;
+    *tiles_out = (int)tiles;
     return SL_OK;
 }
 
@@ -366,7 +421,7 @@ static int launch_flat(const char* who, const OptArgs& a, size_t n, const OptCoe
 }
 
 // THE fused update + repack launch of the nine *_pack_layers entry points and sl_adam_pack_layer.
-// T / PLANES / FMT: the operand format (adam_pack_block)
+// T / PLANES / FMT: the operand format (adam_pack_tile)
 template <typename T, int PLANES, int FMT>
 static int launch_fused(const char* who, const OptArgs& a, const sl_adam_layer* layers, int n_layers, const OptCoeffs& c,
                         float w_scale) {
@@ -494,8 +549,8 @@ extern "C" int sl_splitf16_optimizer_pack_layers(float* param, const float* grad
                             rule_coeffs(who, rule), w_scale);
 }
 
-// one layer block (param, grad, m, v point at its first weight): a one-row table through the fused launch -- the same block
-// function over the same (cout_pad / 64) * (cin_pad / 32) * (k + 1) work-groups.  (any dtype but SL_BF16 means fp32 here)
+// one layer block (param, grad, m, v point at its first weight): a one-row table through the fused launch -- the same tile
+// function over the same tiles.  (any dtype but SL_BF16 means fp32 here)
 extern "C" int sl_adam_pack_layer(float* param, const float* grad, float* m, float* v, void* w_fwd, void* w_dgrad, int k,
                                   int cin_pad, int cout_pad, int dtype, int step, float lr, float beta1, float beta2,
                                   float eps, void* stream) {
