@@ -35,6 +35,12 @@
 //   * conv_nt_ks2_bf16_kernel (cfg it = 5) is the 128x128 tile with eight waves, the two waves of a SIMD splitting the k-halves.
 //   The library's measured table (auto_cfg) picks shape, flavour and kernel per launch; tools/tune_kernels.py sweeps them.
 //
+// Written once for the three main kernels: nt_wave (wave id and the s_setprio block), NtTile (work-group -> split, utterance, first
+// row, first channel, steps; x_base / w_base: the slab and k-half-pair kernels), pin_epilogue_args, mma_half16 (tap-major and slab), relu_mask16 /
+// elu_mask16 (store_run16).  What each kernel still holds for itself -- accumulator zeroing, DMA source offsets and fragment
+// addresses, the 16x16 epilogue, the request stream, the slab loops' counter advance and wait choice, the tap-major kernel's
+// tile decode -- says why where it stands: shared, it changed registers or a step loop of some instantiation.
+//
 // Host side: NT_VARIANTS lists every compiled tile variant once, as (kernel kind, m32, it, wm, wn, ring slots, pipelined,
 // interleaved) plus its launcher; valid_cfg() looks a decoded cfg word up in that list and applies the geometry rules, and
 // conv_nt_bf16() launches what it found.  The LDS-DMA / fragment-read helpers live in lds_dma.h (shared with the fused output
@@ -104,6 +110,33 @@ __device__ __forceinline__ unsigned int plane_pack_lo(float a0, float a1, unsign
 #define SL_NT_ACC_SCALE_BIAS(v, b, a) ((v) + (b))
 #endif
 
+// ReLU / ELU backward on a run of 16 channels: m = the 16 stored bf16 activations of the same row and channels
+__device__ __forceinline__ void relu_mask16(float (&v)[16], const __bf16* m) {
+    const u32x4 m0 = *(const u32x4*)(m);
+    const u32x4 m1 = *(const u32x4*)(m + 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        // bf16 > 0  <=>  sign bit clear and magnitude non-zero
+        const unsigned int lo0 = m0[i] & 0xFFFFu, hi0 = m0[i] >> 16;
+        const unsigned int lo1 = m1[i] & 0xFFFFu, hi1 = m1[i] >> 16;
+        if (!(lo0 != 0 && lo0 < 0x8000u)) v[i * 2] = 0.f;
+        if (!(hi0 != 0 && hi0 < 0x8000u)) v[i * 2 + 1] = 0.f;
+        if (!(lo1 != 0 && lo1 < 0x8000u)) v[8 + i * 2] = 0.f;
+        if (!(hi1 != 0 && hi1 < 0x8000u)) v[8 + i * 2 + 1] = 0.f;
+    }
+}
+__device__ __forceinline__ void elu_mask16(float (&v)[16], const __bf16* m) {
+    const u32x4 m0 = *(const u32x4*)(m);
+    const u32x4 m1 = *(const u32x4*)(m + 8);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[i * 2] *= elu_grad_from_y(bf16_lo(m0[i]));
+        v[i * 2 + 1] *= elu_grad_from_y(bf16_hi(m0[i]));
+        v[8 + i * 2] *= elu_grad_from_y(bf16_lo(m1[i]));
+        v[8 + i * 2 + 1] *= elu_grad_from_y(bf16_hi(m1[i]));
+    }
+}
+
 // epilogue of one run of 16 consecutive output channels of one time row
 template <int MODE, bool OUT_F32>
 __device__ __forceinline__ void store_run16(const NtArgs& a, float (&v)[16], const float (&bias_v)[16], long yidx) {
@@ -122,31 +155,8 @@ __device__ __forceinline__ void store_run16(const NtArgs& a, float (&v)[16], con
 #pragma unroll
         for (int i = 0; i < 16; ++i) v[i] = elu_f(v[i]);
     }
-    if (MODE == SL_EPI_ELU_MASK) {
-        const u32x4 m0 = *(const u32x4*)(a.mask + yidx);
-        const u32x4 m1 = *(const u32x4*)(a.mask + yidx + 8);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[i * 2] *= elu_grad_from_y(bf16_lo(m0[i]));
-            v[i * 2 + 1] *= elu_grad_from_y(bf16_hi(m0[i]));
-            v[8 + i * 2] *= elu_grad_from_y(bf16_lo(m1[i]));
-            v[8 + i * 2 + 1] *= elu_grad_from_y(bf16_hi(m1[i]));
-        }
-    }
-    if (MODE == SL_EPI_RELU_MASK) {
-        const u32x4 m0 = *(const u32x4*)(a.mask + yidx);
-        const u32x4 m1 = *(const u32x4*)(a.mask + yidx + 8);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            // bf16 > 0  <=>  sign bit clear and magnitude non-zero
-            const unsigned int lo0 = m0[i] & 0xFFFFu, hi0 = m0[i] >> 16;
-            const unsigned int lo1 = m1[i] & 0xFFFFu, hi1 = m1[i] >> 16;
-            if (!(lo0 != 0 && lo0 < 0x8000u)) v[i * 2] = 0.f;
-            if (!(hi0 != 0 && hi0 < 0x8000u)) v[i * 2 + 1] = 0.f;
-            if (!(lo1 != 0 && lo1 < 0x8000u)) v[8 + i * 2] = 0.f;
-            if (!(hi1 != 0 && hi1 < 0x8000u)) v[8 + i * 2 + 1] = 0.f;
-        }
-    }
+    if (MODE == SL_EPI_ELU_MASK) elu_mask16(v, a.mask + yidx);
+    if (MODE == SL_EPI_RELU_MASK) relu_mask16(v, a.mask + yidx);
     if (OUT_F32) {
         if (a.out_planes) {
             // bf16x3 (split3.hip): what sl_split3 would do to the fp32 tile in a second pass over HBM -- activation, then
@@ -156,7 +166,9 @@ __device__ __forceinline__ void store_run16(const NtArgs& a, float (&v)[16], con
 #pragma unroll
                 for (int i = 0; i < 16; ++i) v[i] = fmaxf(v[i], 0.f);
             }
-            if (a.out_planes == 3) {  // mask = the stored activation's hi plane, same geometry as y
+            // mask = the stored activation's hi plane, same geometry as y.  (Own copy of relu_mask16: called from this run-time
+            // branch it changes the code of every fp32 / plane-output kernel, registers included.)
+            if (a.out_planes == 3) {
                 const u32x4 m0 = *(const u32x4*)(a.mask + yidx);
                 const u32x4 m1 = *(const u32x4*)(a.mask + yidx + 8);
 #pragma unroll
@@ -256,6 +268,79 @@ struct IlvPhase<IT, G, NQ, NQ, RPG> {
                                                bf16x8 (&)[IT], unsigned, unsigned, const Hook&) {}
 };
 
+// ---- the pieces the three main kernels below are made of
+// wave id, with static priority for the second-dispatched half of the waves (MI355X_MICROARCH.md, "two waves per SIMD", item 4: the
+// younger wave of a SIMD loses every issue arbitration): same-box A/B of the config-3 step 2.2475 -> 2.2374 ms, three alternations
+// of the two builds, every one in favour (profiles/r05_prio_young_ab.txt)
+template <bool PRIO_YOUNG>
+__device__ __forceinline__ int nt_wave() {
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+#if !defined(SL_NO_PRIO_YOUNG)
+    if constexpr (PRIO_YOUNG)
+        if (wave >= (int)(blockDim.x >> 7)) __builtin_amdgcn_s_setprio(1);
+#endif
+    return wave;
+}
+
+// The tile of a work-group: split `split` of the contraction (steps [s_begin, s_begin + n)) of the BM time rows from t0 of utterance b
+// times the BN output channels from co0.
+template <int BM, int BN>
+struct NtTile {
+    int id, split, b, t0, co0, s_begin, n;
+    __device__ __forceinline__ bool decode(const NtArgs& a) {
+        const int m_tiles = a.batch * a.t_tiles;
+        const int tiles = m_tiles * a.n_tiles;
+        id = xcd_remap(blockIdx.x, tiles * a.ksplit);
+        if (id >= tiles * a.ksplit) return false;  // grid padding (xcd_grid)
+        split = id / tiles;
+        const int tile = id - split * tiles;
+        // raster: consecutive ids (= one XCD's concurrently resident work-groups, see xcd_remap) cover a 2-D block of
+        // n_tiles x gm tiles, so that the activation rows AND the weight panels an XCD streams both stay within its 4 MiB
+        // L2.  With gm = m_tiles (1-D, weight-panel-major) big_conv_1's 32 resident activation tiles per XCD (4.7 MB) are
+        // evicted between taps: 1.25 GB per launch re-fetched from the Infinity Cache (profiles/r01c_pmc_*.json).
+        const int span = a.n_tiles * a.gm;
+        const int blk = tile / span;
+        const int rem = tile - blk * span;
+        int cnt = m_tiles - blk * a.gm;
+        if (cnt > a.gm) cnt = a.gm;
+        const int n_tile = rem / cnt;
+        const int m_tile = blk * a.gm + (rem - n_tile * cnt);
+        b = m_tile / a.t_tiles;
+        t0 = (m_tile - b * a.t_tiles) * BM;
+        co0 = n_tile * BN;
+        s_begin = split * a.steps_per_split;  // (slab kernel: a multiple of taps, whole chunks per split)
+        n = a.nsteps - s_begin;
+        if (n > a.steps_per_split) n = a.steps_per_split;
+        return true;
+    }
+    // tap 0, channel 0 of the tile's first activation row / first weight row
+    __device__ __forceinline__ const __bf16* x_base(const NtArgs& a) const {
+        return a.x + (long)b * a.x_bs + (long)(a.x_row0 + t0) * a.x_rs;
+    }
+    __device__ __forceinline__ const __bf16* w_base(const NtArgs& a) const { return a.w + (long)co0 * a.w_rs; }
+};
+
+// ---- a wave's accumulators of the 16x16 shape: [jn][it] tiles, 64 output channels x 16 * IT time rows.
+// The 4 * IT MFMAs of one k-half.  (Every kernel zeroes the accumulators with its own loop: zeroed through a shared function,
+// most instantiations come out with other register counts.)
+template <int IT>
+__device__ __forceinline__ void mma_half16(f32x4 (&acc)[4 * IT], const bf16x8 (&af)[4], const bf16x8 (&bfr)[IT]) {
+#pragma unroll
+    for (int jn = 0; jn < 4; ++jn)
+#pragma unroll
+        for (int it = 0; it < IT; ++it) acc[jn * IT + it] = SL_MFMA16(af[jn], bfr[it], acc[jn * IT + it]);
+}
+
+// Everything the epilogue needs from the kernel arguments is pulled into SGPRs where this stands (after the accumulators are
+// zeroed, before the loop).  Left alone, the compiler parks those scalar loads in the loop pre-header without waiting for them,
+// and a scalar load pending at the loop head forces it to emit lgkmcnt(0) instead of counted waits in front of every MFMA
+// group inside the loop (LDS and scalar loads share the counter and return out of order with respect to each other).
+__device__ __forceinline__ void pin_epilogue_args(NtArgs& e) {
+    asm volatile("" : "+s"(e.y), "+s"(e.mask), "+s"(e.bias), "+s"(e.partial), "+s"(e.y_bs));
+    asm volatile("" : "+s"(e.y_row0), "+s"(e.y_rs), "+s"(e.t_out), "+s"(e.cout), "+s"(e.batch), "+s"(e.t_tiles));
+}
+
+
 // STAGES = ring slots; PIPE = register-pipelined main loop (fragments of the next tile's first half are read from LDS while
 // the MFMAs of the current tile's second half run, see the loop); ILV = hand-interleaved variant of the pipelined loop
 template <bool M32, int IT, int WM, int WN, int STAGES, bool PIPE, bool ILV, int MODE, bool OUT_F32>
@@ -276,27 +361,19 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if !defined(SL_NO_PRIO_YOUNG)
-    // static priority for the second-dispatched half of the waves (MI355X_MICROARCH.md, "two waves per SIMD", item 4: the younger
-    // wave of a SIMD loses every issue arbitration): same-box A/B of the config-3 step 2.2475 -> 2.2374 ms, three alternations
-    // of the two builds, every one in favour (profiles/r05_prio_young_ab.txt)
-    if (wave >= (int)(blockDim.x >> 7)) __builtin_amdgcn_s_setprio(1);
-#endif
+    const int wave = nt_wave<true>();
     const int wm = wave / WN;  // which block of time rows
     const int wn = wave % WN;  // which 64-channel block (co)
 
+    // (own copy of NtTile::decode: through the struct the plain ring's loop of the 256x256 tile comes out with its scalar ring
+    // arithmetic in other places)
     const int m_tiles = a.batch * a.t_tiles;
     const int tiles = m_tiles * a.n_tiles;
     const int id = xcd_remap(blockIdx.x, tiles * a.ksplit);
     if (id >= tiles * a.ksplit) return;  // grid padding (xcd_grid)
     const int split = id / tiles;
     const int tile = id - split * tiles;
-    // raster: consecutive ids (= one XCD's concurrently resident work-groups, see xcd_remap) cover a 2-D block of
-    // n_tiles x gm tiles, so that the activation rows AND the weight panels an XCD streams both stay within its 4 MiB
-    // L2.  With gm = m_tiles (1-D, weight-panel-major) big_conv_1's 32 resident activation tiles per XCD (4.7 MB) are
-    // evicted between taps: 1.25 GB per launch re-fetched from the Infinity Cache (profiles/r01c_pmc_*.json).
-    const int span = a.n_tiles * a.gm;
+    const int span = a.n_tiles * a.gm;  // 2-D raster, see NtTile
     const int blk = tile / span;
     const int rem = tile - blk * span;
     int cnt = m_tiles - blk * a.gm;
@@ -314,6 +391,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
     // swizzle keys (function of the tile row r):
     //   16x16 shape, activations: r & 7            weights: ((r>>1)&1) | (((r>>4)&3)<<1)   (rows reach the MFMA permuted)
     //   32x32 shape, both:        ((r>>1)&3) | (((r>>4)&1)<<2)
+    // (these source offsets and the fragment read addresses below are written out in each of the three kernels: computed
+    // through shared helpers the same expressions reach the scheduler in another order, and the register counts of the slab
+    // and k-half-pair kernels move with it)
     const __bf16* xbase = a.x + (long)b * a.x_bs + (long)(a.x_row0 + t0) * a.x_rs;
     const __bf16* wbase = a.w + (long)co0 * a.w_rs;
     int xoff[XPW], woff[WPW];
@@ -385,8 +465,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc32[i][r] = 0.f;
 
-    // one 64-channel step = two halves of 32 channels; a half's fragments: NA weight vectors + NB activation vectors
-    constexpr int NA = M32 ? 4 : 4;
+    // one 64-channel step = two halves of 32 channels; a half's fragments: NA = 4 weight vectors + NB activation vectors
+    constexpr int NA = 4;
     constexpr int NB = M32 ? 4 : IT;
     auto load_half = [&](int slot, int h, bf16x8 (&af)[NA], bf16x8 (&bfr)[NB]) {
         const char* sl = smem + slot * STAGE_BYTES;
@@ -407,31 +487,21 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
         }
     };
     auto mma_half = [&](const bf16x8 (&af)[NA], const bf16x8 (&bfr)[NB]) {
-        if (M32) {
+        if constexpr (M32) {
 #pragma unroll
             for (int k2 = 0; k2 < 2; ++k2)
 #pragma unroll
                 for (int jn = 0; jn < 2; ++jn)
 #pragma unroll
                     for (int it = 0; it < 2; ++it)
-                        acc32[jn * 2 + it] = SL_MFMA32(af[k2 * 2 + jn], bfr[k2 * 2 + it],
-                                                                                     acc32[jn * 2 + it]);
+                        acc32[jn * 2 + it] = SL_MFMA32(af[k2 * 2 + jn], bfr[k2 * 2 + it], acc32[jn * 2 + it]);
         } else {
-#pragma unroll
-            for (int jn = 0; jn < 4; ++jn)
-#pragma unroll
-                for (int it = 0; it < IT; ++it)
-                    acc[jn * IT + it] = SL_MFMA16(af[jn], bfr[it], acc[jn * IT + it]);
+            mma_half16<IT>(acc, af, bfr);
         }
     };
 
-    // Everything the epilogue needs from the kernel arguments is pulled into SGPRs HERE.  Left alone, the compiler parks
-    // those scalar loads in the loop pre-header without waiting for them, and a scalar load pending at the loop head
-    // forces it to emit lgkmcnt(0) instead of counted waits in front of every MFMA group inside the loop (LDS and
-    // scalar loads share the counter and return out of order with respect to each other).
     NtArgs e = a;
-    asm volatile("" : "+s"(e.y), "+s"(e.mask), "+s"(e.bias), "+s"(e.partial), "+s"(e.y_bs));
-    asm volatile("" : "+s"(e.y_row0), "+s"(e.y_rs), "+s"(e.t_out), "+s"(e.cout), "+s"(e.batch), "+s"(e.t_tiles));
+    pin_epilogue_args(e);
 
     if constexpr (ILV) {
         // ---- interleaved schedule (see IlvPhase).  Per step and wave:
@@ -638,7 +708,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
         }
     }
 
-    // ---- epilogue: the lane holds runs of 16 consecutive channels of a time row
+    // ---- epilogue: the lane holds runs of 16 consecutive channels of a time row.  (The slab and k-half-pair kernels carry
+    // their own copy of the 16x16 path: as one shared function over the tile and the accumulators it changed the register
+    // counts of the pipelined and plain instantiations of all three kernels.)
     //   16x16 shape: per it one run   at co0 + wn*64 + (lane>>4)*16, row t0 + wm*WROWS + it*16 + (lane&15)
     //   32x32 shape: per (it, jn) one at co0 + wn*64 + jn*32 + (lane>>5)*16, row t0 + wm*64 + it*32 + (lane&31)
     constexpr int NRUN_T = M32 ? 2 : IT;
@@ -710,45 +782,23 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#if !defined(SL_NO_PRIO_YOUNG)
-    // static priority for the second-dispatched half of the waves (MI355X_MICROARCH.md, "two waves per SIMD", item 4: the younger
-    // wave of a SIMD loses every issue arbitration): same-box A/B of the config-3 step 2.2475 -> 2.2374 ms, three alternations
-    // of the two builds, every one in favour (profiles/r05_prio_young_ab.txt)
-    if (wave >= (int)(blockDim.x >> 7)) __builtin_amdgcn_s_setprio(1);
-#endif
+    const int wave = nt_wave<true>();
     const int wm = wave / WN;
     const int wn = wave % WN;
 
-    const int m_tiles = a.batch * a.t_tiles;
-    const int tiles = m_tiles * a.n_tiles;
-    const int id = xcd_remap(blockIdx.x, tiles * a.ksplit);
-    if (id >= tiles * a.ksplit) return;  // grid padding (xcd_grid)
-    const int split = id / tiles;
-    const int tile = id - split * tiles;
-    const int span = a.n_tiles * a.gm;  // 2-D raster, see conv_nt_bf16_kernel
-    const int blk = tile / span;
-    const int rem = tile - blk * span;
-    int cnt = m_tiles - blk * a.gm;
-    if (cnt > a.gm) cnt = a.gm;
-    const int n_tile = rem / cnt;
-    const int m_tile = blk * a.gm + (rem - n_tile * cnt);
-    const int b = m_tile / a.t_tiles;
-    const int t0 = (m_tile - b * a.t_tiles) * BM;
-    const int co0 = n_tile * BN;
-    const int s_begin = split * a.steps_per_split;  // a multiple of taps (whole chunks per split)
-    int n = a.nsteps - s_begin;
-    if (n > a.steps_per_split) n = a.steps_per_split;
+    NtTile<BM, BN> t;
+    if (!t.decode(a)) return;
+    const int n = t.n;
     const int taps = a.taps;
-    const int c0 = s_begin / taps;
+    const int c0 = t.s_begin / taps;  // (s_begin is a multiple of taps: whole chunks per split)
     const int nchunks = n / taps;
 
-    const __bf16* xbase = a.x + (long)b * a.x_bs + (long)(a.x_row0 + t0) * a.x_rs;
-    const __bf16* wbase = a.w + (long)co0 * a.w_rs;
+    const __bf16* xbase = t.x_base(a);
+    const __bf16* wbase = t.w_base(a);
     int xoff[XPW], xdst[XPW], woff[WPW];
     const int last_row = BM + taps - 2;  // last slab row any tap reads; rows behind it are clamped (never read from LDS)
 #pragma unroll
-    for (int q = 0; q < XPW; ++q) {
+    for (int q = 0; q < XPW; ++q) {  // (16x16 activation key, with the group and the row clamped)
         int j = wave * XPW + q;
         if (j > SLAB_GROUPS - 1) j = SLAB_GROUPS - 1;
         int row = j * 8 + (lane >> 3);
@@ -788,17 +838,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
     f32x4 acc[4 * IT];
 #pragma unroll
     for (int i = 0; i < 4 * IT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    auto mma_half = [&](const bf16x8 (&af)[4], const bf16x8 (&bfr)[IT]) {
-#pragma unroll
-        for (int jn = 0; jn < 4; ++jn)
-#pragma unroll
-            for (int it = 0; it < IT; ++it)
-                acc[jn * IT + it] = SL_MFMA16(af[jn], bfr[it], acc[jn * IT + it]);
-    };
+    auto mma_half = [&](const bf16x8 (&af)[4], const bf16x8 (&bfr)[IT]) { mma_half16<IT>(acc, af, bfr); };
 
-    NtArgs e = a;  // epilogue arguments pinned in SGPRs before the loop, see conv_nt_bf16_kernel
-    asm volatile("" : "+s"(e.y), "+s"(e.mask), "+s"(e.bias), "+s"(e.partial), "+s"(e.y_bs));
-    asm volatile("" : "+s"(e.y_row0), "+s"(e.y_rs), "+s"(e.t_out), "+s"(e.cout), "+s"(e.batch), "+s"(e.t_tiles));
+    NtArgs e = a;
+    pin_epilogue_args(e);
 
     // issue-side counters (the next weight tile to request) and compute-side counters (the step being multiplied)
     int tap_i = 0, cc_i = c0;
@@ -1007,8 +1050,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
                     bfr[it] = *(const bf16x8*)(smem + ((b_offset(par_c, tap_c) + it * 2048) ^ (kk << 6)));
                 mma_half(af, bfr);
             }
-            if (++tap_c == taps) {
-                tap_c = 0;
+            if (++tap_c == taps) {  // (the counter advance and the wait choice above are the pipelined loop's, written out again: as
+                tap_c = 0;          // shared functions they move the 3- and 4-slot loops by an instruction)
                 par_c ^= 1;
                 ++chunk_c;
             }
@@ -1018,7 +1061,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
     }
 
     // ---- epilogue (identical to conv_nt_bf16_kernel's 16x16 path)
-    const int co_base = co0 + wn * 64 + (lane >> 4) * 16;
+    const int co_base = t.co0 + wn * 64 + (lane >> 4) * 16;
     float bias_v[16];
     if (MODE == SL_EPI_BIAS || MODE == SL_EPI_BIAS_RELU || MODE == SL_EPI_BIAS_ELU) load_bias16(e.bias, co_base, bias_v);
 #pragma unroll
@@ -1030,13 +1073,13 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN >= 16 ? 4 : 2)) void conv_nt
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[jn * 4 + r] = acc[jn * IT + it][r];
         if (MODE == MODE_PARTIAL) {
-            float* out = e.partial + ((long)(split * e.batch + b) * (e.t_tiles * BM) + t0 + trow) * e.cout + co_base;
+            float* out = e.partial + ((long)(t.split * e.batch + t.b) * (e.t_tiles * BM) + t.t0 + trow) * e.cout + co_base;
 #pragma unroll
             for (int i = 0; i < 4; ++i) *(f32x4*)(out + i * 4) = (f32x4){v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
         } else {
-            const int t = t0 + trow;
-            if (t < e.t_out) {
-                const long yidx = (long)b * e.y_bs + (long)(e.y_row0 + t) * e.y_rs + co_base;
+            const int tr = t.t0 + trow;
+            if (tr < e.t_out) {
+                const long yidx = (long)t.b * e.y_bs + (long)(e.y_row0 + tr) * e.y_rs + co_base;
                 store_run16<MODE, OUT_F32>(e, v, bias_v, yidx);
             }
         }
@@ -1064,34 +1107,18 @@ __global__ __launch_bounds__(512, 2) void conv_nt_ks2_bf16_kernel(NtArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = nt_wave<false>();
     const int kh = wave >> 2;  // the k-half this wave multiplies
     const int pw = wave & 3;   // the patch it shares with wave pw + 4 * (1 - kh)
     const int wm = pw / WN;
     const int wn = pw % WN;
 
-    const int m_tiles = a.batch * a.t_tiles;
-    const int tiles = m_tiles * a.n_tiles;
-    const int id = xcd_remap(blockIdx.x, tiles * a.ksplit);
-    if (id >= tiles * a.ksplit) return;  // grid padding (xcd_grid)
-    const int split = id / tiles;
-    const int tile = id - split * tiles;
-    const int span = a.n_tiles * a.gm;  // 2-D raster, see conv_nt_bf16_kernel
-    const int blk = tile / span;
-    const int rem = tile - blk * span;
-    int cnt = m_tiles - blk * a.gm;
-    if (cnt > a.gm) cnt = a.gm;
-    const int n_tile = rem / cnt;
-    const int m_tile = blk * a.gm + (rem - n_tile * cnt);
-    const int b = m_tile / a.t_tiles;
-    const int t0 = (m_tile - b * a.t_tiles) * BM;
-    const int co0 = n_tile * BN;
-    const int s_begin = split * a.steps_per_split;
-    int n = a.nsteps - s_begin;
-    if (n > a.steps_per_split) n = a.steps_per_split;
+    NtTile<BM, BN> t;
+    if (!t.decode(a)) return;
+    const int s_begin = t.s_begin, n = t.n;
 
-    const __bf16* xbase = a.x + (long)b * a.x_bs + (long)(a.x_row0 + t0) * a.x_rs;
-    const __bf16* wbase = a.w + (long)co0 * a.w_rs;
+    const __bf16* xbase = t.x_base(a);
+    const __bf16* wbase = t.w_base(a);
     int xoff[XPW], woff[WPW];
 #pragma unroll
     for (int q = 0; q < XPW; ++q) {
@@ -1118,11 +1145,11 @@ __global__ __launch_bounds__(512, 2) void conv_nt_ks2_bf16_kernel(NtArgs a) {
 #pragma unroll
     for (int i = 0; i < 4 * IT; ++i) acc[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    NtArgs e = a;  // epilogue arguments pinned in SGPRs before the loop, see conv_nt_bf16_kernel
-    asm volatile("" : "+s"(e.y), "+s"(e.mask), "+s"(e.bias), "+s"(e.partial), "+s"(e.y_bs));
-    asm volatile("" : "+s"(e.y_row0), "+s"(e.y_rs), "+s"(e.t_out), "+s"(e.cout), "+s"(e.batch), "+s"(e.t_tiles));
+    NtArgs e = a;
+    pin_epilogue_args(e);
 
-    // request stream (see conv_nt_bf16_kernel)
+    // request stream (see conv_nt_bf16_kernel; own copy, on one count: as a struct shared with that kernel the pointer step
+    // is sign-extended in another place, five instructions fewer in its step loop and six more in this one)
     const __bf16* xs_n = nullptr;
     const __bf16* ws_n = nullptr;
     unsigned xl_n = 0, wl_n = 0;
@@ -1209,7 +1236,7 @@ __global__ __launch_bounds__(512, 2) void conv_nt_ks2_bf16_kernel(NtArgs a) {
     for (int i = 0; i < 4 * IT; ++i) acc[i] += xch[i * 64];
 
     // ---- epilogue (identical to conv_nt_bf16_kernel's 16x16 path)
-    const int co_base = co0 + wn * 64 + (lane >> 4) * 16;
+    const int co_base = t.co0 + wn * 64 + (lane >> 4) * 16;
     float bias_v[16];
     if (MODE == SL_EPI_BIAS || MODE == SL_EPI_BIAS_RELU || MODE == SL_EPI_BIAS_ELU) load_bias16(e.bias, co_base, bias_v);
 #pragma unroll
@@ -1221,13 +1248,13 @@ __global__ __launch_bounds__(512, 2) void conv_nt_ks2_bf16_kernel(NtArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) v[jn * 4 + r] = acc[jn * IT + it][r];
         if (MODE == MODE_PARTIAL) {
-            float* out = e.partial + ((long)(split * e.batch + b) * (e.t_tiles * BM) + t0 + trow) * e.cout + co_base;
+            float* out = e.partial + ((long)(t.split * e.batch + t.b) * (e.t_tiles * BM) + t.t0 + trow) * e.cout + co_base;
 #pragma unroll
             for (int i = 0; i < 4; ++i) *(f32x4*)(out + i * 4) = (f32x4){v[i * 4], v[i * 4 + 1], v[i * 4 + 2], v[i * 4 + 3]};
         } else {
-            const int t = t0 + trow;
-            if (t < e.t_out) {
-                const long yidx = (long)b * e.y_bs + (long)(e.y_row0 + t) * e.y_rs + co_base;
+            const int tr = t.t0 + trow;
+            if (tr < e.t_out) {
+                const long yidx = (long)t.b * e.y_bs + (long)(e.y_row0 + tr) * e.y_rs + co_base;
                 store_run16<MODE, OUT_F32>(e, v, bias_v, yidx);
             }
         }
