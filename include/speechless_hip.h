@@ -788,6 +788,18 @@ int sl_splitf16_bias_grad(const void* g, float* db, int batch, int t_out, int ch
                           float scale, void* workspace, size_t workspace_bytes, void* stream);
 int sl_splitf16_dropout(const void* src, void* dst, const void* y, int64_t rows, int channels, int mode, float rate,
                         uint64_t seed, void* stream);
+/* Raw-wave input on the plane paths (net.py:310-312: `wave_conv`): sl_wave_frames(SL_F32) on scale * audio followed by
+ * sl_splitf16 / sl_split3 mode 0, in ONE launch that never writes the fp32 windows (1.5 KiB per row of 256 columns instead of
+ * 1 KiB written, 1 KiB read and 1.5 KiB written) -- bit for bit the planes of those two.  Row t < t_out of utterance b receives
+ * [hi | lo | hi] over `channels` columns each of v = scale * audio[b][t * stride + j - pad_left][c] at column j * cin + c
+ * (0 outside [0, t_in) and in the columns >= k * cin), hi = cvt(v), lo = cvt(v - float(hi)), round to nearest even; rows
+ * >= t_out are not written.  fp16 planes carry 22 bits only where |v| >= 2^-3 and audio sits in [-1, 1] with quiet passages
+ * far below: `scale` (a finite positive power of two: exact) lifts the samples, and whatever contracts the windows divides it
+ * out again (sl_conv_geom.acc_scale, sl_split3_wgrad_combine_scaled).
+ *   audio: float[B][t_in][cin];   dst: [B][rows >= t_out][3 * channels] at dst_batch_stride elements per utterance (a multiple
+ *   of 8);   channels: a multiple of 8, >= k * cin;   dtype: SL_F16 or SL_BF16 (the plane format) */
+int sl_wave_frames_planes(const float* audio, void* dst, int batch, int t_in, int cin, int k, int stride, int pad_left,
+                          int t_out, int channels, int64_t dst_batch_stride, float scale, int dtype, void* stream);
 
 /* ---- audio front end (speechless/labeled_example.py:99-160, 28-29) ---------------------------
  * sl_stft_power_db: librosa.stft(y, n_fft, hop_length) with its defaults (periodic Hann window of n_fft samples,

@@ -107,13 +107,17 @@ class _Buffers:
             g.batch, g.t_out, g.taps, g.cin, g.cout = batch, 2 * tt_pad, 1, fp.cin_pad * pl, fp.cout_pad
             g.x_row0, g.x_row_stride, g.x_batch_stride = 0, fp.cin_pad * pl, 2 * tt_pad * fp.cin_pad * pl
             g.y_row0, g.y_row_stride, g.y_batch_stride = p0.pad_left, p0.cin_pad * pl, self.rows0 * p0.cin_pad * pl
+            if eng.x3_f16:  # the windows hold x_scale * x and the operand copy w_scale * w
+                g.acc_scale = 1.0 / (eng.w_scale * eng.x_scale)
             self.front_geom = g  # forward (x = frames, y = x0) and weight gradient (x = frames, "y" = gx0): t_out = input frames
             if pl > 1:
-                # bf16x3: the windows are gathered in fp32 and split into planes (sl_wave_frames + sl_split3); an ELU front
+                # bf16x3: the windows are gathered in fp32 and split into planes (sl_wave_frames + sl_split3; f16x3: straight
+                # into planes, sl_wave_frames_planes, no fp32 windows); an ELU front
                 # layer goes through the fp32 staging buffer (front_stage_geom) like every ELU layer of this path; the weight
                 # gradient is two launches -- the [hi | lo] prefix of the windows against gx0's hi plane (front_geom with
                 # cin = 2 K_pad) and their hi plane against gx0's lo plane (front_wgrad_geom_b) -- plus sl_split3_wgrad_combine
-                self.frames32 = torch.zeros((batch, 2 * tt_pad, fp.cin_pad), dtype=torch.float32, device=dev)
+                if not eng.x3_f16:
+                    self.frames32 = torch.zeros((batch, 2 * tt_pad, fp.cin_pad), dtype=torch.float32, device=dev)
                 sg = g.copy()
                 sg.y_row0, sg.y_row_stride, sg.y_batch_stride = 0, fp.cout_pad, 2 * tt_pad * fp.cout_pad
                 self.front_stage_geom = sg
@@ -296,6 +300,8 @@ class _Buffers:
                 # the longest batch of this buffer set), from where sl_split3 applies the activation mask and writes the planes
                 # of the FRAME rows (a pair row of 2 cin_pad floats = two frame rows of cin_pad)
                 dg.y_row0, dg.y_batch_stride = 0, (self.tt_pad + eng.FRONT_DGRAD_EXTRA_ROWS) * p0.cin_view
+            if eng.x3_f16:  # g_scale * g in, g_scale * g out: the scale of the pair-view operand copy is divided out
+                dg.acc_scale = 1.0 / eng.w_scale
             self.front_dgrad_geom = dg
         self.bias_ws = self.bwd1x1_ws = self.ctc_ws = self.labels = None
         self.label_len = torch.zeros((self.batch,), dtype=torch.int32, device=dev)

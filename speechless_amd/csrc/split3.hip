@@ -100,6 +100,61 @@ __global__ __launch_bounds__(256) void pack_input3_kernel(const float* __restric
     row[2 * c + ch] = hi;
 }
 
+// raw-wave input (sl_wave_frames + sl_split3 mode 0 in one pass): the sample windows of the output frames straight into planes.
+// Column j * cin + ch of frame t is audio[b][t * stride + j - pad_left][ch]: the window of frame t is the CONTIGUOUS run of
+// k * cin floats from flat index (t * stride - pad_left) * cin of the utterance, zero outside [0, t_in * cin).  A work-group
+// takes `tf` frames of one utterance and stages their span ((tf - 1) * stride + k) * cin floats, scaled, in LDS once
+// (neighbouring windows share k - stride samples); every thread then splits 8 columns of a row and writes three 16-byte
+// stores.  lds = 0: the span does not fit, every window value is read from HBM.
+template <typename F>
+__global__ __launch_bounds__(256) void wave_frames_planes_kernel(const float* __restrict__ audio, unsigned short* __restrict__ dst,
+                                                                 long n_flat, int cin, int kc, int stride, int pad_left,
+                                                                 int t_out, int c, long dst_bs, float scale, int tf, int lds) {
+    extern __shared__ float span[];
+    const int b = blockIdx.y;
+    const int t0 = blockIdx.x * tf;
+    const int rows = min(tf, t_out - t0);
+    const float* src = audio + (long)b * n_flat;
+    const long f0 = ((long)t0 * stride - pad_left) * cin;  // flat index of the tile's first window value
+    const int step = stride * cin;
+    if (lds) {
+        const int len = (rows - 1) * step + kc;
+        for (int i = threadIdx.x; i < len; i += 256) {
+            const long f = f0 + i;
+            span[i] = (f >= 0 && f < n_flat) ? src[f] * scale : 0.f;
+        }
+        __syncthreads();
+    }
+    const int c8 = c >> 3;
+    for (int it = threadIdx.x; it < rows * c8; it += 256) {
+        const int r = it / c8, col = (it - r * c8) * 8;
+        unsigned short hi[8], lo[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            float v = 0.f;
+            if (col + j < kc) {
+                if (lds) {
+                    v = span[r * step + col + j];
+                } else {
+                    const long f = f0 + (long)r * step + col + j;
+                    if (f >= 0 && f < n_flat) v = src[f] * scale;
+                }
+            }
+            split2<F>(v, hi[j], lo[j]);
+        }
+        u32x4 h, l;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            h[j] = (unsigned)hi[2 * j] | ((unsigned)hi[2 * j + 1] << 16);
+            l[j] = (unsigned)lo[2 * j] | ((unsigned)lo[2 * j + 1] << 16);
+        }
+        unsigned short* row = dst + (long)b * dst_bs + (long)(t0 + r) * (3 * c) + col;
+        *(u32x4*)row = h;
+        *(u32x4*)(row + c) = l;
+        *(u32x4*)(row + 2 * c) = h;
+    }
+}
+
 // elementwise: v -> (float(hi), v - float(hi)) so that sl_pack_weights' own rounding of the two outputs yields hi and lo
 __global__ __launch_bounds__(256) void split_f32_kernel(const float* __restrict__ v, float* __restrict__ hi,
                                                         float* __restrict__ lo, long n) {
@@ -352,6 +407,40 @@ extern "C" int sl_split3_pack_input(const float* src, void* dst, int batch, int 
 extern "C" int sl_splitf16_pack_input(const float* src, void* dst, int batch, int t_in, int f, int channels, int dst_row0,
                                       int64_t dst_batch_stride, void* stream) {
     return pack_input_impl<PlaneF16>("sl_splitf16_pack_input", src, dst, batch, t_in, f, channels, dst_row0, dst_batch_stride, stream);
+}
+
+extern "C" int sl_wave_frames_planes(const float* audio, void* dst, int batch, int t_in, int cin, int k, int stride, int pad_left,
+                                     int t_out, int channels, int64_t dst_batch_stride, float scale, int dtype, void* stream) {
+    const char* who = "sl_wave_frames_planes";
+    SL_CHECK_ARG(audio && dst, "%s: null pointer", who);
+    SL_CHECK_ARG(batch > 0 && batch <= 65535 && t_in > 0 && cin > 0 && k > 0 && stride > 0 && pad_left >= 0 && t_out > 0 &&
+                     channels > 0,
+                 "%s: bad sizes", who);
+    SL_CHECK_ARG((long)k * cin <= channels && channels % 8 == 0,
+                 "%s: a row holds k * cin = %ld columns in planes of a multiple of 8 channels", who, (long)k * cin);
+    SL_CHECK_ARG(dst_batch_stride >= (int64_t)t_out * 3 * channels && dst_batch_stride % 8 == 0,
+                 "%s: an utterance holds t_out rows of 3 * channels elements, 16-byte aligned", who);
+    SL_CHECK_ARG((long)stride * cin < (1L << 24) && (long)t_in * cin < (1L << 40), "%s: sizes out of range", who);
+    SL_CHECK_ARG(dtype == SL_F16 || dtype == SL_BF16, "%s: dtype %d is neither SL_F16 nor SL_BF16", who, dtype);
+    int exponent = 0;
+    SL_CHECK_ARG(scale > 0.f && scale <= 3.4028234e38f && frexpf(scale, &exponent) == 0.5f,
+                 "%s: scale must be a finite positive power of two", who);
+    const int kc = k * cin, step = stride * cin;
+    int tf = 16, lds = 1;  // frames per work-group: the most whose sample span fits 32 KB of LDS
+    while (tf > 1 && ((long)(tf - 1) * step + kc) * 4 > (32L << 10)) tf >>= 1;
+    if (((long)(tf - 1) * step + kc) * 4 > (32L << 10)) lds = 0;
+    const size_t lds_bytes = lds ? (size_t)((tf - 1) * step + kc) * 4 : 0;
+    const dim3 grid((unsigned)((t_out + tf - 1) / tf), batch);
+#define SL_WAVE_PLANES(F_)                                                                                                  \
+    hipLaunchKernelGGL(wave_frames_planes_kernel<F_>, grid, dim3(256), lds_bytes, (hipStream_t)stream, audio,               \
+                       (unsigned short*)dst, (long)t_in * cin, cin, kc, stride, pad_left, t_out, channels,                  \
+                       (long)dst_batch_stride, scale, tf, lds)
+    if (dtype == SL_F16)
+        SL_WAVE_PLANES(PlaneF16);
+    else
+        SL_WAVE_PLANES(PlaneBf16);
+#undef SL_WAVE_PLANES
+    return sl_check_launch(who);
 }
 
 extern "C" int sl_split3_weights(const float* v, float* hi, float* lo, size_t n, void* stream) {

@@ -31,7 +31,8 @@ from .plan import HALO, TIME_TILE, LayerPlan, LayerSpec, _round_up, same_padding
 class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
     """Forward / CTC / backward / Adam on one MI355X.  dtype 'bf16' (bf16 storage, fp32 accumulate, fp32 CTC: the
     benchmarked path), 'f32' (parity path: fp32 storage, exact-fp32 MFMA) or 'bf16x3' (the fast parity path: every value as
-    hi + lo bf16 planes, three bf16 MFMA terms per product, fp32 accumulate; csrc/split3.hip)."""
+    hi + lo bf16 planes, three bf16 MFMA terms per product, fp32 accumulate; csrc/split3.hip) or 'f16x3' (the same scheme on
+    fp16 planes under power-of-two scales: w_scale, g_scale and, under a raw-wave front layer, x_scale)."""
 
     FRONT_DGRAD_ROW0 = 7          # first pair row of x0's gradient that is computed (frames start at pair row 11)
     FRONT_DGRAD_EXTRA_ROWS = 17   # pair rows computed beyond the output frames: up to row T' + 23 = the last frame's
@@ -86,8 +87,10 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
             frozen_layer_count = max(frozen_layer_count - 1, 0)
             if self.front_spec.activation not in ("relu", "elu"):
                 raise NotImplementedError("the raw-wave layer takes a relu / elu activation")
-            if dtype == "f16x3":
-                raise NotImplementedError("raw-wave input runs on 'bf16', 'f32' and 'bf16x3' (f16x3: spectrogram input)")
+        # f16x3 under a raw-wave front layer: the gathered sample windows hold x_scale * x (audio sits in [-1, 1] with quiet
+        # passages orders of magnitude below; fp16 planes carry 22 bits only where |v| >= 2^-3: x 2^10 lifts samples down to
+        # 2^-13 into that range and keeps full-scale audio a factor of 64 below 65504).  1 on every other path.
+        self._x_scale = 1024.0 if (self.x3_f16 and self.front_spec is not None) else 1.0
         self.specs = specs
         self.all_specs = ([self.front_spec] if self.front_spec is not None else []) + list(specs)
         self.grapheme_set_size = grapheme_set_size
@@ -285,6 +288,23 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self._sharded_reducer = None  # the reducer of the last step, if that step ran Adam on this rank's slices only
 
     # ------------------------------------------------------------------ plumbing
+
+    @property
+    def x_scale(self):
+        """the power of two the gathered sample windows of the f16x3 raw-wave path are stored multiplied by (1024; 1 on every
+        other path); the front layer's launches divide it out again.  Settable until the first batch is loaded."""
+        return self._x_scale
+
+    @x_scale.setter
+    def x_scale(self, value):
+        value = float(value)
+        if not (self.x3_f16 and self.front_spec is not None):
+            raise ValueError("x_scale belongs to the raw-wave front layer of an 'f16x3' engine")
+        if not (0.0 < value < float("inf")) or np.frexp(value)[0] != 0.5:
+            raise ValueError("x_scale must be a finite positive power of two, not {!r}".format(value))
+        if self._buffers:
+            raise ValueError("x_scale is fixed once the first batch is loaded (the buffer sets' geometries hold it)")
+        self._x_scale = value
 
     def cu_hints(self):
         """the sl_set_available_cus settings this engine launches under (workspaces are sized for all of them)"""
@@ -613,7 +633,10 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
 
     def load_input(self, input_batch):
         """input_batch: (B,T,F) numpy (any float dtype; the reference packs float64, net.py:583) or a float32 torch
-        tensor already resident in HBM."""
+        tensor already resident in HBM.  Raw-wave input on 'f16x3': the sample windows are stored as fp16 planes of
+        x_scale * x, so samples must satisfy |x| * x_scale < 6.0e4 (|x| < 58 at the default 1024; audio sits in [-1, 1]) --
+        beyond that the planes saturate at 65504.  Wav2Letter checks the host batches it packs; a device tensor is not read
+        back here."""
         if isinstance(input_batch, np.ndarray):
             src = torch.from_numpy(np.ascontiguousarray(input_batch, dtype=np.float32)).to(self.device,
                                                                                             non_blocking=True)
@@ -1773,7 +1796,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         # per operand format: the entry point's prefix and its arguments in front of / behind the rule's coefficients
         # (bf16x3: the [w_hi | w_hi | w_lo] operand rows are rewritten in the same pass, layer 0's pair view behind it)
         if self.planes == 3 and self.x3_f16:
-            prefix, pre, post, pair = "sl_splitf16_", (), (self.w_scale,), False
+            prefix, pre, post, pair = "sl_splitf16_", (), (self.w_scale,), self.w_dgrad[0] is not None
         elif self.planes == 3:
             prefix, pre, post, pair = "sl_split3_", (), (), self.w_dgrad[0] is not None
         else:

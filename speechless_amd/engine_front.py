@@ -45,7 +45,11 @@ class FrontLayerMixin:
     def _front_gather(self, buf, src):
         fs, fp = self.front_spec, self.front_plan
         t_audio, t1, pad_l = buf.front_geometry
-        if self.planes > 1:  # bf16x3: fp32 windows, then the planes [hi | lo | hi] of every window row
+        if self.x3_f16:  # f16x3: the planes [hi | lo | hi] of x_scale * (every window row), one launch, no fp32 windows
+            self._launch("wave_frames", "sl_wave_frames_planes", src.data_ptr(), buf.frames.data_ptr(), buf.batch, t_audio, fs.cin,
+                         fs.kernel_size, fs.stride, pad_l, t1, fp.cin_pad, buf.frames.stride(0), self.x_scale, self.dtype_code,
+                         self._stream())
+        elif self.planes > 1:  # bf16x3: fp32 windows, then the planes [hi | lo | hi] of every window row
             self._launch("wave_frames", "sl_wave_frames", src.data_ptr(), buf.frames32.data_ptr(), buf.batch, t_audio, fs.cin,
                          fs.kernel_size, fs.stride, pad_l, t1, fp.cin_pad, buf.frames32.stride(0), _lib.SL_F32, self._stream())
             self._launch("split:wave_frames", "sl_split3", buf.frames32.data_ptr(), buf.frames.data_ptr(), None, buf.batch, t1,
@@ -102,7 +106,10 @@ class FrontLayerMixin:
         self._launch("bgrad:" + fp.spec.name, "sl_bias_grad", buf.gx0.data_ptr(), db.data_ptr(), ctypes.byref(buf.front_geom),
                      self.dtype_code, buf.bias_ws.data_ptr(), buf.bias_ws.numel(), st)
 
-    # ------------------------------------------------------------------ bf16x3 (round 5)
+    # ------------------------------------------------------------------ bf16x3 (round 5) and f16x3
+    # f16x3: the same launches on fp16 planes.  The windows hold x_scale * x, the operand copies w_scale * w and the gradient
+    # planes g_scale * g; front_geom.acc_scale = 1 / (w_scale * x_scale) and front_dgrad_geom.acc_scale = 1 / w_scale
+    # (buffers.py) and the `scale` arguments below divide them out again -- x0 holds unscaled activations on every path.
     def _front_forward_x3(self, buf, bias, st):
         """wave_conv on the planes: the unchanged NT kernel over the window rows [hi | lo | hi] against [w_hi | w_hi | w_lo];
         ReLU: bias, activation and the split into x0's planes in its epilogue (out_f32 = 2); ELU: fp32 staging + sl_split3"""
@@ -115,7 +122,7 @@ class FrontLayerMixin:
         self._launch("fwd:" + fp.spec.name, "sl_conv1d_nt", buf.frames.data_ptr(), self.w_fwd[fp.index].data_ptr(),
                      bias.data_ptr(), None, buf.stage32.data_ptr(), ctypes.byref(buf.front_stage_geom), _lib.EPI_BIAS,
                      self.dtype_code, 1, 0, buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
-        self._launch("split:" + fp.spec.name, "sl_split3", buf.stage32.data_ptr(), buf.x0.data_ptr(), None, buf.batch,
+        self._launch("split:" + fp.spec.name, self._x3("sl_split3"), buf.stage32.data_ptr(), buf.x0.data_ptr(), None, buf.batch,
                      buf.front_geom.t_out, fp.cout_pad, buf.front_stage_geom.y_batch_stride, p0.pad_left, buf.x0.stride(0),
                      2 if fp.spec.activation == "elu" else 1, st)
 
@@ -131,7 +138,7 @@ class FrontLayerMixin:
                      buf.stage32.data_ptr(), ctypes.byref(dg), _lib.EPI_NONE, self.dtype_code, 1, 0, buf.nt_ws.data_ptr(),
                      buf.nt_ws.numel(), st)
         mode = 0 if elu_dropped else (4 if elu else 3)
-        self._launch("split:dgrad:" + p0.spec.name, "sl_split3", buf.stage32.data_ptr(), buf.gx0.data_ptr(),
+        self._launch("split:dgrad:" + p0.spec.name, self._x3("sl_split3"), buf.stage32.data_ptr(), buf.gx0.data_ptr(),
                      None if elu_dropped else x0.data_ptr(), buf.batch, 2 * dg.t_out, p0.cin_pad, dg.y_batch_stride,
                      2 * self.FRONT_DGRAD_ROW0, buf.gx0.stride(0), mode, st)
         if elu_dropped:
@@ -146,11 +153,16 @@ class FrontLayerMixin:
                      ctypes.byref(buf.front_wgrad_geom_a), self.dtype_code, 0, buf.wgrad_ws.data_ptr(), buf.wgrad_ws.numel(), st)
         self._launch("wgrad_lo:" + fp.spec.name, "sl_conv1d_wgrad", buf.frames.data_ptr(), g_lo, rb.data_ptr(),
                      ctypes.byref(buf.front_wgrad_geom_b), self.dtype_code, 0, buf.wgrad_ws.data_ptr(), buf.wgrad_ws.numel(), st)
-        self._launch("combine:" + fp.spec.name, "sl_split3_wgrad_combine", ra.data_ptr(), rb.data_ptr(), dw.data_ptr(), 1,
-                     fp.cin_pad, fp.cout_pad, 1, 0, 2 * fp.cin_pad, fp.cin_pad, 0, st)
+        args = (ra.data_ptr(), rb.data_ptr(), dw.data_ptr(), 1, fp.cin_pad, fp.cout_pad, 1, 0, 2 * fp.cin_pad, fp.cin_pad, 0)
+        if self.x3_f16:  # the partial sums are x_scale * g_scale * dW (windows and gradient planes are stored scaled)
+            self._launch("combine:" + fp.spec.name, "sl_split3_wgrad_combine_scaled", *args,
+                         1.0 / (self.x_scale * self.g_scale), st)
+        else:
+            self._launch("combine:" + fp.spec.name, "sl_split3_wgrad_combine", *args, st)
         if self._x3_bias_ws is None:
             self._x3_bias_ws = torch.empty((self.lib.raw("sl_split3_bias_grad_workspace_bytes")(
                 max(q.cout_pad for q in self.plans)),), dtype=torch.uint8, device=self.device)
-        self._launch("bgrad:" + fp.spec.name, "sl_split3_bias_grad", buf.gx0.data_ptr(), db.data_ptr(), buf.batch,
-                     buf.front_geom.t_out, fp.cout_pad, p0.pad_left, buf.gx0.stride(0), self._x3_bias_ws.data_ptr(),
+        scale = (1.0 / self.g_scale,) if self.x3_f16 else ()  # (f16x3: gx0's planes hold g_scale * g)
+        self._launch("bgrad:" + fp.spec.name, self._x3("sl_split3_bias_grad"), buf.gx0.data_ptr(), db.data_ptr(), buf.batch,
+                     buf.front_geom.t_out, fp.cout_pad, p0.pad_left, buf.gx0.stride(0), *scale, self._x3_bias_ws.data_ptr(),
                      self._x3_bias_ws.numel(), st)

@@ -392,7 +392,8 @@ class Wav2Letter:
         # path (greedy decode bit-exact against the fp32 CPU port, loss to 2e-7) that shares the fp32 master weights in HBM
         # and re-packs its operand copies whenever they changed: `f16x3` (hi + lo fp16 planes, 22 operand bits; weights
         # representable up to |w| < 1000 -- eval_engine falls back to bf16x3 beyond that) for spectrogram input, `bf16x3`
-        # (hi + lo bf16 planes, fp32's range) for raw-wave input.  compute_dtype="bf16" / "f32" / "bf16x3" / "f16x3" given
+        # (hi + lo bf16 planes, fp32's range) for raw-wave input -- which runs on `f16x3` too when asked for by name
+        # (eval_dtype / compute_dtype; samples stored scaled by Engine.x_scale, _check_sample_range).  compute_dtype="bf16" / "f32" / "bf16x3" / "f16x3" given
         # explicitly: that one engine does everything (eval_dtype overrides the evaluation side alone).
         self.compute_dtype = compute_dtype if compute_dtype is not None else "bf16"
         if eval_dtype is None:
@@ -592,7 +593,22 @@ class Wav2Letter:
         input_batch = np.zeros((len(spectrograms), max(input_lengths), spectrograms[0].shape[1]), dtype=np.float32)
         for row, s in zip(input_batch, spectrograms):
             row[:s.shape[0], :s.shape[1]] = s
+        self._check_sample_range(input_batch)
         return input_batch, prediction_lengths
+
+    F16X3_SAMPLE_LIMIT = 6.0e4
+
+    def _check_sample_range(self, input_batch):
+        """Raw-wave input on f16x3: the sample windows are fp16 planes of x_scale * x (Engine.x_scale), which saturate at
+        65504 -- a host batch beyond the range is refused here, before it is uploaded."""
+        if not self.use_raw_wave_input or "f16x3" not in (self.compute_dtype, self.eval_dtype):
+            return
+        # (the evaluation engine is built lazily: until then its default scale stands in for it)
+        x_scale = max((e.x_scale for e in (self.engine, self._eval_engine) if e is not None and e.x3_f16), default=1024.0)
+        peak = float(np.abs(input_batch).max()) if input_batch.size else 0.0
+        if not peak * x_scale < self.F16X3_SAMPLE_LIMIT:
+            raise ValueError("raw-wave input on f16x3: max|x| * x_scale = {:g} * {:g} is not below the limit {:g} of the "
+                             "fp16 sample planes (audio is expected in [-1, 1])".format(peak, x_scale, self.F16X3_SAMPLE_LIMIT))
 
     def _input_dictionary_for_loss_net(self, labeled_spectrogram_batch):
         spectrograms = [x.z_normalized_transposed_spectrogram() for x in labeled_spectrogram_batch]
@@ -644,7 +660,9 @@ class Wav2Letter:
 
     def prediction_batch(self, input_batch):
         """Grapheme probabilities (B, T', K) for a (B, T, F) spectrogram batch."""
-        return self.eval_engine.forward(np.asarray(input_batch)).cpu().numpy()
+        input_batch = np.asarray(input_batch)
+        self._check_sample_range(input_batch)
+        return self.eval_engine.forward(input_batch).cpu().numpy()
 
     def predict_batch_greedily(self, spectrograms):
         input_batch, prediction_lengths = self._input_batch_and_prediction_lengths(spectrograms)

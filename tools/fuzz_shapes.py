@@ -30,7 +30,12 @@ def main():
     ap.add_argument("--wave", action="store_true",
                     help="the raw-wave topology (use_raw_wave_input: wave_conv over --bins sample channels, 256 output filters in "
                          "the wide layers to keep it quick): --max-frames then counts SAMPLES / 100 (1400 -> up to 140 000)")
+    ap.add_argument("--wave-f16x3", action="store_true",
+                    help="with --wave --x3: also the f16x3 path of the raw-wave topology (sample windows as fp16 planes of "
+                         "x_scale * x; loss within 2e-6 of fp32)")
     args = ap.parse_args()
+    if args.wave_f16x3 and not (args.wave and args.x3):
+        ap.error("--wave-f16x3 goes with --wave --x3")
     import torch
     from speechless_amd.engine import Engine, wav2letter_layer_specs
     from speechless_amd.net import Wav2Letter
@@ -42,7 +47,8 @@ def main():
         specs = wav2letter_layer_specs(args.bins, 29)
     weights = Wav2Letter._glorot_uniform(specs, 2)
     engines = {}
-    for dtype in ("bf16", "f32") + (("bf16x3",) if args.x3 else ()) + (("f16x3",) if (args.x3 and not args.wave) else ()):
+    for dtype in ("bf16", "f32") + (("bf16x3",) if args.x3 else ()) + \
+            (("f16x3",) if (args.x3 and (not args.wave or args.wave_f16x3)) else ()):
         eng = engines[dtype] = Engine(specs, 29, dtype=dtype)
         eng.max_cached_shapes = 4
     rng = np.random.RandomState(args.seed)
