@@ -89,10 +89,14 @@ __device__ __forceinline__ unsigned int pack_bf16x2_hw(float lo, float hi) {
 }
 __device__ __forceinline__ float bf16_bits_to_f32(unsigned short b) { return __uint_as_float(((unsigned int)b) << 16); }
 
-// fp32 <-> fp16 (round to nearest even, v_cvt_f16_f32; clamped to the largest finite fp16 so that an out-of-range value of the
-// f16x3 planes stays a number -- the scales of that path keep everything far inside)
+// fp32 <-> fp16 (round to nearest even, v_cvt_f16_f32; clamped to the largest finite fp16 so that an out-of-range NUMBER of
+// the f16x3 planes stays a number -- the scales of that path keep everything far inside: +-inf and every |f| >= 65520 become
+// +-65504).  Comparisons, not fminf / fmaxf: those return the other operand for a NaN, which would turn a diverged run's NaN
+// into -65504; here a NaN stays a NaN, as through the bf16 conversion.
 __device__ __forceinline__ unsigned short f32_to_f16_bits(float f) {
-    const _Float16 h = (_Float16)fminf(fmaxf(f, -65504.f), 65504.f);
+    float c = f < -65504.f ? -65504.f : f;
+    c = c > 65504.f ? 65504.f : c;
+    const _Float16 h = (_Float16)c;
     return __builtin_bit_cast(unsigned short, h);
 }
 __device__ __forceinline__ float f16_bits_to_f32(unsigned short b) { return (float)__builtin_bit_cast(_Float16, b); }

@@ -28,8 +28,12 @@ struct PlaneF16 {
     static __device__ __forceinline__ unsigned short enc(float v) { return f32_to_f16_bits(v); }
     static __device__ __forceinline__ float dec(unsigned short b) { return f16_bits_to_f32(b); }
 };
+// The pair is a function of the fp32 VALUE v.  Without the pragma a caller's product feeding v (dropout's v * scale in mode 1,
+// where no select stands between the two) is contracted into the subtraction as fma(a, b, -hi): lo then holds bits of the exact
+// product that fp32 never had, and the same element splits differently in mode 0 (all kept) and in mode 1.
 template <typename F>
 __device__ __forceinline__ void split2(float v, unsigned short& hi, unsigned short& lo) {
+#pragma clang fp contract(off)
     hi = F::enc(v);
     lo = F::enc(v - F::dec(hi));
 }

@@ -430,15 +430,7 @@ def test_optimizer_state_checkpoint_resumes_bitwise(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------ dropout
-def _dropout_keep(seed, n, rate):
-    """numpy mirror of dropout_bits (csrc/misc.hip): splitmix64 finaliser of seed + golden * (index + 1)."""
-    with np.errstate(over="ignore"):
-        idx = np.arange(1, n + 1, dtype=np.uint64)
-        z = np.uint64(seed) + np.uint64(0x9E3779B97F4A7C15) * idx
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        z ^= z >> np.uint64(31)
-    return (z >> np.uint64(32)).astype(np.uint32) >= np.uint32(int(rate * 4294967296.0))
+from plane_ref import _dropout_keep  # noqa: E402  (the numpy mirror of dropout_bits; test_gpu_round4.py imports it from here)
 
 
 @pytest.mark.parametrize("activation", ["elu", "relu"])
