@@ -824,6 +824,29 @@ size_t sl_z_normalize_workspace_bytes(int batch);
 int sl_z_normalize(const float* src, const int32_t* frames, float* dst, int batch, int max_frames, int f,
                    int src_row_stride, int64_t src_batch_stride, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- sample-rate conversion (speechless/labeled_example.py:200-205: librosa.load(file, sr=16000); DESIGN.md "Resampling") ----
+ * sl_resample_polyphase: a ragged batch of utterances (the layout of sl_stft_power_db) through the polyphase FIR bank that
+ * speechless_amd/resample.py: polyphase_bank(sr_orig, sr_new) builds, q / p = sr_new / sr_orig in lowest terms:
+ *      y[t] = sum_{j < width} bank[r][j] * x[n - (left - 1) + j],   n = (t p) div q,  r = (t p) mod q   (exact integers),
+ *      x = 0 outside [0, in_lengths[b]);   t < floor(len q / p);   y[t] = 0 for floor(len q / p) <= t < ceil(len q / p).
+ *   audio, in_offsets, in_lengths: utterance b is read at audio + in_offsets[b] and has in_lengths[b] >= 1 samples
+ *   out, out_offsets             : its ceil(in_lengths[b] q / p) outputs go to out + out_offsets[b]; nothing else is written
+ *   bank                         : float[q][width] in HBM, left = taps at and before sample n (1 <= left <= width)
+ * fp32 FMAs accumulated in fp32, in an order that depends on nothing but (p, q, width): an utterance's output does not depend
+ * on the batch it sits in.  |y[t] - exact| <= (width + 2) 2^-24 sum_j |bank[r][j]| |x[..]|.
+ * Errors (on the host, before any launch): SL_ERR_INVALID_ARGUMENT for a null pointer, batch outside [1, 65535], p or q < 1,
+ * p == q, a common factor of p and q, left outside [1, width].  SL_ERR_UNSUPPORTED beyond the limits: q <= SL_RESAMPLE_MAX_PHASES,
+ * width <= SL_RESAMPLE_MAX_TAPS, and the LDS of a tile -- its input span, (SL_RESAMPLE_TILE - 1) p / q + 1 + width floats, plus a
+ * bank chunk of q * (min(width, 4096 / q) | 1) floats -- within 64 KiB: p / q up to about 7 (96 -> 16 kHz fits, 192 -> 16 kHz
+ * does not).  One work-group per (utterance, tile of SL_RESAMPLE_TILE consecutive outputs), a fixed grid striding over the
+ * tiles (the lengths are in HBM); all work on `stream`, no workspace, no allocation, no synchronisation. */
+#define SL_RESAMPLE_TILE 2048
+#define SL_RESAMPLE_MAX_PHASES 1024
+#define SL_RESAMPLE_MAX_TAPS 4096
+int sl_resample_polyphase(const float* audio, const int64_t* in_offsets, const int32_t* in_lengths, float* out,
+                          const int64_t* out_offsets, const float* bank, int batch, int p, int q, int left, int width,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,9 @@ SIGNATURES = {
     "sl_z_normalize_workspace_bytes": (c_size_t, [c_int]),
     "sl_z_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_size_t,
                                c_void_p]),
+    # audio, in_offsets, in_lengths, out, out_offsets, bank, batch, p, q, left, width, stream
+    "sl_resample_polyphase": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_int, c_void_p]),
     "sl_bias_grad_from_wgrad": (c_int, [c_void_p, POINTER(BgwLayer), c_int, c_int, c_void_p]),
     "sl_adam_pack_layers": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, POINTER(AdamLayer), c_int, c_int, c_int,
                                     c_float, c_float, c_float, c_float, c_void_p]),

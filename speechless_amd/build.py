@@ -13,7 +13,8 @@ HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csr
 CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "ctc_long.hip", "misc.hip", "optimizer.hip", "spectrogram.hip", "conv_chain_bf16.hip",
            "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip",
-           "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip"]
+           "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
+           "resample.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
 # f16x3 parity path (csrc/common.h: SL_MFMA16; only the fp32 / plane-output instantiations, about a third of the bf16 build)
 F16_VARIANTS = {"conv_nt_f16": "conv_nt_bf16.hip", "wgrad_tn_f16": "wgrad_tn_bf16.hip"}
@@ -46,7 +47,9 @@ def _newest_source_mtime():
 # unrolled constants; scratch there is the same traffic inside the same barrier interval)
 # (ctc_long.hip: up to 4 lattice states in doubles, two chunks of 8 frames' emissions and the list builder's ranks per thread are
 # register arrays indexed by unrolled constants; scratch there is memory traffic inside the per-frame barrier interval of 16 waves)
-NO_SCRATCH = {"conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
+# (resample.hip: a thread's eight accumulators and sample offsets are register arrays indexed by unrolled constants; scratch there
+# puts a memory round trip beside every FMA of the tap loop)
+NO_SCRATCH = {"resample.hip","conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
               "ctc_align_long.hip", "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
               "ctc_long.hip"}
 

@@ -679,19 +679,48 @@ class Wav2Letter:
         return engine.greedy_decode(prediction_lengths)
 
     def predict_batch_greedily_from_audio(self, raw_audio_batch, sample_rate=16000, fourier_window_length=512,
-                                          hop_length=128):
+                                          hop_length=128, original_sample_rates=None):
         """Extension: predict_batch_greedily for raw audio (1-D float arrays).  STFT, power level, mel projection and
         z-normalisation (labeled_example.py:99-160, 28-29) run on the GPU (speechless_amd/spectrogram.py) and their result
-        feeds the conv stack directly in HBM -- no spectrogram crosses PCIe."""
+        feeds the conv stack directly in HBM -- no spectrogram crosses PCIe.
+        original_sample_rates: one rate per utterance; those that differ from `sample_rate` are converted in HBM first
+        (speechless_amd/resample.py: one launch per distinct rate), the others never pass through the filter."""
         from .spectrogram import shared_extractor
         bins = 1 + fourier_window_length // 2
         mel = None if self.input_size_per_time_step == bins else self.input_size_per_time_step
         extractor = shared_extractor(sample_rate, fourier_window_length, hop_length, mel, self.device)
-        x, frames = extractor.batch(raw_audio_batch)
+        if original_sample_rates is not None and any(int(r) != sample_rate for r in original_sample_rates):
+            x, frames = self._front_end_at_mixed_rates(extractor, raw_audio_batch, original_sample_rates)
+        else:
+            x, frames = extractor.batch(raw_audio_batch)
         engine = self.eval_engine
         engine.forward(x)
         decoded, _ = self._decode(engine, [n // self.input_to_prediction_length_ratio for n in frames])
         return [self.grapheme_encoding.decode_graphemes(d, merge_repeated=False) for d in decoded]
+
+    @staticmethod
+    def _front_end_at_mixed_rates(extractor, raw_audio_batch, rates):
+        """extractor.batch() for utterances at their own sample rates: the samples cross PCIe as they are, the converted
+        utterances are written behind them in the same device buffer and the front end reads each where it then lies."""
+        import torch
+        from .resample import MixedRatePlan
+        audios = [np.ascontiguousarray(np.asarray(a).reshape(-1), dtype=np.float32) for a in raw_audio_batch]
+        if not audios or min(a.shape[0] for a in audios) < 1:
+            raise ValueError("empty batch or empty audio")
+        lengths = np.array([a.shape[0] for a in audios], dtype=np.int32)
+        offsets = np.zeros(len(audios), dtype=np.int64)
+        offsets[1:] = np.cumsum(lengths[:-1], dtype=np.int64)
+        n = int(lengths.sum(dtype=np.int64))
+        plan = MixedRatePlan(offsets, lengths, rates, extractor.sample_rate, n)
+        if plan.lengths.min() <= extractor.n_fft // 2:
+            raise ValueError("audio shorter than {} samples cannot be reflect-padded (librosa.stft raises too)".format(
+                extractor.n_fft // 2 + 1))
+        device = extractor.device
+        buffer = torch.empty((plan.total,), dtype=torch.float32, device=device)
+        buffer[:n].copy_(torch.from_numpy(np.concatenate(audios)))
+        plan.launch(plan.to_device(device), buffer, device)
+        return extractor.batch_device(buffer, torch.from_numpy(plan.offsets).to(device),
+                                      torch.from_numpy(plan.lengths).to(device), plan.lengths)
 
     def test_and_predict_batch(self, labeled_spectrogram_batch):
         """ONE forward pass yields both the greedy transcription and the per-utterance CTC loss."""
@@ -930,8 +959,14 @@ class Wav2Letter:
     def _pack_audio_for_staging(self, labeled_example_batch):
         """The host half of a training step from raw audio (pipeline.AudioBatchStager): samples and encoded labels."""
         labels = [x.label for x in labeled_example_batch]
-        return ([x.get_raw_audio() for x in labeled_example_batch], self.grapheme_encoding.encode_label_batch(labels),
-                self._label_lengths(labels))
+        # an example that knows its file's own rate (spectrogram.LabeledExampleFromFile.get_original_audio) is staged at that
+        # rate and converted in HBM; the fourth entry names it (None: get_raw_audio() is at the net's rate already)
+        audios, rates = [], []
+        for x in labeled_example_batch:
+            audio, rate = x.get_original_audio() if hasattr(x, "get_original_audio") else (x.get_raw_audio(), None)
+            audios.append(audio)
+            rates.append(rate)
+        return (audios, self.grapheme_encoding.encode_label_batch(labels), self._label_lengths(labels), rates)
 
     def _audio_extractor(self, example):
         """The GPU front end matching this net's input (mel count = input size, or the linear 1 + n_fft / 2 bins) with the
@@ -963,7 +998,7 @@ class Wav2Letter:
 
     def train(self, labeled_spectrogram_batches, preview_labeled_spectrogram_batch, tensor_board_log_directory,
               net_directory, batches_per_epoch, max_epochs=100000000, reducer=None, prefetch_depth=3,
-              save_optimizer_state=False, from_audio=False):
+              save_optimizer_state=False, from_audio=False, front_end_on_copy_stream=False):
         """Epoch loop of reference net.py:541-576: preview, then epochs of `batches_per_epoch` steps starting at
         `load_epoch or 0`; after every epoch the preview is logged and (epoch > 0) the weights are saved as
         weights-epoch{N}.  Ends when the batch iterable is exhausted or after max_epochs (Keras: 1e8).
@@ -975,7 +1010,10 @@ class Wav2Letter:
         are computed on the GPU from their raw audio (`get_raw_audio()`): the samples arrive on the copy stream under the
         previous step, the front end runs on the compute stream in front of the step that consumes it
         (pipeline.AudioBatchStager, front_end_on_copy_stream=False) -- labeled_example.py:136-140 feeding net.py:593
-        without the spectrogram ever existing on the host.  Needs prefetch_depth > 0."""
+        without the spectrogram ever existing on the host.  Needs prefetch_depth > 0.  Examples that carry their file's own
+        sample rate (spectrogram.LabeledExampleFromFile) are staged at that rate and converted in HBM in front of the front
+        end, one launch per distinct rate (speechless_amd/resample.py).  front_end_on_copy_stream=True moves the conversion
+        and the front end onto the copy stream, beside the previous step (pipeline.AudioBatchStager)."""
         def print_preview_batch():
             log(self.test_and_predict_batch(preview_labeled_spectrogram_batch))
 
@@ -998,7 +1036,8 @@ class Wav2Letter:
             extractor = self._audio_extractor(first[0]) if first else None
             stager = AudioBatchStager(with_first(), self._pack_audio_for_staging, extractor,
                                       self.input_to_prediction_length_ratio, self.engine.device,
-                                      blank=self.grapheme_encoding.grapheme_set_size - (0 if self.criterion == "asg" else 1), depth=prefetch_depth)
+                                      blank=self.grapheme_encoding.grapheme_set_size - (0 if self.criterion == "asg" else 1), depth=prefetch_depth,
+                                      front_end_on_copy_stream=front_end_on_copy_stream)
             batches = iter(stager)
         elif prefetch_depth > 0:
             from .pipeline import BatchStager

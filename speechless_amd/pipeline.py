@@ -187,7 +187,10 @@ class AudioBatchStager(BatchStager):
     92 % of the resident-input rate), optionally on the copy stream right behind the copy, beside the training step of the
     previous batch (90 %: the step's kernels and the front end's then share the CUs and the power budget; it was the better
     choice while the front end took 0.26 ms).  The spectrogram never exists on the host.  pack(batch) -> (raw audio list, label_batch, label_lengths); prediction lengths follow from the frame
-    counts."""
+    counts.  pack may return a fourth entry, one source sample rate per utterance (None = the extractor's): utterances at
+    another rate cross PCIe as they are and are converted in HBM (speechless_amd/resample.py), one launch per distinct rate on
+    the stream that runs the front end, directly in front of it; frame counts and prediction lengths then follow from the
+    converted lengths."""
 
     def __init__(self, batches, pack, extractor, length_ratio, device, blank, depth=3, workers=3, spare_slots=5,
                  front_end_on_copy_stream=False):
@@ -203,25 +206,41 @@ class AudioBatchStager(BatchStager):
 
     def _stage(self, slot, batch):
         torch.cuda.set_device(self.device)
-        audios, labels, label_lengths = self.pack(batch)
+        audios, labels, label_lengths, *source_rates = self.pack(batch)
         b = len(audios)
+        # pack may add one source sample rate per utterance (None: already at the extractor's rate).  Utterances at another
+        # rate are staged as they are and converted in HBM, one sl_resample_polyphase launch per distinct rate directly in
+        # front of the front end (speechless_amd/resample.py); a batch with nothing to convert takes the path below unchanged
+        target_rate = self.extractor.sample_rate
+        rates = [target_rate if r is None else int(r) for r in source_rates[0]] if source_rates and source_rates[0] is not None else []
+        convert = any(r != target_rate for r in rates)
         # the samples go into the staging buffer as a (B, longest, 1) batch through the native packer (several threads, no
         # GIL: a Python loop of 32 slice copies holds the interpreter for milliseconds, which the training thread feels)
         arrays = [np.asarray(a).reshape(-1, 1) for a in audios]
         arrays = [a if a.dtype in (np.float32, np.float64) else a.astype(np.float32) for a in arrays]
         lengths = np.array([a.shape[0] for a in arrays], dtype=np.int32)
-        if lengths.min() <= self.extractor.n_fft // 2:
-            raise ValueError("audio shorter than {} samples cannot be reflect-padded".format(self.extractor.n_fft // 2 + 1))
         t_max = int(lengths.max())
         n = b * t_max
         offsets = np.arange(b, dtype=np.int64) * t_max
+        plan, total = None, n
+        if convert:  # the converted utterances go behind the n staged samples of the same device buffer
+            from .resample import MixedRatePlan, shared_resampler
+            if lengths.min() < 1:
+                raise ValueError("empty audio")
+            plan = MixedRatePlan(offsets, lengths, rates, target_rate, n)
+            for rate, _, _, _ in plan.jobs:
+                shared_resampler(rate, target_rate, self.device)  # (its bank is uploaded here, on the worker thread)
+            offsets, lengths, total = plan.offsets, plan.lengths, plan.total
+        if lengths.min() <= self.extractor.n_fft // 2:
+            raise ValueError("audio shorter than {} samples cannot be reflect-padded".format(self.extractor.n_fft // 2 + 1))
         if slot.copied is not None:
             slot.copied.synchronize()      # the previous H2D out of this staging buffer is done
         if slot.consumed is not None:
             slot.consumed.synchronize()    # ... and the readers of the slot's device buffers have run
         if slot.pinned is None or slot.pinned.numel() < n:
             slot.pinned = torch.empty((n,), dtype=torch.float32)
-            slot.device = torch.empty((n,), dtype=torch.float32, device=self.device)
+        if slot.device is None or slot.device.numel() < total:
+            slot.device = torch.empty((total,), dtype=torch.float32, device=self.device)
         pack_spectrograms(arrays, slot.pinned[:n].view(b, t_max, 1).numpy())
         labels = np.asarray(labels, dtype=np.int32)
         lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
@@ -235,17 +254,21 @@ class AudioBatchStager(BatchStager):
             labels = np.zeros((b, 1), dtype=np.int32)
         with self.copy_lock, torch.cuda.stream(self.copy_stream):
             # (the device audio buffer of this slot is only ever touched on the copy stream: refills are ordered behind
-            # the front-end kernels that read it by the stream itself)
-            audio_dev = slot.device[:n]
-            audio_dev.copy_(slot.pinned[:n], non_blocking=True)
+            # the front-end kernels that read it by the stream itself; where the front end -- and with it a rate conversion,
+            # which writes behind the n staged samples -- runs on the compute stream, by slot.consumed above)
+            audio_dev = slot.device[:total]
+            audio_dev[:n].copy_(slot.pinned[:n], non_blocking=True)
             off_dev = torch.from_numpy(offsets).to(self.device)
             len_dev = torch.from_numpy(lengths).to(self.device)
+            jobs_dev = plan.to_device(self.device) if plan is not None else None
             copied = torch.cuda.Event()
             copied.record(self.copy_stream)
             if self.time_front_end:
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 t0.record(self.copy_stream)
             if self.front_end_on_copy_stream:
+                if plan is not None:
+                    plan.launch(jobs_dev, audio_dev, self.device)
                 x_dev, frames = self.extractor.batch_device(audio_dev, off_dev, len_dev, lengths, bufs=slot.__dict__.setdefault(
                     "front_end_buffers", {}))
             else:
@@ -265,6 +288,7 @@ class AudioBatchStager(BatchStager):
         staged = StagedBatch(slot, x_dev, labels_dev, lab_len_dev, pred_len_dev, ready)
         staged.frames = frames
         staged.audio = (audio_dev, off_dev, len_dev, lengths, None if self.front_end_on_copy_stream else frames_dev)
+        staged.resample = None if plan is None or self.front_end_on_copy_stream else (plan, jobs_dev)
         return staged
 
     def __next__(self):
@@ -274,6 +298,12 @@ class AudioBatchStager(BatchStager):
             audio_dev, off_dev, len_dev, lengths, frames_dev = item.audio
             for tensor in (off_dev, len_dev, frames_dev):
                 tensor.record_stream(stream)
+            if item.resample is not None:  # source rates to convert: in HBM, directly in front of the front end
+                plan, jobs_dev = item.resample
+                for job in jobs_dev:
+                    for tensor in job[1:4]:
+                        tensor.record_stream(stream)
+                plan.launch(jobs_dev, audio_dev, self.device)
             item.x_dev, _ = self.extractor.batch_device(audio_dev, off_dev, len_dev, lengths, frames_dev,
                                                         bufs=item.slot.__dict__.setdefault("front_end_buffers", {}))
         return item

@@ -15,6 +15,8 @@ Mirrors the reference's speechless/labeled_example.py: `LabeledExample` with `ge
 spectrogram over PCIe; `LabeledExample.z_normalized_transposed_spectrogram()` is the drop-in, numpy-returning form.
 """
 import ctypes
+import logging
+from pathlib import Path
 
 import numpy as np
 import torch
@@ -195,3 +197,69 @@ class LabeledExample:
 
     def __str__(self):
         return str(self.id) + (": {}".format(self.label) if self.label else "")
+
+
+class LabeledExampleFromFile(LabeledExample):
+    """Duck type of speechless.labeled_example.LabeledExampleFromFile (labeled_example.py:174-233) for WAV files: the file is
+    parsed by speechless_amd.audio and brought to `sample_rate_to_convert_to` on the GPU (speechless_amd.resample), where the
+    reference calls librosa.load(file, sr=...).  `get_original_audio()` is the extension the staged input pipeline uses: the
+    samples at the file's own rate, to be converted in HBM together with the rest of their batch."""
+
+    def __init__(self, audio_file, id=None, sample_rate_to_convert_to=16000, label="nolabel", fourier_window_length=512,
+                 hop_length=128, mel_frequency_count=128, label_with_tags=None, positional_label=None, device="cuda:0"):
+        self.audio_file = Path(audio_file)
+        super().__init__(self._converted_audio, sample_rate=sample_rate_to_convert_to,
+                         id=self.audio_file.stem if id is None else id, label=label,
+                         fourier_window_length=fourier_window_length, hop_length=hop_length,
+                         mel_frequency_count=mel_frequency_count, label_with_tags=label_with_tags,
+                         positional_label=positional_label, device=device)
+        self._original_sample_rate = None
+        self._duration_in_s = None
+
+    def get_original_audio(self):
+        """(float32 mono samples, the file's sample rate)"""
+        from .audio import read_wav
+        return read_wav(self.audio_file)
+
+    def _converted_audio(self):
+        from .resample import resample
+        samples, rate = self.get_original_audio()
+        return resample(samples, rate, self.sample_rate, device=self._device)
+
+    @property
+    def audio_directory(self):
+        return Path(self.audio_file.parent)
+
+    @property
+    def original_sample_rate(self):
+        if self._original_sample_rate is None:
+            self._original_sample_rate = LabeledExampleFromFile.file_sample_rate(self.audio_file)
+        return self._original_sample_rate
+
+    @staticmethod
+    def file_sample_rate(audio_file):
+        from .audio import wav_sample_rate
+        return wav_sample_rate(audio_file)
+
+    @property
+    def duration_in_s(self):
+        """From the header, without decoding; 0 for a file that cannot be read (labeled_example.py:211-217)."""
+        if self._duration_in_s is None:
+            from .audio import wav_duration_in_s
+            try:
+                self._duration_in_s = wav_duration_in_s(self.audio_file)
+            except (OSError, ValueError) as e:
+                logging.getLogger("speechless_amd").info("Failed to get duration of {}: {}".format(self.audio_file, e))
+                self._duration_in_s = 0
+        return self._duration_in_s
+
+    def sections(self):
+        """One LabeledExample per word timing of `positional_label` (seconds), cut from the converted audio; None without one."""
+        if self.positional_label is None:
+            return None
+        audio = self.get_raw_audio()
+        rate = self.sample_rate
+        return [LabeledExample(lambda a=audio[int(start * rate):int(end * rate)]: a, sample_rate=rate, label=word,
+                               fourier_window_length=self.fourier_window_length, hop_length=self.hop_length,
+                               mel_frequency_count=self.mel_frequency_count, device=self._device)
+                for word, (start, end) in self.positional_label.labeled_sections]
