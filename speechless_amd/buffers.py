@@ -51,7 +51,8 @@ class _Buffers:
         self._decoded_flat = torch.zeros((batch * self.tt_pad,), dtype=torch.int32, device=dev)
         self._argmax_flat = torch.zeros((batch * self.tt_pad,), dtype=torch.int32, device=dev)
         self.g = [None] * n  # allocated lazily by ensure_backward()
-        self.align_labels = self.align_ws = None  # allocated lazily by ensure_align()
+        self.align = None  # _AlignBuffers of Engine.ctc_align / asg_align (frames = tt_pad), on first use
+        self.asg_score = self.asg_vit_ws = None  # (B,) result and workspace of Engine.asg_viterbi, on first use
         self.error_counts = self.edit_rows = None  # allocated lazily by ensure_error_counts() / ensure_edit_rows()
         self.decoded_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
         self.input_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
@@ -373,19 +374,6 @@ class _Buffers:
         if self.labels is None or self.labels.shape[1] < l_max:
             self.labels = torch.zeros((self.batch, l_max), dtype=torch.int32, device=eng.device)
 
-    def ensure_align(self, eng, l_max, workspace_query="sl_ctc_align_workspace_bytes"):
-        """Tensors of Engine.ctc_align / asg_align (an engine has one criterion, so one of the two), apart from those of the
-        loss (a forward-only engine aligns without gradient buffers): labels of up to l_max graphemes, lengths, the
-        (B, tt_pad) path / (B,) score results and the workspace, allocated on first use and grown with l_max only."""
-        if self.align_labels is None or self.align_labels.shape[1] < l_max:
-            self.align_labels = torch.zeros((self.batch, l_max), dtype=torch.int32, device=eng.device)
-            self.align_label_len = torch.zeros((self.batch,), dtype=torch.int32, device=eng.device)
-            self._align_path_flat = torch.zeros((self.batch * self.tt_pad,), dtype=torch.int32, device=eng.device)
-            self.align_score = torch.zeros((self.batch,), dtype=torch.float32, device=eng.device)
-        need = lib().raw(workspace_query)(self.batch, self.tt_pad, l_max)  # covers every length
-        if self.align_ws is None or self.align_ws.numel() < need:
-            self.align_ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=eng.device)
-
     def ensure_error_counts(self, eng, batch):
         """Results of sl_edit_distance for up to `batch` utterances: int32 (3, batch) -- letter errors, word errors, words of
         the expected row.  (The kernel needs no workspace: include/speechless_hip.h.)"""
@@ -401,27 +389,30 @@ class _Buffers:
         return self.edit_rows[:count]
 
 
-class _LongAlignBuffers:
-    """Tensors of Engine.ctc_align_long / asg_align_long (an engine has one criterion, so one of the two), which align a logq
-    tensor handed to them and so belong to no (batch, frames) buffer set: labels, lengths, the path / score results and the
-    backpointer workspace of sl_ctc_align_long / sl_asg_align_long (workspace_query), grown only."""
+class _AlignBuffers:
+    """Tensors of one forced aligner or of Engine.asg_viterbi_long (engine_decode.py), apart from those of the loss (a
+    forward-only engine aligns without gradient buffers, the labels of the loss stay as they are): labels, label lengths,
+    input lengths, the flat path / (B,) score results and the workspace whose size the library's workspace_query(batch,
+    frames, l_max) states.  One instance serves one entry point (an engine has one criterion): _Buffers.align the aligners of
+    a buffer set (frames = tt_pad, so every length of the set), Engine._long_align those of a logq tensor handed to them,
+    Engine._long_viterbi the decode of one (its query takes the class count for l_max).  Grown only."""
 
-    def __init__(self, device, workspace_query="sl_ctc_align_long_workspace_bytes"):
+    def __init__(self, device, workspace_query):
         self.device = device
         self.workspace_query = workspace_query
         self.labels = self.label_len = self.input_len = self.score = self.path = self.ws = None
 
-    def ensure(self, batch, t_out, l_max):
+    def ensure(self, batch, frames, l_max):
+        """room for `batch` rows (tensors of exactly that many) of `frames` frames and labels of up to l_max letters"""
         dev = self.device
         if self.labels is None or self.labels.shape[0] != batch or self.labels.shape[1] < l_max:
             self.labels = torch.zeros((batch, l_max), dtype=torch.int32, device=dev)
             self.label_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
             self.input_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
             self.score = torch.zeros((batch,), dtype=torch.float32, device=dev)
-        if self.path is None or self.path.numel() < batch * t_out:
-            self.path = torch.zeros((batch * t_out,), dtype=torch.int32, device=dev)
-        need = lib().raw(self.workspace_query)(batch, t_out, self.labels.shape[1])
+        if self.path is None or self.path.numel() < batch * frames:
+            self.path = torch.zeros((batch * frames,), dtype=torch.int32, device=dev)
+        need = lib().raw(self.workspace_query)(batch, frames, self.labels.shape[1])  # (the launch states the labels' width)
         if self.ws is None or self.ws.numel() < need:
             self.ws = None  # (free the old one first: at the limit a recording's backpointers take 4 KB (ASG: 1 KB) per frame)
             self.ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
-        return need

@@ -20,15 +20,15 @@ import torch
 from . import _lib, launch_list
 from ._lib import lib
 from .buffers import _Buffers
+from .engine_decode import DecodeAlignMixin, check_label_batch
 from .engine_front import FrontLayerMixin
 from .engine_split import SplitTopMixin
 from .engine_x3 import X3Mixin
-from .error_counts import host_counts, pack_rows
 from ._hipevents import TimingEvent
 from .plan import HALO, TIME_TILE, LayerPlan, LayerSpec, _round_up, same_padding, wav2letter_layer_specs  # noqa: F401
 
 
-class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
+class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
     """Forward / CTC / backward / Adam on one MI355X.  dtype 'bf16' (bf16 storage, fp32 accumulate, fp32 CTC: the
     benchmarked path), 'f32' (parity path: fp32 storage, exact-fp32 MFMA) or 'bf16x3' (the fast parity path: every value as
     hi + lo bf16 planes, three bf16 MFMA terms per product, fp32 accumulate; csrc/split3.hip) or 'f16x3' (the same scheme on
@@ -216,8 +216,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         self.dropout_seed = 0
         self._dropout_steps = 0
         self.cur = None
-        self._long_align = None  # buffers._LongAlignBuffers of ctc_align_long / asg_align_long, on first use
-        self._long_viterbi = None  # tensors of asg_viterbi_long, on first use
+        self._long_align = None  # buffers._AlignBuffers of ctc_align_long / asg_align_long, on first use
+        self._long_viterbi = None  # buffers._AlignBuffers of asg_viterbi_long, on first use
         self.timeline = None
         self.kernel_timeline = None  # (set of tags, list of (tag, start, stop)): see _around
         self._side_stream = None
@@ -797,28 +797,6 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         buf.input_len.copy_(torch.as_tensor(np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)),
                             non_blocking=True)
 
-    def greedy_decode(self, prediction_lengths=None):
-        """Greedy CTC decode of the current probabilities.  Returns (list of index lists, frame argmax (B,T') numpy)."""
-        buf = self.cur
-        if prediction_lengths is not None:
-            self.set_input_lengths(prediction_lengths)
-        k = self.grapheme_set_size
-        self._launch("decode", "sl_greedy_decode", buf.probs.data_ptr(), buf.input_len.data_ptr(), buf.decoded.data_ptr(),
-                      buf.decoded_len.data_ptr(), buf.frame_argmax.data_ptr(), buf.batch, buf.t_out, k, k - 1,
-                      self._stream())
-        dec = buf.decoded.cpu().numpy()
-        lens = buf.decoded_len.cpu().numpy()
-        return [list(map(int, dec[i, :lens[i]])) for i in range(buf.batch)], buf.frame_argmax.cpu().numpy()
-
-    def beam_search(self, decoder, prediction_lengths=None):
-        """CTC beam search (decoder: decoder.GpuCtcBeamSearchDecoder) over the current probabilities, in place on the
-        device: no host copy of the probabilities, no gradient buffers.  Returns (list of index lists, log-probabilities
-        (B,) numpy), as the decoder's decode()."""
-        buf = self.cur
-        if prediction_lengths is not None:
-            self.set_input_lengths(prediction_lengths)
-        return decoder.decode(buf.probs, buf.input_len)  # launched on the current stream, behind forward()
-
     # ------------------------------------------------------------------ loss + backward
 
     def _check_label_width(self, width):
@@ -832,17 +810,12 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         """label_batch: int (B,Lmax) padded with anything (reference pads -1); lengths: (B,) or (B,1)."""
         buf = self.cur
         buf.ensure_backward(self)
-        labels = np.asarray(label_batch, dtype=np.int32)
-        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
-        if labels.ndim != 2 or labels.shape[0] != buf.batch:
+        if np.ndim(label_batch) != 2 or np.shape(label_batch)[0] != buf.batch:
             raise ValueError("label batch must be (B, Lmax)")
         k = self.grapheme_set_size
-        top = k if self.criterion == "asg" else k - 1  # (ASG has no blank: every index is a label)
-        for i in range(buf.batch):
-            row = labels[i, :lab_len[i]]
-            if row.size and (row.min() < 0 or row.max() >= top):
-                raise ValueError("label {} holds an index outside [0, {}){}".format(
-                    i, top, "" if self.criterion == "asg" else " (blank is {})".format(k - 1)))
+        asg = self.criterion == "asg"  # (ASG has no blank: every index is a label)
+        labels, lab_len = check_label_batch(label_batch, label_lengths, buf.batch, k if asg else k - 1,
+                                            blank=None if asg else k - 1, check_lengths=False)
         self._check_label_width(labels.shape[1])
         l_max = max(int(labels.shape[1]), 1)
         if labels.shape[1] == 0:
@@ -868,29 +841,36 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
         buf.label_len = label_len_dev
         buf.input_len = input_len_dev
 
+    def _loss_grad_target(self, buf, grad_scale):
+        """Where the criterion's kernel writes grad_scale * dL/dlogits -> (grad, halo, cp, batch_stride, code, scale): g[last]
+        itself, or on the plane paths the fp32 staging buffer, whose rows are zeroed here (padded classes: the kernel writes
+        the k real ones), under the planes' scale; _split_loss_grad then fills the planes of g[last] from it."""
+        cp = self.plans[-1].cout_pad
+        if self.planes > 1:
+            buf.stage32[:buf.batch * buf.tt_pad * cp].zero_()
+            return buf.stage32, 0, cp, buf.tt_pad * cp, _lib.SL_F32, grad_scale * self.g_scale
+        return buf.g[-1], HALO, cp, buf.rows * cp, self.dtype_code, grad_scale
+
+    def _split_loss_grad(self, buf, tag):
+        """plane paths, behind the criterion's kernel: the staged fp32 gradient into the planes of g[last]"""
+        cp = self.plans[-1].cout_pad
+        self._launch(tag, self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[-1].data_ptr(), None, buf.batch, buf.t_out, cp,
+                     buf.tt_pad * cp, HALO, buf.rows * cp * self.planes, 0, self._stream())
+
     def ctc(self, grad_scale=None, with_grad=True):
         """Per-utterance CTC loss of the current probabilities (tensor (B,) in HBM) and, into g[last], the gradient
         w.r.t. the output_conv logits of grad_scale * sum_b loss_b (default 1/B: Keras' mean, net.py:389)."""
         buf = self.cur
         buf.ensure_backward(self)
-        last = len(self.plans) - 1
         if grad_scale is None:
             grad_scale = 1.0 / buf.batch
-        l_max = buf.labels.shape[1]
-        cp = self.plans[last].cout_pad
-        x3 = self.planes > 1
-        if x3:  # fp32 dL/dlogits into the staging buffer, then into the planes of g[last]
-            buf.stage32[:buf.batch * buf.tt_pad * cp].zero_()  # (padded classes: the CTC kernel writes the k real ones)
-            grad, halo, batch_stride, code, scale = buf.stage32, 0, buf.tt_pad * cp, _lib.SL_F32, grad_scale * self.g_scale
-        else:
-            grad, halo, batch_stride, code, scale = buf.g[last], HALO, buf.rows * cp, self.dtype_code, grad_scale
+        grad, halo, cp, batch_stride, code, scale = self._loss_grad_target(buf, grad_scale)
         self._launch("ctc", "sl_ctc_loss_grad", buf.probs.data_ptr(), buf.logq.data_ptr(), buf.labels.data_ptr(),
                      buf.label_len.data_ptr(), buf.input_len.data_ptr(), buf.loss.data_ptr(), grad.data_ptr(),
-                     buf.batch, buf.t_out, self.grapheme_set_size, l_max, halo, cp, batch_stride, code,
+                     buf.batch, buf.t_out, self.grapheme_set_size, buf.labels.shape[1], halo, cp, batch_stride, code,
                      self.ctc_epsilon, scale, buf.ctc_ws.data_ptr(), buf.ctc_ws.numel(), self._stream())
-        if x3:
-            self._launch("split:ctc", self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[last].data_ptr(), None, buf.batch, buf.t_out,
-                         cp, buf.tt_pad * cp, HALO, buf.rows * cp * self.planes, 0, self._stream())
+        if self.planes > 1:
+            self._split_loss_grad(buf, "split:ctc")
         return buf.loss
 
     # ------------------------------------------------------------------ ASG criterion (csrc/asg.hip)
@@ -976,336 +956,29 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin):
                          None, None, buf.batch, buf.t_out, k, l_max, 0, k, 0, _lib.SL_F32, self.ctc_epsilon, grad_scale, *ws)
             return buf.loss
         buf.ensure_backward(self)
-        last = len(self.plans) - 1
-        cp = self.plans[last].cout_pad
-        x3 = self.planes > 1
-        if x3:  # fp32 dL/dlogits into the staging buffer, then into the planes of g[last] (as ctc())
-            buf.stage32[:buf.batch * buf.tt_pad * cp].zero_()
-            grad, halo, batch_stride, code, scale = buf.stage32, 0, buf.tt_pad * cp, _lib.SL_F32, grad_scale * self.g_scale
-        else:
-            grad, halo, batch_stride, code, scale = buf.g[last], HALO, buf.rows * cp, self.dtype_code, grad_scale
+        grad, halo, cp, batch_stride, code, scale = self._loss_grad_target(buf, grad_scale)
         dtrans, dinit = self._asg_views(self.asg_grads)
         self._launch("asg", "sl_asg_loss_grad", buf.probs.data_ptr(), buf.logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
                      buf.labels.data_ptr(), buf.label_len.data_ptr(), buf.input_len.data_ptr(), buf.loss.data_ptr(),
                      grad.data_ptr(), dtrans.data_ptr(), dinit.data_ptr(), buf.batch, buf.t_out, k, l_max, halo, cp,
                      batch_stride, code, self.ctc_epsilon, scale, *ws)
-        if x3:
+        if self.planes > 1:
             # (the table gradients carry the planes' power-of-two scale too: taken out again, exactly)
             if self.g_scale != 1.0:
                 self._launch("scale:asg", "sl_scale", self.asg_grads.data_ptr(), self.asg_grads.numel(), _lib.SL_F32,
                              1.0 / self.g_scale, self._stream())
-            self._launch("split:asg", self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[last].data_ptr(), None, buf.batch,
-                         buf.t_out, cp, buf.tt_pad * cp, HALO, buf.rows * cp * self.planes, 0, self._stream())
+            self._split_loss_grad(buf, "split:asg")
         return buf.loss
 
     def loss(self, grad_scale=None):
         """the engine's criterion on the current probabilities and labels: ctc() or asg()"""
         return self.asg(grad_scale) if self.criterion == "asg" else self.ctc(grad_scale)
 
-    def asg_viterbi(self, prediction_lengths=None):
-        """greedy_decode() for the ASG criterion: the best letter sequence under emissions + scores (sl_asg_viterbi on the
-        current logq), repeats merged.  Returns (list of index lists, per-frame path (B, T') numpy with -1 past T_b)."""
-        self._require_asg("asg_viterbi()")
-        buf = self.cur
-        if prediction_lengths is not None:
-            self.set_input_lengths(prediction_lengths)
-        k = self.grapheme_set_size
-        buf.grow("asg_vit_ws", self.lib.raw("sl_asg_viterbi_workspace_bytes")(buf.batch, buf.tt_pad, k), 16)
-        if getattr(buf, "asg_score", None) is None:
-            buf.asg_score = torch.zeros((buf.batch,), dtype=torch.float32, device=self.device)
-        trans, init = self._asg_views(self.asg_params)
-        path = buf.frame_argmax  # int32 (B, T'): the per-frame result of the decode, as greedy_decode keeps it
-        self._launch("asg_viterbi", "sl_asg_viterbi", buf.logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
-                     buf.input_len.data_ptr(), path.data_ptr(), buf.asg_score.data_ptr(), buf.batch, buf.t_out, k,
-                     buf.asg_vit_ws.data_ptr(), buf.asg_vit_ws.numel(), self._stream())
-        paths = path.cpu().numpy()
-        decoded = []
-        for row in paths:
-            row = row[row >= 0]
-            decoded.append([int(g) for g in row[np.concatenate([[True], row[1:] != row[:-1]])]] if row.size else [])
-        return decoded, paths
-
-    def asg_beam_search(self, decoder, prediction_lengths=None):
-        """asg_viterbi() with a beam and, if the decoder has one, the n-gram language model (decoder:
-        decoder.GpuAsgBeamSearchDecoder): sl_asg_beam_search over the current logq and the engine's asg_trans / asg_init, in
-        place on the device and on the current stream.  Returns (list of grapheme index lists, scores (B,) numpy)."""
-        self._require_asg("asg_beam_search()")
-        buf = self.cur
-        if prediction_lengths is not None:
-            self.set_input_lengths(prediction_lengths)
-        trans, init = self._asg_views(self.asg_params)
-        return decoder.decode(buf.logq, trans, init, buf.input_len)
-
     def asg_adam_step(self):
         """Adam on the two ASG tables with the step's hyper-parameters and iteration count (adam_iterations already counts
         this step): one sl_adam_step launch over [g | g0].  Another rule: the same launch of its flat kernel."""
         self._launch_adam_flat("adam:asg", (self.asg_params, self.asg_grads, self.asg_adam_m, self.asg_adam_v), 0,
                                self.asg_params.numel(), self._stream(), clip=False)
-
-    def _align_labels(self, label_batch, label_lengths, batch, asg, in_len=None, max_letters=None, too_long_text=None):
-        """What the four forced aligners ask of a label batch: (B, Lmax) with B lengths (and, for a _long method, the B
-        prediction lengths in_len and at most max_letters letters, too_long_text being the error's text), every length
-        within the row, every index in [0, K - 1) under CTC, whose blank is K - 1, and in [0, K) under ASG.  Returns
-        (labels, lab_len), int32 numpy."""
-        labels = np.asarray(label_batch, dtype=np.int32)
-        lab_len = np.asarray(label_lengths, dtype=np.int32).reshape(-1)
-        if labels.ndim != 2 or labels.shape[0] != batch or lab_len.shape[0] != batch or \
-                (in_len is not None and in_len.shape[0] != batch):
-            raise ValueError("label batch must be (B, Lmax) with B lengths" if in_len is None else
-                             "label batch must be (B, Lmax) with B label lengths and B prediction lengths")
-        if max_letters is not None and labels.shape[1] > max_letters:
-            raise ValueError(too_long_text.format(labels.shape[1], max_letters))
-        end = self.grapheme_set_size if asg else self.grapheme_set_size - 1
-        for i in range(batch):
-            if not 0 <= lab_len[i] <= labels.shape[1]:
-                raise ValueError("label length {} of utterance {} outside [0, {}]".format(lab_len[i], i, labels.shape[1]))
-            row = labels[i, :lab_len[i]]
-            if row.size and (row.min() < 0 or row.max() >= end):
-                raise ValueError("label {} holds an index outside [0, {})".format(i, end) +
-                                 ("" if asg else " (blank is {})".format(end)))
-        return labels, lab_len
-
-    @staticmethod
-    def _fill_align_labels(label_tensor, length_tensor, labels, lab_len):
-        """the aligners' label tensors (at least as wide as labels): zeros, the labels, their lengths"""
-        label_tensor.zero_()
-        label_tensor[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
-        length_tensor.copy_(torch.from_numpy(lab_len))
-
-    def _long_logq(self, logq):
-        """the logq argument of the _long aligners, checked -> (contiguous logq, B, T')"""
-        k = self.grapheme_set_size
-        if logq.dim() != 3 or logq.shape[2] != k or logq.dtype != torch.float32 or not logq.is_cuda:
-            raise ValueError("logq must be a float32 (B, T', {}) tensor on the device".format(k))
-        return logq.contiguous(), int(logq.shape[0]), int(logq.shape[1])
-
-    def ctc_align(self, label_batch, label_lengths, prediction_lengths):
-        """CTC forced alignment (Viterbi) of the labels on the current buffer set's logq -- the distribution ctc() sees --
-        after forward().  label_batch: int (B, Lmax) padded with anything; lengths: (B,) or (B, 1).  Returns (paths int32
-        (B, T') numpy: the lattice state of the best path per frame, -1 past the utterance's length or for every frame of
-        an infeasible one; scores float32 (B,) numpy: its log-probability, -inf when infeasible).  Semantics:
-        sl_ctc_align (include/speechless_hip.h).  Uses tensors of its own: no gradient buffers, labels of ctc() untouched."""
-        if self.criterion == "asg":
-            raise ValueError("criterion='asg': forced alignment runs over the CTC lattice (blank = K - 1); not supported")
-        buf = self.cur
-        labels, lab_len = self._align_labels(label_batch, label_lengths, buf.batch, asg=False)
-        k = self.grapheme_set_size
-        buf.ensure_align(self, max(int(labels.shape[1]), 1))
-        self._fill_align_labels(buf.align_labels, buf.align_label_len, labels, lab_len)
-        self.set_input_lengths(prediction_lengths)
-        path = buf._align_path_flat[:buf.batch * buf.t_out]
-        self._launch("align", "sl_ctc_align", buf.logq.data_ptr(), buf.align_labels.data_ptr(), buf.align_label_len.data_ptr(),
-                     buf.input_len.data_ptr(), path.data_ptr(), buf.align_score.data_ptr(), buf.batch, buf.t_out, k,
-                     buf.align_labels.shape[1], buf.align_ws.data_ptr(), buf.align_ws.numel(), self._stream())
-        return path.view(buf.batch, buf.t_out).cpu().numpy(), buf.align_score.cpu().numpy()
-
-    # ------------------------------------------------------------------ long recordings (longform.py)
-
-    def forward_long(self, input_2d, window_input_frames=None, batch_windows=8):
-        """forward() over a recording of any length: the windows of longform.window_plan run through forward() in batches of
-        up to batch_windows, and the output frames of each that equal a single pass over the whole recording are copied on
-        the device into tensors of this call's own.  input_2d: (T, F) numpy or float32 tensor.  Returns (probs, logq), fp32
-        (1, ceil(T / ratio), K) in HBM; nothing but the input crosses PCIe.  window_input_frames: None = DEFAULT_WINDOW."""
-        from . import longform
-        if self.front_plan is not None:
-            raise ValueError("forward_long: raw-wave input is not supported (the window geometry of the sample-rate front "
-                             "layer is out of scope)")
-        if isinstance(input_2d, np.ndarray):
-            src = torch.from_numpy(np.ascontiguousarray(input_2d, dtype=np.float32)).to(self.device, non_blocking=True)
-        else:
-            src = input_2d.to(device=self.device, dtype=torch.float32).contiguous()
-        if src.dim() != 2 or src.shape[0] < 1:
-            raise ValueError("forward_long takes one recording: (frames, bins) with at least one frame")
-        window = longform.DEFAULT_WINDOW if window_input_frames is None else int(window_input_frames)
-        plan = longform.window_plan(int(src.shape[0]), self.plans, window)
-        k = self.grapheme_set_size
-        frames_out = plan[-1].out_end
-        probs = torch.empty((1, frames_out, k), dtype=torch.float32, device=self.device)
-        logq = torch.empty((1, frames_out, k), dtype=torch.float32, device=self.device)
-        step = max(int(batch_windows), 1)
-        for i in range(0, len(plan), step):
-            part = plan[i:i + step]
-            batch = torch.stack([src[w.input_start:w.input_start + w.input_length] for w in part])
-            self.forward(batch)
-            buf = self.cur
-            for row, w in enumerate(part):
-                probs[0, w.out_start:w.out_end].copy_(buf.probs[row, w.keep_start:w.keep_end])
-                logq[0, w.out_start:w.out_end].copy_(buf.logq[row, w.keep_start:w.keep_end])
-        return probs, logq
-
-    def greedy_decode_long(self, probs):
-        """Greedy CTC decode (sl_greedy_decode) of a (B, T', K) fp32 probability tensor in HBM, e.g. forward_long's, over all
-        of its frames.  Returns a list of index lists.  The kernel keeps a recording's frame argmax in LDS: beyond
-        longform.GREEDY_DECODE_MAX_FRAMES output frames it raises longform.RecordingTooLongError."""
-        from . import longform
-        b, t_out, k = probs.shape
-        if t_out > longform.GREEDY_DECODE_MAX_FRAMES:
-            raise longform.RecordingTooLongError(
-                "greedy decoding takes at most {} output frames per recording (sl_greedy_decode keeps them in LDS), not {}".format(
-                    longform.GREEDY_DECODE_MAX_FRAMES, t_out))
-        if t_out == 0:
-            return [[] for _ in range(b)]
-        dev = self.device
-        lens = torch.full((b,), t_out, dtype=torch.int32, device=dev)
-        out = torch.zeros((b, t_out), dtype=torch.int32, device=dev)
-        out_len = torch.zeros((b,), dtype=torch.int32, device=dev)
-        probs = probs.contiguous()
-        self._launch("decode_long", "sl_greedy_decode", probs.data_ptr(), lens.data_ptr(), out.data_ptr(), out_len.data_ptr(),
-                     None, b, t_out, k, k - 1, self._stream())
-        dec, n = out.cpu().numpy(), out_len.cpu().numpy()
-        return [list(map(int, dec[i, :n[i]])) for i in range(b)]
-
-    def ctc_align_long(self, logq, label_batch, label_lengths, prediction_lengths):
-        """ctc_align() beyond 511 letters, on a given (B, T', K) fp32 logq tensor in HBM (forward_long's): one
-        sl_ctc_align_long launch (include/speechless_hip.h; labels of up to longform.ALIGN_MAX_LABEL letters).  Does not touch
-        the current buffer set.  label_batch: int (B, Lmax) padded with anything; lengths: (B,) or (B, 1).  Returns (paths
-        int32 (B, T') numpy, scores float32 (B,) numpy) as ctc_align does."""
-        from . import longform
-        from .buffers import _LongAlignBuffers
-        if self.criterion == "asg":
-            raise ValueError("criterion='asg': forced alignment runs over the CTC lattice (blank = K - 1); not supported")
-        k = self.grapheme_set_size
-        logq, batch, t_out = self._long_logq(logq)
-        in_len = np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)
-        labels, lab_len = self._align_labels(
-            label_batch, label_lengths, batch, asg=False, in_len=in_len, max_letters=longform.ALIGN_MAX_LABEL,
-            too_long_text="labels of {} letters: forced alignment takes at most {} (sl_ctc_align_long)")
-        if self._long_align is None:
-            self._long_align = _LongAlignBuffers(self.device)
-        la = self._long_align
-        need = la.ensure(batch, t_out, max(int(labels.shape[1]), 1))
-        self._fill_align_labels(la.labels, la.label_len, labels, lab_len)
-        la.input_len.copy_(torch.from_numpy(in_len))
-        path = la.path[:batch * t_out]
-        self._launch("align_long", "sl_ctc_align_long", logq.data_ptr(), la.labels.data_ptr(), la.label_len.data_ptr(),
-                     la.input_len.data_ptr(), path.data_ptr(), la.score.data_ptr(), batch, t_out, k, la.labels.shape[1],
-                     la.ws.data_ptr(), need, self._stream())
-        return path.view(batch, t_out).cpu().numpy(), la.score.cpu().numpy()
-
-    def asg_align_long(self, logq, label_batch, label_lengths, prediction_lengths):
-        """asg_align() beyond 511 graphemes, on a given (B, T', K) fp32 logq tensor in HBM (forward_long's) and the engine's
-        asg_trans / asg_init: one sl_asg_align_long launch (include/speechless_hip.h; encoded labels of up to
-        longform.ASG_ALIGN_MAX_LABEL graphemes).  Does not touch the current buffer set.  label_batch: int (B, Lmax) padded
-        with anything; lengths: (B,) or (B, 1).  Returns (paths int32 (B, T') numpy, scores float32 (B,) numpy) as asg_align
-        does."""
-        from . import longform
-        from .buffers import _LongAlignBuffers
-        self._require_asg("asg_align_long()")
-        k = self.grapheme_set_size
-        logq, batch, t_out = self._long_logq(logq)
-        in_len = np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)
-        labels, lab_len = self._align_labels(
-            label_batch, label_lengths, batch, asg=True, in_len=in_len, max_letters=longform.ASG_ALIGN_MAX_LABEL,
-            too_long_text="labels of {} graphemes: ASG forced alignment takes at most {} (sl_asg_align_long)")
-        if self._long_align is None:
-            self._long_align = _LongAlignBuffers(self.device, "sl_asg_align_long_workspace_bytes")
-        la = self._long_align
-        need = la.ensure(batch, t_out, max(int(labels.shape[1]), 1))
-        self._fill_align_labels(la.labels, la.label_len, labels, lab_len)
-        la.input_len.copy_(torch.from_numpy(in_len))
-        path = la.path[:batch * t_out]
-        trans, init = self._asg_views(self.asg_params)
-        self._launch("asg_align_long", "sl_asg_align_long", logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
-                     la.labels.data_ptr(), la.label_len.data_ptr(), la.input_len.data_ptr(), path.data_ptr(),
-                     la.score.data_ptr(), batch, t_out, k, la.labels.shape[1], la.ws.data_ptr(), need, self._stream())
-        return path.view(batch, t_out).cpu().numpy(), la.score.cpu().numpy()
-
-    def asg_viterbi_long(self, logq):
-        """asg_viterbi() on a given (B, T', K) fp32 logq tensor in HBM (forward_long's), over all of its frames: one
-        sl_asg_viterbi launch whose workspace is sized for that T' (its backpointers spill there, so T' has no limit but
-        memory).  Does not touch the current buffer set.  Returns (list of index lists with repeats merged as asg_viterbi
-        merges them, per-frame paths (B, T') numpy)."""
-        self._require_asg("asg_viterbi_long()")
-        k = self.grapheme_set_size
-        if logq.dim() != 3 or logq.shape[2] != k or logq.dtype != torch.float32 or not logq.is_cuda:
-            raise ValueError("logq must be a float32 (B, T', {}) tensor on the device".format(k))
-        batch, t_out = int(logq.shape[0]), int(logq.shape[1])
-        if t_out == 0:
-            return [[] for _ in range(batch)], np.zeros((batch, 0), dtype=np.int32)
-        logq = logq.contiguous()
-        dev = self.device
-        need = self.lib.raw("sl_asg_viterbi_workspace_bytes")(batch, t_out, k)
-        lv = self._long_viterbi
-        if lv is None or lv["path"].numel() < batch * t_out or lv["score"].shape[0] != batch or lv["ws"].numel() < need:
-            self._long_viterbi = lv = None  # (free the old tensors first)
-            self._long_viterbi = lv = {"path": torch.zeros((batch * t_out,), dtype=torch.int32, device=dev),
-                                       "score": torch.zeros((batch,), dtype=torch.float32, device=dev),
-                                       "lens": torch.zeros((batch,), dtype=torch.int32, device=dev),
-                                       "ws": torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)}
-        lv["lens"].fill_(t_out)
-        path = lv["path"][:batch * t_out]
-        trans, init = self._asg_views(self.asg_params)
-        self._launch("asg_viterbi_long", "sl_asg_viterbi", logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
-                     lv["lens"].data_ptr(), path.data_ptr(), lv["score"].data_ptr(), batch, t_out, k, lv["ws"].data_ptr(),
-                     lv["ws"].numel(), self._stream())
-        paths = path.view(batch, t_out).cpu().numpy()
-        decoded = []
-        for row in paths:
-            row = row[row >= 0]
-            decoded.append([int(g) for g in row[np.concatenate([[True], row[1:] != row[:-1]])]] if row.size else [])
-        return decoded, paths
-
-    def asg_align(self, label_batch, label_lengths, prediction_lengths):
-        """ctc_align() for the ASG criterion: the best segmentation of the (run-length-encoded) labels over the frames under
-        the current buffer set's logq -- the emissions asg_viterbi() sees -- and the engine's asg_trans / asg_init, after
-        forward().  label_batch: int (B, Lmax) padded with anything; lengths: (B,) or (B, 1).  Returns (paths int32 (B, T')
-        numpy: the label position of the best path per frame, -1 past the utterance's length or for every frame of an
-        infeasible one; scores float32 (B,) numpy: the path's score, -inf when infeasible).  Semantics: sl_asg_align
-        (include/speechless_hip.h).  Uses tensors of its own: no gradient buffers, labels of asg() untouched."""
-        self._require_asg("asg_align()")
-        buf = self.cur
-        labels, lab_len = self._align_labels(label_batch, label_lengths, buf.batch, asg=True)
-        k = self.grapheme_set_size
-        buf.ensure_align(self, max(int(labels.shape[1]), 1), "sl_asg_align_workspace_bytes")
-        self._fill_align_labels(buf.align_labels, buf.align_label_len, labels, lab_len)
-        self.set_input_lengths(prediction_lengths)
-        path = buf._align_path_flat[:buf.batch * buf.t_out]
-        trans, init = self._asg_views(self.asg_params)
-        self._launch("asg_align", "sl_asg_align", buf.logq.data_ptr(), trans.data_ptr(), init.data_ptr(),
-                     buf.align_labels.data_ptr(), buf.align_label_len.data_ptr(), buf.input_len.data_ptr(), path.data_ptr(),
-                     buf.align_score.data_ptr(), buf.batch, buf.t_out, k, buf.align_labels.shape[1], buf.align_ws.data_ptr(),
-                     buf.align_ws.numel(), self._stream())
-        return path.view(buf.batch, buf.t_out).cpu().numpy(), buf.align_score.cpu().numpy()
-
-    def error_counts(self, space_index):
-        """Letter and word error counts of the greedy transcriptions against the labels, after forward() + set_labels() +
-        greedy_decode(): one sl_edit_distance launch on buf.labels / label_len and buf.decoded / decoded_len where they lie.
-        space_index: the word separator's index, < 0 for an alphabet without one.  Returns (letter_errors, word_errors),
-        int32 (B,) numpy -- net.edit_distance of the decoded strings and of their .split()."""
-        buf = self.cur
-        return self._edit_distance(buf, buf.labels, buf.label_len, buf.decoded, buf.decoded_len, space_index)
-
-    def edit_distance_batch(self, expected_rows, predicted_rows, space_index):
-        """error_counts for index lists that live on the host, as the beam decoders return them: pads both sides, uploads
-        them in one copy and makes the same launch.  Returns the same tuple.  Any number of rows; the staging and result
-        tensors belong to the current buffer set, so a forward pass (or load_input) comes first."""
-        if len(expected_rows) != len(predicted_rows) or len(expected_rows) == 0:
-            raise ValueError("need as many expected as predicted rows, and at least one")
-        buf = self.cur
-        a, a_len = pack_rows(expected_rows)
-        b, b_len = pack_rows(predicted_rows)
-        n = len(a_len)
-        staged = buf.ensure_edit_rows(self, a.size + b.size + 2 * n)
-        staged.copy_(torch.from_numpy(np.concatenate([a.ravel(), b.ravel(), a_len, b_len])))
-        a_dev, b_dev, a_len_dev, b_len_dev = staged.split([a.size, b.size, n, n])
-        return self._edit_distance(buf, a_dev.view(a.shape), a_len_dev, b_dev.view(b.shape), b_len_dev, space_index)
-
-    def _edit_distance(self, buf, a, a_len, b, b_len, space_index):
-        n, a_max, b_max = int(a.shape[0]), int(a.shape[1]), int(b.shape[1])
-        if not self.lib.raw("sl_edit_distance_supported")(a_max, b_max):
-            # rows beyond what the kernel keeps in LDS (include/speechless_hip.h): the host function counts this batch
-            a, a_len, b, b_len = (t.cpu().numpy() for t in (a, a_len, b, b_len))
-            return host_counts([a[i, :a_len[i]].tolist() for i in range(n)], [b[i, :b_len[i]].tolist() for i in range(n)],
-                               space_index)
-        out = buf.ensure_error_counts(self, n)
-        self._launch("edit_distance", "sl_edit_distance", a.data_ptr(), a_len.data_ptr(), a.stride(0), b.data_ptr(),
-                     b_len.data_ptr(), b.stride(0), n, a_max, b_max, int(space_index), out[0].data_ptr(), out[1].data_ptr(),
-                     out[2].data_ptr(), self._stream())
-        counts = out.cpu().numpy()
-        if (counts[:2] < 0).any():
-            raise ValueError("utterance {}: a length outside its row (expected rows hold {}, predicted rows {})".format(
-                int(np.argmax((counts[:2] < 0).any(axis=0))), a_max, b_max))
-        return counts[0].copy(), counts[1].copy()
 
     def backward(self, on_bucket_ready=None):
         """wgrad / bias-grad / dgrad for every trainable layer, output layer first.

@@ -753,31 +753,67 @@ class Wav2Letter:
             [ExpectationVsPrediction(predicted=p, expected=x.label, loss=float(l), letter_error_count=le, word_error_count=we)
              for p, x, l, le, we in zip(predictions, labeled_spectrogram_batch, losses, letter_errors, word_errors)])
 
+    # ------------------------------------------------------------------ forced alignment (extension; alignment.py)
+    # kind "ctc": the CTC lattice over the label's letters; kind "asg": the segmentation of the encoded label, under the asg_
+    # names.  One path per granularity; a method refuses the net of the other criterion.
+    def _require_alignment_kind(self, kind, method, positional):
+        if kind == "ctc" and self.criterion == "asg":
+            raise ValueError("criterion='asg': forced alignment ({}, {}) runs over the CTC lattice; not supported".format(
+                method, positional))
+        if kind == "asg" and self.criterion != "asg":
+            raise ValueError("asg_{0} / asg_{1} need a net built with criterion='asg' (a CTC net aligns with {0} / {1})".format(
+                method, positional))
+
+    def _alignment_from_path(self, kind, label, encoded, score, path):
+        from .alignment import AsgAlignment, CtcAlignment
+        if kind == "ctc":
+            return CtcAlignment.from_path(label, score, path)
+        enc = self.grapheme_encoding
+        return AsgAlignment.from_path(label, encoded, enc.asg_twice, enc.asg_thrice, score, path)
+
+    def _alignment_batch(self, kind, batch):
+        self._require_alignment_kind(kind, "alignment_batch", "positional_label_batch")
+        inputs = self._input_dictionary_for_loss_net(batch)
+        names = Wav2Letter.InputNames
+        engine = self.eval_engine
+        engine.forward(inputs[names.input_batch])
+        label_lengths = inputs[names.label_lengths].reshape(-1)
+        paths, scores = (engine.asg_align if kind == "asg" else engine.ctc_align)(
+            inputs[names.label_batch], label_lengths, inputs[names.prediction_lengths])
+        return [self._alignment_from_path(kind, x.label, row[:n], score, path)
+                for x, row, n, score, path in zip(batch, inputs[names.label_batch], label_lengths, scores, paths)]
+
+    def _positional_labels(self, alignments, examples, seconds_per_input_step):
+        """the word timings of alignments that exist already: whatever cannot be aligned has been refused by now"""
+        seconds = [self._seconds_per_input_step(x, seconds_per_input_step) for x in examples]
+        ratio = self.input_to_prediction_length_ratio
+        return [a.positional_label(ratio * s) for a, s in zip(alignments, seconds)]
+
     def alignment_batch(self, labeled_spectrogram_batch):
         """Extension (no reference counterpart): CTC forced alignment of every example's label, one forward pass on the
         evaluation engine and one sl_ctc_align launch over the distribution the CTC loss sees.  Inputs and lengths are
         packed as test_and_predict_batch packs them.  Returns a list of alignment.CtcAlignment (frames = output frames)."""
-        from .alignment import CtcAlignment
-        if self.criterion == "asg":
-            raise ValueError("criterion='asg': forced alignment (alignment_batch, positional_label_batch) runs over the CTC "
-                             "lattice; not supported")
-        inputs = self._input_dictionary_for_loss_net(labeled_spectrogram_batch)
-        names = Wav2Letter.InputNames
-        engine = self.eval_engine
-        engine.forward(inputs[names.input_batch])
-        paths, scores = engine.ctc_align(inputs[names.label_batch], inputs[names.label_lengths],
-                                         inputs[names.prediction_lengths])
-        return [CtcAlignment.from_path(x.label, score, path)
-                for x, score, path in zip(labeled_spectrogram_batch, scores, paths)]
+        return self._alignment_batch("ctc", labeled_spectrogram_batch)
 
     def positional_label_batch(self, labeled_spectrogram_batch, seconds_per_input_step=None):
         """Word timings in seconds (alignment.PositionalLabel, as labeled_example.py:32-60 holds them) of every example,
         None where the label cannot be aligned or has no words.  Output frame t covers input steps [r t, r (t + 1)), r =
         input_to_prediction_length_ratio.  One input step lasts seconds_per_input_step if given, else hop_length /
         sample_rate of the example (speechless_amd.spectrogram.LabeledExample) -- 1 / sample_rate on a raw-wave net."""
-        seconds = [self._seconds_per_input_step(x, seconds_per_input_step) for x in labeled_spectrogram_batch]
-        ratio = self.input_to_prediction_length_ratio
-        return [a.positional_label(ratio * s) for a, s in zip(self.alignment_batch(labeled_spectrogram_batch), seconds)]
+        return self._positional_labels(self._alignment_batch("ctc", labeled_spectrogram_batch), labeled_spectrogram_batch,
+                                       seconds_per_input_step)
+
+    def asg_alignment_batch(self, labeled_spectrogram_batch):
+        """alignment_batch for criterion='asg': the best segmentation of every example's encoded label over the frames, one
+        forward pass on the evaluation engine and one sl_asg_align launch over the emissions and scores the ASG loss and
+        decode see.  Returns a list of alignment.AsgAlignment (frames = output frames)."""
+        return self._alignment_batch("asg", labeled_spectrogram_batch)
+
+    def asg_positional_label_batch(self, labeled_spectrogram_batch, seconds_per_input_step=None):
+        """positional_label_batch for criterion='asg': the word timings in seconds of every example from
+        asg_alignment_batch, None where the label cannot be aligned or has no words."""
+        return self._positional_labels(self._alignment_batch("asg", labeled_spectrogram_batch), labeled_spectrogram_batch,
+                                       seconds_per_input_step)
 
     # ------------------------------------------------------------------ long recordings (extension; longform.py)
     def _recording_spectrogram(self, spectrogram_or_example, what):
@@ -797,40 +833,44 @@ class Wav2Letter:
         spectrogram = self._recording_spectrogram(spectrogram_or_example, "predict_recording")
         engine = self.eval_engine
         frames = spectrogram.shape[0] // self.input_to_prediction_length_ratio
+        probs, logq = engine.forward_long(spectrogram, window_input_frames)
         if self.criterion == "asg":
-            _, logq = engine.forward_long(spectrogram, window_input_frames)
             decoded = engine.asg_viterbi_long(logq[:, :frames])[0][0]
-            return self.grapheme_encoding.decode_graphemes(decoded, merge_repeated=False)
-        probs, _ = engine.forward_long(spectrogram, window_input_frames)
-        decoded = engine.greedy_decode_long(probs[:, :spectrogram.shape[0] // self.input_to_prediction_length_ratio])[0]
+        else:
+            decoded = engine.greedy_decode_long(probs[:, :frames])[0]
         return self.grapheme_encoding.decode_graphemes(decoded, merge_repeated=False)
+
+    def _align_recording(self, kind, example, window_input_frames):
+        from . import longform
+        self._require_alignment_kind(kind, "align_recording", "positional_label_of_recording")
+        asg = kind == "asg"
+        method, entry = ("asg_align_recording", "sl_asg_align_long") if asg else ("align_recording", "sl_ctc_align_long")
+        spectrogram = self._recording_spectrogram(example, method)
+        enc = self.grapheme_encoding
+        encoded = enc.encode(example.label) if asg else None  # (CTC: one index per letter, encoded behind the forward pass)
+        letters = len(encoded) if asg else len(example.label)
+        limit = longform.ASG_ALIGN_MAX_LABEL if asg else longform.ALIGN_MAX_LABEL
+        if letters > limit:
+            raise ValueError("a label of {} {}: {} takes at most {} ({})".format(
+                letters, "encoded graphemes" if asg else "letters", method, limit, entry))
+        engine = self.eval_engine
+        _, logq = engine.forward_long(spectrogram, window_input_frames)
+        labels = np.asarray(encoded, dtype=np.int32).reshape(1, -1) if asg else enc.encode_label_batch([example.label])
+        paths, scores = (engine.asg_align_long if asg else engine.ctc_align_long)(
+            logq, labels, [letters], [spectrogram.shape[0] // self.input_to_prediction_length_ratio])
+        return self._alignment_from_path(kind, example.label, encoded, scores[0], paths[0])
 
     def align_recording(self, example, window_input_frames=None):
         """alignment_batch for ONE recording of any length and a label of up to longform.ALIGN_MAX_LABEL letters:
         Engine.forward_long over windows, then one sl_ctc_align_long launch over the stitched logq.  Returns an
         alignment.CtcAlignment (frames = output frames); alignment.cut_sections cuts it into utterances."""
-        from . import longform
-        from .alignment import CtcAlignment
-        if self.criterion == "asg":
-            raise ValueError("criterion='asg': forced alignment (align_recording, positional_label_of_recording) runs over the "
-                             "CTC lattice; not supported")
-        spectrogram = self._recording_spectrogram(example, "align_recording")
-        if len(example.label) > longform.ALIGN_MAX_LABEL:
-            raise ValueError("a label of {} letters: align_recording takes at most {} (sl_ctc_align_long)".format(
-                len(example.label), longform.ALIGN_MAX_LABEL))
-        engine = self.eval_engine
-        _, logq = engine.forward_long(spectrogram, window_input_frames)
-        labels = self.grapheme_encoding.encode_label_batch([example.label])
-        paths, scores = engine.ctc_align_long(logq, labels, [len(example.label)],
-                                              [spectrogram.shape[0] // self.input_to_prediction_length_ratio])
-        return CtcAlignment.from_path(example.label, scores[0], paths[0])
+        return self._align_recording("ctc", example, window_input_frames)
 
     def positional_label_of_recording(self, example, seconds_per_input_step=None, window_input_frames=None):
         """positional_label_batch for ONE recording of any length (align_recording): its word timings in seconds, None where
         the label cannot be aligned or has no words."""
-        alignment = self.align_recording(example, window_input_frames)  # (first: it refuses what it cannot align)
-        seconds = self._seconds_per_input_step(example, seconds_per_input_step)
-        return alignment.positional_label(self.input_to_prediction_length_ratio * seconds)
+        return self._positional_labels([self._align_recording("ctc", example, window_input_frames)], [example],
+                                       seconds_per_input_step)[0]
 
     def asg_align_recording(self, example, window_input_frames=None):
         """asg_alignment_batch for ONE recording of any length and a label of up to longform.ASG_ALIGN_MAX_LABEL ENCODED
@@ -838,57 +878,13 @@ class Wav2Letter:
         launch over the stitched logq and the engine's scores.  Returns an alignment.AsgAlignment (frames = output frames);
         alignment.cut_sections cuts it into utterances.  (Named like asg_alignment_batch: align_recording keeps refusing
         an ASG net.)"""
-        from . import longform
-        from .alignment import AsgAlignment
-        if self.criterion != "asg":
-            raise ValueError("asg_align_recording / asg_positional_label_of_recording need a net built with criterion='asg' "
-                             "(a CTC net aligns with align_recording / positional_label_of_recording)")
-        spectrogram = self._recording_spectrogram(example, "asg_align_recording")
-        enc = self.grapheme_encoding
-        encoded = enc.encode(example.label)
-        if len(encoded) > longform.ASG_ALIGN_MAX_LABEL:
-            raise ValueError("a label of {} encoded graphemes: asg_align_recording takes at most {} (sl_asg_align_long)".format(
-                len(encoded), longform.ASG_ALIGN_MAX_LABEL))
-        engine = self.eval_engine
-        _, logq = engine.forward_long(spectrogram, window_input_frames)
-        labels = np.asarray(encoded, dtype=np.int32).reshape(1, -1)
-        paths, scores = engine.asg_align_long(logq, labels, [len(encoded)],
-                                              [spectrogram.shape[0] // self.input_to_prediction_length_ratio])
-        return AsgAlignment.from_path(example.label, encoded, enc.asg_twice, enc.asg_thrice, scores[0], paths[0])
+        return self._align_recording("asg", example, window_input_frames)
 
     def asg_positional_label_of_recording(self, example, seconds_per_input_step=None, window_input_frames=None):
         """asg_positional_label_batch for ONE recording of any length (asg_align_recording): its word timings in seconds,
         None where the label cannot be aligned or has no words."""
-        alignment = self.asg_align_recording(example, window_input_frames)  # (first: it refuses what it cannot align)
-        seconds = self._seconds_per_input_step(example, seconds_per_input_step)
-        return alignment.positional_label(self.input_to_prediction_length_ratio * seconds)
-
-    def asg_alignment_batch(self, labeled_spectrogram_batch):
-        """alignment_batch for criterion='asg': the best segmentation of every example's encoded label over the frames, one
-        forward pass on the evaluation engine and one sl_asg_align launch over the emissions and scores the ASG loss and
-        decode see.  Returns a list of alignment.AsgAlignment (frames = output frames)."""
-        from .alignment import AsgAlignment
-        if self.criterion != "asg":
-            raise ValueError("asg_alignment_batch / asg_positional_label_batch need a net built with criterion='asg' "
-                             "(a CTC net aligns with alignment_batch / positional_label_batch)")
-        inputs = self._input_dictionary_for_loss_net(labeled_spectrogram_batch)
-        names = Wav2Letter.InputNames
-        engine = self.eval_engine
-        engine.forward(inputs[names.input_batch])
-        label_lengths = inputs[names.label_lengths].reshape(-1)
-        paths, scores = engine.asg_align(inputs[names.label_batch], label_lengths, inputs[names.prediction_lengths])
-        enc = self.grapheme_encoding
-        return [AsgAlignment.from_path(x.label, row[:n], enc.asg_twice, enc.asg_thrice, score, path)
-                for x, row, n, score, path in zip(labeled_spectrogram_batch, inputs[names.label_batch], label_lengths, scores,
-                                                  paths)]
-
-    def asg_positional_label_batch(self, labeled_spectrogram_batch, seconds_per_input_step=None):
-        """positional_label_batch for criterion='asg': the word timings in seconds of every example from
-        asg_alignment_batch, None where the label cannot be aligned or has no words."""
-        alignments = self.asg_alignment_batch(labeled_spectrogram_batch)  # (first: a CTC net is refused before anything else)
-        seconds = [self._seconds_per_input_step(x, seconds_per_input_step) for x in labeled_spectrogram_batch]
-        ratio = self.input_to_prediction_length_ratio
-        return [a.positional_label(ratio * s) for a, s in zip(alignments, seconds)]
+        return self._positional_labels([self._align_recording("asg", example, window_input_frames)], [example],
+                                       seconds_per_input_step)[0]
 
     def _seconds_per_input_step(self, example, seconds_per_input_step):
         if seconds_per_input_step is not None:
