@@ -383,6 +383,35 @@ int sl_ctc_align_long(const float* logq, const int32_t* labels, const int32_t* l
                       int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- CTC segment posteriors: the probability that a stretch of frames, read on its own, says exactly a stretch of a label
+ *      (the forward SUM over the CTC lattice where the aligners above take the max).  With the word ranges of a forced
+ *      alignment: a confidence per word; over all frames and the whole label: minus the CTC loss.  No reference counterpart. ---
+ * logq: float[B][t_out][k], as the aligners take it; labels: int32[B][l_max]; input_len: T_b; blank = k-1.
+ * segments: int32[n_segments][5] = {b, frame_begin, frame_end, label_begin, label_end}, half-open ranges into utterance b.
+ * Limits: 1 < k <= 64, 0 <= seg_l_max <= 511, n_segments >= 1: SL_ERR_UNSUPPORTED otherwise.  A null pointer (labels may be
+ * null when l_max = 0) or batch, t_out <= 0 or l_max < 0 is SL_ERR_INVALID_ARGUMENT, a workspace below the size asked for
+ * SL_ERR_WORKSPACE_TOO_SMALL; all of these are refused on the host before any launch.
+ * Per segment: frame_begin and frame_end are each clamped into [0, min(max(T_b, 0), t_out)], T = frame_end - frame_begin (0 if
+ * that is negative); label_begin and label_end are each clamped into [0, l_max], L = min(label_end - label_begin, seg_l_max)
+ * (0 if negative); the segment's letters are l_i = labels[b][label_begin + i], i < L, its frames logq_t = logq[b][frame_begin
+ * + t], t < T.  A letter's column is clamped into [0, k) as the aligners clamp it.
+ *   states s in [0, S), S = 2L+1: even s blank, odd s letter (s-1)/2.
+ *   a_0(0) = logq_0(blank), a_0(1) = logq_0(l_0), every other state -inf;
+ *   a_t(s) = logsumexp(a_{t-1}(s), a_{t-1}(s-1), a_{t-1}(s-2)) + logq_t(label(s)) for 0 < t < T, where the s-2 term counts only
+ *   for an odd s >= 3 whose letter differs from l_{(s-1)/2 - 1} (sl_ctc_align's rule).
+ *   log_posterior[i] = logsumexp(a_{T-1}(2L), a_{T-1}(2L-1)), float32, natural logarithm.
+ * L = 0: the sum of logq_t(blank) over the frames; L = 0 and T = 0: 0.  T < L + (number of adjacent equal letters of the
+ * segment): -inf.  b outside [0, batch): -inf, and nothing else of the segment is read.  Only log_posterior[0 .. n_segments) is
+ * written.  Not bit-exact: the lattice is held in doubles in log2 units and each step's log2 of a sum in [1, 3] is taken in
+ * fp32; against a float64 evaluation of the above the result is within 1e-6 * (T + |log_posterior|).
+ * workspace: sl_ctc_segment_scores_workspace_bytes(n_segments, seg_l_max) bytes -- 0 today: a segment's lattice lives in the
+ * registers of its wave (workspace may then be null).  One wave per segment; 2 / 4 / 8 / 16 states per lane for seg_l_max <=
+ * 63 / 127 / 255 / 511. */
+size_t sl_ctc_segment_scores_workspace_bytes(int n_segments, int seg_l_max);
+int sl_ctc_segment_scores(const float* logq, const int32_t* labels, const int32_t* input_len, const int32_t* segments,
+                          float* log_posterior, int batch, int t_out, int k, int l_max, int n_segments, int seg_l_max,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- ASG criterion (auto segmentation criterion of the wav2letter paper, arXiv:1609.03193).  No reference counterpart:
  *      the reference raises NotImplementedError where its ASG loss would be (speechless/net.py:397-399). ----------------------
  * K = k letters and NO blank.  trans: float[k][k], trans[i*k + j] = g(i, j) = the score of moving from letter i to letter

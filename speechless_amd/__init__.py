@@ -11,7 +11,8 @@ def __getattr__(name):
                 "ExpectationsVsPredictionsInBatches", "ExpectationsVsPredictionsInGroupedBatches"):
         from . import net
         return getattr(net, name)
-    if name in ("PositionalLabel", "CtcAlignment", "AsgAlignment", "cut_sections"):
+    if name in ("PositionalLabel", "CtcAlignment", "AsgAlignment", "cut_sections", "cut_section_spans", "word_spans",
+                "WordConfidence", "ScoredAlignment"):
         from . import alignment
         return getattr(alignment, name)
     if name == "window_plan":

@@ -143,6 +143,10 @@ SIGNATURES = {
     "sl_ctc_align_long_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sl_ctc_align_long": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                   c_void_p, c_size_t, c_void_p]),
+    "sl_ctc_segment_scores_workspace_bytes": (c_size_t, [c_int, c_int]),
+    # logq, labels, input_len, segments, log_posterior, batch, t_out, k, l_max, n_segments, seg_l_max, workspace, bytes, stream
+    "sl_ctc_segment_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_void_p, c_size_t, c_void_p]),
     "sl_asg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     # probs, logq, trans, init, labels, label_len, input_len, loss, dlogits, dtrans, dinit; then sl_ctc_loss_grad's tail
     "sl_asg_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -4,7 +4,9 @@ asg_alignment_batch / asg_positional_label_batch / asg_align_recording under ASG
 `PositionalLabel` is the reference's word-timing label (speechless/labeled_example.py:32-60): `(word, (start, end))`
 sections, which LabeledExampleFromFile.sections() (:219-234) uses to cut long recordings.  `CtcAlignment` is one
 utterance's Viterbi alignment (include/speechless_hip.h, sl_ctc_align) turned into character and word frame ranges;
-`AsgAlignment` is the same for the ASG criterion (sl_asg_align / sl_asg_align_long), whose path runs over the run-length-encoded label."""
+`AsgAlignment` is the same for the ASG criterion (sl_asg_align / sl_asg_align_long), whose path runs over the run-length-encoded label.
+`ScoredAlignment` adds the confidences of sl_ctc_segment_scores to a `CtcAlignment` (Wav2Letter.word_confidence_batch /
+predict_with_confidence_batch / confidence_of_recording): a `WordConfidence` per word and the posterior of the whole label."""
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -43,9 +45,9 @@ class PositionalLabel:
         return PositionalLabel(sections)
 
 
-def _word_frames(label: str, character_frames) -> List[Tuple[str, Tuple[int, int]]]:
-    """(word, (first, end)) per space-separated word of `label`: from its first character's first frame to its last one's end"""
-    words = []
+def word_spans(label: str) -> List[Tuple[int, int]]:
+    """(char_begin, char_end), half-open, of each space-separated word of `label` (any run of spaces separates)"""
+    spans = []
     i = 0
     while i < len(label):
         if label[i] == " ":
@@ -54,9 +56,14 @@ def _word_frames(label: str, character_frames) -> List[Tuple[str, Tuple[int, int
         j = i
         while j < len(label) and label[j] != " ":
             j += 1
-        words.append((label[i:j], (character_frames[i][0], character_frames[j - 1][1])))
+        spans.append((i, j))
         i = j
-    return words
+    return spans
+
+
+def _word_frames(label: str, character_frames) -> List[Tuple[str, Tuple[int, int]]]:
+    """(word, (first, end)) per space-separated word of `label`: from its first character's first frame to its last one's end"""
+    return [(label[i:j], (character_frames[i][0], character_frames[j - 1][1])) for i, j in word_spans(label)]
 
 
 class _WordTimings:
@@ -108,14 +115,8 @@ class CtcAlignment(_WordTimings):
         return "CtcAlignment({!r}, log_probability={}, words={})".format(self.label, self.log_probability, self.word_frames)
 
 
-def cut_sections(alignment, max_frames: int) -> List[Tuple[str, Tuple[int, int]]]:
-    """Cuts an aligned recording (Wav2Letter.align_recording, or asg_align_recording) into sections of whole words, (text, (first, end)) in output
-    frames: what LabeledExampleFromFile.sections() (labeled_example.py:219-234) needs to turn a long recording into utterances.
-    Greedy: a section takes words while its last word's end - its first word's first <= max_frames; a single word longer
-    than that is a section by itself.  The cut between two sections lies at the midpoint (integer floor) of the gap between
-    the neighbouring words; the first section starts at its first word's first frame, the last ends at its last word's end.
-    Empty for an infeasible alignment (or one without words)."""
-    words = alignment.word_frames
+def _section_groups(words, max_frames: int) -> List[Tuple[List[int], Tuple[int, int]]]:
+    """the grouping and the cut rule of cut_sections / cut_section_spans: (indices of the section's words, (first, end))"""
     groups = []  # type: List[List[int]]
     for i, (_, (first, end)) in enumerate(words):
         if groups and end - words[groups[-1][0]][1][0] <= max_frames:
@@ -130,8 +131,70 @@ def cut_sections(alignment, max_frames: int) -> List[Tuple[str, Tuple[int, int]]
             start = (words[group[0] - 1][1][1] + start) // 2
         if n + 1 < len(groups):
             end = (end + words[group[-1] + 1][1][0]) // 2
-        sections.append((" ".join(words[i][0] for i in group), (start, end)))
+        sections.append((group, (start, end)))
     return sections
+
+
+def cut_sections(alignment, max_frames: int) -> List[Tuple[str, Tuple[int, int]]]:
+    """Cuts an aligned recording (Wav2Letter.align_recording, or asg_align_recording) into sections of whole words, (text, (first, end)) in output
+    frames: what LabeledExampleFromFile.sections() (labeled_example.py:219-234) needs to turn a long recording into utterances.
+    Greedy: a section takes words while its last word's end - its first word's first <= max_frames; a single word longer
+    than that is a section by itself.  The cut between two sections lies at the midpoint (integer floor) of the gap between
+    the neighbouring words; the first section starts at its first word's first frame, the last ends at its last word's end.
+    Empty for an infeasible alignment (or one without words)."""
+    words = alignment.word_frames
+    return [(" ".join(words[i][0] for i in group), frames) for group, frames in _section_groups(words, max_frames)]
+
+
+def cut_section_spans(alignment, max_frames: int) -> List[Tuple[str, Tuple[int, int], Tuple[int, int]]]:
+    """cut_sections with each section's character span in alignment.label: (text, (first, end), (char_begin, char_end)), from
+    its first word's first character to its last word's last (so label[char_begin:char_end] keeps the label's own spacing,
+    where the text joins the words with single spaces).  What Wav2Letter.confidence_of_recording scores."""
+    words = alignment.word_frames
+    spans = word_spans(alignment.label)
+    return [(" ".join(words[i][0] for i in group), frames, (spans[group[0]][0], spans[group[-1]][1]))
+            for group, frames in _section_groups(words, max_frames)]
+
+
+class WordConfidence:
+    """One word of a scored alignment: its output frames [first, end) and the log of its segment posterior -- the
+    probability that those frames, read on their own, say exactly the word (sl_ctc_segment_scores)."""
+
+    def __init__(self, word: str, first: int, end: int, log_posterior: float):
+        self.word = word
+        self.first = int(first)
+        self.end = int(end)
+        self.log_posterior = float(log_posterior)
+
+    @property
+    def confidence(self) -> float:
+        return float(np.exp(self.log_posterior))
+
+    def __repr__(self):
+        return "WordConfidence({!r}, ({}, {}), confidence={:.4f})".format(self.word, self.first, self.end, self.confidence)
+
+
+class ScoredAlignment:
+    """A CtcAlignment with confidences.  words: a WordConfidence per word of alignment.word_frames, in order (empty when the
+    alignment is infeasible or has no words).  log_posterior: the whole label over all of the utterance's frames, log p(label |
+    audio) = minus the CTC loss (-inf when infeasible)."""
+
+    def __init__(self, alignment: CtcAlignment, word_log_posteriors, log_posterior: float):
+        word_log_posteriors = [float(x) for x in word_log_posteriors]
+        if len(word_log_posteriors) != len(alignment.word_frames):
+            raise ValueError("{} word scores for the {} words of {!r}".format(len(word_log_posteriors), len(alignment.word_frames),
+                                                                            alignment.label))
+        self.alignment = alignment
+        self.words = [WordConfidence(word, first, end, score)
+                      for (word, (first, end)), score in zip(alignment.word_frames, word_log_posteriors)]
+        self.log_posterior = float(log_posterior)
+
+    @property
+    def label(self) -> str:
+        return self.alignment.label
+
+    def __repr__(self):
+        return "ScoredAlignment({!r}, log_posterior={}, words={})".format(self.label, self.log_posterior, self.words)
 
 
 def _characters_per_grapheme(label: str) -> List[Tuple[int, bool]]:

@@ -52,6 +52,7 @@ class _Buffers:
         self._argmax_flat = torch.zeros((batch * self.tt_pad,), dtype=torch.int32, device=dev)
         self.g = [None] * n  # allocated lazily by ensure_backward()
         self.align = None  # _AlignBuffers of Engine.ctc_align / asg_align (frames = tt_pad), on first use
+        self.segment = None  # _SegmentBuffers of Engine.ctc_segment_scores, on first use
         self.asg_score = self.asg_vit_ws = None  # (B,) result and workspace of Engine.asg_viterbi, on first use
         self.error_counts = self.edit_rows = None  # allocated lazily by ensure_error_counts() / ensure_edit_rows()
         self.decoded_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
@@ -415,4 +416,28 @@ class _AlignBuffers:
         need = lib().raw(self.workspace_query)(batch, frames, self.labels.shape[1])  # (the launch states the labels' width)
         if self.ws is None or self.ws.numel() < need:
             self.ws = None  # (free the old one first: at the limit a recording's backpointers take 4 KB (ASG: 1 KB) per frame)
+            self.ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+
+
+class _SegmentBuffers:
+    """Tensors of Engine.ctc_segment_scores / ctc_segment_scores_long (engine_decode.py): the labels, the input lengths of a
+    logq tensor handed to the _long method, the (N, 5) segments, their (N,) results and the workspace whose size
+    sl_ctc_segment_scores_workspace_bytes states.  _Buffers.segment serves a buffer set, Engine._long_segment a logq tensor handed
+    over.  Grown only."""
+
+    def __init__(self, device):
+        self.device = device
+        self.labels = self.input_len = self.segments = self.out = self.ws = None
+
+    def ensure(self, batch, l_max, n_segments, seg_l_max):
+        """room for `batch` label rows (tensors of exactly that many) of up to l_max letters and n_segments segments"""
+        dev = self.device
+        if self.labels is None or self.labels.shape[0] != batch or self.labels.shape[1] < l_max:
+            self.labels = torch.zeros((batch, l_max), dtype=torch.int32, device=dev)
+            self.input_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        if self.segments is None or self.segments.shape[0] < n_segments:
+            self.segments = torch.zeros((n_segments, 5), dtype=torch.int32, device=dev)
+            self.out = torch.zeros((n_segments,), dtype=torch.float32, device=dev)
+        need = lib().raw("sl_ctc_segment_scores_workspace_bytes")(n_segments, seg_l_max)
+        if self.ws is None or self.ws.numel() < need:
             self.ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)

@@ -12,7 +12,7 @@ HOST_LIB_PATH = PACKAGE_DIR / "libspeechless_host.so"  # plain C++ helpers of th
 HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csrc_host" / "beam_search.cpp"]
 CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "ctc_long.hip", "misc.hip", "optimizer.hip", "spectrogram.hip", "conv_chain_bf16.hip",
-           "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip",
+           "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip", "ctc_segment.hip",
            "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
            "resample.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
@@ -24,7 +24,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 
 
 def _newest_source_mtime():
-    files = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "lds_dma.h", CSRC / "lattice.h", CSRC / "beam_shared.h", CSRC / "ctc_shared.h", PACKAGE_DIR.parent / "include" / "speechless_hip.h"]
+    files = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "lds_dma.h", CSRC / "lattice.h", CSRC / "lse_double.h", CSRC / "beam_shared.h", CSRC / "ctc_shared.h", PACKAGE_DIR.parent / "include" / "speechless_hip.h"]
     return max(f.stat().st_mtime for f in files)
 
 
@@ -49,9 +49,11 @@ def _newest_source_mtime():
 # register arrays indexed by unrolled constants; scratch there is memory traffic inside the per-frame barrier interval of 16 waves)
 # (resample.hip: a thread's eight accumulators and sample offsets are register arrays indexed by unrolled constants; scratch there
 # puts a memory round trip beside every FMA of the tap loop)
+# (ctc_segment.hip: up to 16 lattice states in doubles, their columns and a chunk of staged emissions per lane are register
+# arrays indexed by unrolled constants; scratch there is memory traffic on the per-frame sequential path of a lone wave)
 NO_SCRATCH = {"resample.hip","conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
               "ctc_align_long.hip", "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
-              "ctc_long.hip"}
+              "ctc_long.hip", "ctc_segment.hip"}
 
 
 def _scratch_users(remarks):

@@ -16,35 +16,13 @@
 //                         order, same destination.  No tickets, no repair pass: the lattice is the accurate one already.
 #include "common.h"
 #include "ctc_shared.h"
+#include "lse_double.h"
 
 namespace {
 
-constexpr double LOG2E_D = 1.4426950408889634;
-constexpr double LN2_D = 0.6931471805599453;
-constexpr double NEG_INF = -(double)INFINITY;
+constexpr double NEG_INF = NEG_INF_D;  // (LOG2E_D, LN2_D and the lse2_long / lse3_long step: lse_double.h)
 constexpr int LONG_THREADS_MAX = 1024;
 constexpr int LONG_DUMP_DOUBLES = 64 * 4;  // per (utterance, direction): the NS <= 4 states of the <= 63 dead lanes of the last wave
-
-// log2(2^a + 2^b [+ 2^c]) of lattice values in DOUBLES.  The values carry the whole utterance (|log2| up to 1e5 over 4000
-// frames, where an fp32 ulp is 8e-3); the step's own part -- log2 of a sum in [1, 3] of powers 2^(x - max) <= 1 -- is taken
-// with the raw fp32 instructions, as ctc_lattice_kernel's lse3_2 does: it is below 1.585 and comes back to within 1.5e-7, so
-// a frame adds at most 1e-7 (in natural-log units) to a state, against the 1.2e-6 per frame that the fp32 emissions
-// themselves are allowed, and the error is common to the states of a frame to first order (alpha + beta - log Z cancels it).
-// The library's double exp2 / log2 here cost four times the frame time.  Branch-free: an all -inf input gives -inf.
-__device__ __forceinline__ double lse_tail(double m, float sum) {
-    return m + (double)__builtin_amdgcn_logf(sum);  // (sum == 0 only where m stands in for -inf: log2(0) = -inf)
-}
-__device__ __forceinline__ double lse2_long(double a, double b) {
-    const double mx = fmax(a, b);
-    const double m = mx == NEG_INF ? 0.0 : mx;
-    return lse_tail(m, __builtin_amdgcn_exp2f((float)(a - m)) + __builtin_amdgcn_exp2f((float)(b - m)));
-}
-__device__ __forceinline__ double lse3_long(double a, double b, double c) {
-    const double mx = fmax(a, fmax(b, c));
-    const double m = mx == NEG_INF ? 0.0 : mx;
-    return lse_tail(m, __builtin_amdgcn_exp2f((float)(a - m)) + __builtin_amdgcn_exp2f((float)(b - m)) +
-                           __builtin_amdgcn_exp2f((float)(c - m)));
-}
 
 // One direction (DIR 0: alpha, forwards; 1: beta, backwards) of utterance b by the whole work-group.  Thread tid owns the states
 // NS * tid .. NS * tid + NS - 1: even offsets are blanks, odd offsets the label positions NS / 2 * tid + i.

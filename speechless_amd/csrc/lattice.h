@@ -1,14 +1,16 @@
 // lattice.h -- what the lattice kernels that keep their states in registers share (ctc_align.hip, ctc_align_long.hip, asg.hip,
-// asg_align.hip, asg_align_long.hip):
+// asg_align.hip, asg_align_long.hip, ctc_segment.hip):
 //   - the clamps of lengths and labels, and the neighbour-lane move;
 //   - the windows of whole backpointer rows that a one-wave backtrace pulls from HBM into LDS (load_window / store_window),
 //     and the bands of them that a long aligner's backtrace pulls (load_band / store_band);
 //   - for the four forced aligners, each piece that include/speechless_hip.h defines bit for bit, ONCE: the CTC states of a
 //     thread and their frame step (ctc_states_init / ctc_frame), the ASG ones (asg_states_init / asg_frame), and the stager of
-//     their emissions (EmissionStager, ALIGN_CH).
+//     their emissions (EmissionStager, ALIGN_CH);
+//   - for the segment posteriors (ctc_segment.hip), the SUMMING frame step over the same states (ctc_frame_sum), in doubles.
 // No helper here holds a barrier, a fence or a return: those stay in the kernels, next to the argument for their uniformity.
 #pragma once
 #include "common.h"
+#include "lse_double.h"
 
 __device__ __forceinline__ int clamp_label(int c, int k) { return c < 0 ? 0 : (c >= k ? k - 1 : c); }
 
@@ -22,6 +24,12 @@ __device__ __forceinline__ void clamp_lengths(const int32_t* label_len, const in
 
 __device__ __forceinline__ float dpp_float_from_lower_lane(float v, float lane0_value) {  // lane l <- lane l-1
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0_value), __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ double dpp_double_from_lower_lane(double v, double lane0_value) {  // the same move, both halves
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(lane0_value), __double2loint(v), 0x138, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(lane0_value), __double2hiint(v), 0x138, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
 }
 
 constexpr int BT_W = 64;  // frames per backtrace window (one per lane)
@@ -132,6 +140,24 @@ __device__ __forceinline__ uint32_t ctc_frame(const int (&col)[NJ / 2], const bo
         word |= bp << (2 * j);
     }
     return word;
+}
+// The same frame with the SUM in place of the max, for the forward (alpha) lattice of sl_ctc_segment_scores: d[] in doubles and
+// log2 units, a(s) = log2(2^a(s) + 2^a(s-1) [+ 2^a(s-2) where the state may be entered from s-2]) + logq(label(s)) * log2(e),
+// the sum by lse2_long / lse3_long of lse_double.h (the step of ctc_long.hip) and the emission by one fma.  No backpointers.
+// A state beyond the label has the blank's column and nothing above it reads it.
+template <int NJ>
+__device__ __forceinline__ void ctc_frame_sum(const int (&col)[NJ / 2], const bool (&skip)[NJ / 2], double (&d)[NJ], const float* e,
+                                              float eb, double lo1) {
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) {  // descending: d[j-1], d[j-2] still hold frame t-1
+        const double p1 = j >= 1 ? d[j - 1] : lo1;
+        if (j & 1) {
+            const double p2 = j >= 2 ? d[j - 2] : lo1;
+            d[j] = fma((double)e[col[j >> 1]], LOG2E_D, lse3_long(d[j], p1, skip[j >> 1] ? p2 : NEG_INF_D));
+        } else {
+            d[j] = fma((double)eb, LOG2E_D, lse2_long(d[j], p1));
+        }
+    }
 }
 
 // NS consecutive states of a label under the ASG criterion (state s: letter s of the label): col[] the emission column, gs[]

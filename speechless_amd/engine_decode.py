@@ -1,13 +1,14 @@
 """What runs on the probabilities behind forward() outside the training step: greedy / Viterbi / beam decoding, the four forced
-aligners, long recordings (longform.py) and the error counts.  One host path each: the aligners differ by a row of _ALIGNERS,
-their label batches pass check_label_batch, their tensors live in buffers._AlignBuffers.  Methods of Engine."""
+aligners, the CTC segment posteriors, long recordings (longform.py) and the error counts.  One host path each: the aligners
+differ by a row of _ALIGNERS, their label batches pass check_label_batch, their tensors live in buffers._AlignBuffers (the
+segment posteriors': _SegmentBuffers).  Methods of Engine."""
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import longform
-from .buffers import _AlignBuffers
+from .buffers import _AlignBuffers, _SegmentBuffers
 from .error_counts import host_counts, pack_rows
 
 
@@ -29,6 +30,7 @@ _ALIGNERS = {  # (kind, long)
     ("asg", True): _Aligner("sl_asg_align_long", "asg_align_long", longform.ASG_ALIGN_MAX_LABEL,
                             "labels of {} graphemes: ASG forced alignment takes at most {}"),
 }
+_SEGMENTS = "sl_ctc_segment_scores"
 _VITERBI = "sl_asg_viterbi"
 _GREEDY = "sl_greedy_decode"
 
@@ -57,6 +59,23 @@ def check_label_batch(labels, lengths, batch, n_labels, *, blank=None, in_len=No
             raise ValueError("label {} holds an index outside [0, {})".format(i, n_labels) +
                              ("" if blank is None else " (blank is {})".format(blank)))
     return labels, lab_len
+
+
+def check_segments(segments, batch):
+    """What the engine asks of the segments of ctc_segment_scores, on the host: (N, 5) integers {b, frame_begin, frame_end,
+    label_begin, label_end} with N >= 1, b in [0, batch), 0 <= begin <= end for both ranges and a label span of at most
+    longform.SEGMENT_MAX_LABEL letters; the first row that breaks a rule is named.  Returns them as contiguous int32 numpy."""
+    seg = np.asarray(segments)
+    if seg.ndim != 2 or seg.shape[1] != 5 or seg.shape[0] < 1 or not np.issubdtype(seg.dtype, np.integer):
+        raise ValueError("segments must be an (N, 5) integer array of (b, frame_begin, frame_end, label_begin, label_end), N >= 1")
+    seg = seg.astype(np.int64)
+    bad = (seg[:, 0] < 0) | (seg[:, 0] >= batch) | (seg[:, 1] < 0) | (seg[:, 2] < seg[:, 1]) | (seg[:, 3] < 0) | \
+        (seg[:, 4] < seg[:, 3]) | (seg[:, 4] - seg[:, 3] > longform.SEGMENT_MAX_LABEL) | (seg[:, 1:].max(axis=1) >= 2 ** 31)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError("segment {} = {}: need b in [0, {}), 0 <= begin <= end for frames and letters, and at most {} letters "
+                         "({})".format(i, seg[i].tolist(), batch, longform.SEGMENT_MAX_LABEL, _SEGMENTS))
+    return np.ascontiguousarray(seg, dtype=np.int32)
 
 
 def _merge_repeats(paths):
@@ -216,6 +235,61 @@ class DecodeAlignMixin:
         with anything; lengths: (B,) or (B, 1).  Returns (paths int32 (B, T') numpy, scores float32 (B,) numpy) as asg_align
         does."""
         return self._align("asg", True, logq, label_batch, label_lengths, prediction_lengths)
+
+    # ------------------------------------------------------------------ segment posteriors
+
+    def _segment_scores(self, long, logq, label_batch, prediction_lengths, segments):
+        """sl_ctc_segment_scores over the current buffer set's logq with its input lengths (tensors: buf.segment), or -- long --
+        over a given logq with its prediction lengths (tensors: _long_segment).  Checks in _align's order: the criterion, logq
+        (long), the segments, the labels -- of each row the letters that some segment covers.  Returns float32 (N,) numpy."""
+        if self.criterion == "asg":
+            raise ValueError("criterion='asg': segment posteriors run over the CTC lattice (blank = K - 1); not supported")
+        k = self.grapheme_set_size
+        if long:
+            buf, in_len = None, np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)
+            logq, batch, t_out = self._long_logq(logq)
+        else:
+            buf, in_len = self.cur, None
+            logq, batch, t_out = buf.logq, buf.batch, buf.t_out
+        seg = check_segments(segments, batch)
+        labels = np.asarray(label_batch, dtype=np.int32)
+        covered = np.zeros((batch,), dtype=np.int32)
+        np.maximum.at(covered, seg[:, 0], seg[:, 4])
+        labels, _ = check_label_batch(labels, np.minimum(covered, labels.shape[1] if labels.ndim == 2 else 0), batch, k - 1,
+                                      blank=k - 1, in_len=in_len)
+        n, seg_l_max = int(seg.shape[0]), int((seg[:, 4] - seg[:, 3]).max())
+        if long:
+            sb = self._long_segment = self._long_segment or _SegmentBuffers(self.device)
+        else:
+            sb = buf.segment = buf.segment or _SegmentBuffers(self.device)
+        sb.ensure(batch, max(int(labels.shape[1]), 1), n, seg_l_max)
+        sb.labels.zero_()  # (at least as wide as the labels)
+        sb.labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
+        sb.segments[:n].copy_(torch.from_numpy(seg))
+        if long:
+            lens = sb.input_len
+            lens.copy_(torch.from_numpy(in_len))
+        else:
+            lens = buf.input_len
+        self._launch("segment_scores_long" if long else "segment_scores", _SEGMENTS, logq.data_ptr(), sb.labels.data_ptr(),
+                     lens.data_ptr(), sb.segments.data_ptr(), sb.out.data_ptr(), batch, t_out, k, sb.labels.shape[1], n, seg_l_max,
+                     sb.ws.data_ptr(), sb.ws.numel(), self._stream())
+        return sb.out[:n].cpu().numpy()
+
+    def ctc_segment_scores(self, label_batch, segments):
+        """CTC segment posteriors on the current buffer set's logq after forward(), under the input lengths of the last
+        set_input_lengths (ctc_align sets them): per row {b, frame_begin, frame_end, label_begin, label_end} of segments -- an
+        (N, 5) integer array, half-open ranges -- the log of the probability that those frames of utterance b, read on their
+        own, say exactly those letters of row b of label_batch (int (B, Lmax); at most longform.SEGMENT_MAX_LABEL letters per
+        segment).  With a word's range of a forced alignment: the word's confidence; over all frames and the whole label: minus
+        the CTC loss.  Returns float32 (N,) numpy, -inf where the frames cannot hold the letters.  Semantics: the entry point
+        sl_ctc_segment_scores of include/speechless_hip.h.  Uses tensors of its own, reused across calls."""
+        return self._segment_scores(False, None, label_batch, None, segments)
+
+    def ctc_segment_scores_long(self, logq, label_batch, prediction_lengths, segments):
+        """ctc_segment_scores() on a given (B, T', K) fp32 logq tensor in HBM (forward_long's) with its B prediction lengths:
+        one launch whatever the number of segments.  Does not touch the current buffer set."""
+        return self._segment_scores(True, logq, label_batch, prediction_lengths, segments)
 
     # ------------------------------------------------------------------ long recordings (longform.py)
 

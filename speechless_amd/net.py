@@ -678,6 +678,19 @@ class Wav2Letter:
             return engine.asg_viterbi(prediction_lengths)
         return engine.greedy_decode(prediction_lengths)
 
+    def _decode_for_evaluation(self, engine, prediction_lengths, lengths_are_set=False):
+        """what test_and_predict_batch predicts from the engine's current forward pass: the beam search of the net's decoder if
+        it has one (kenlm_directory), else _decode.  lengths_are_set: set_labels has stated the prediction lengths already."""
+        if self._beam_decoder is not None and self.criterion == "asg":
+            decoded, _ = engine.asg_beam_search(self._beam_decoder, prediction_lengths)
+        elif self._beam_decoder is not None and self.beam_search_device == "gpu":
+            decoded, _ = engine.beam_search(self._beam_decoder, prediction_lengths)
+        elif self._beam_decoder is not None:  # net.py:444-451: beam search scored by the language model
+            decoded, _ = self._beam_decoder.decode(engine.cur.probs.cpu().numpy(), prediction_lengths)
+        else:
+            decoded, _ = self._decode(engine, None if lengths_are_set else prediction_lengths)
+        return decoded
+
     def predict_batch_greedily_from_audio(self, raw_audio_batch, sample_rate=16000, fourier_window_length=512,
                                           hop_length=128, original_sample_rates=None):
         """Extension: predict_batch_greedily for raw audio (1-D float arrays).  STFT, power level, mel projection and
@@ -731,15 +744,7 @@ class Wav2Letter:
         engine.set_labels(inputs[names.label_batch], inputs[names.label_lengths],
                           inputs[names.prediction_lengths])
         losses = engine.loss().cpu().numpy()
-        if self._beam_decoder is not None and self.criterion == "asg":
-            decoded, _ = engine.asg_beam_search(self._beam_decoder, inputs[names.prediction_lengths])
-        elif self._beam_decoder is not None and self.beam_search_device == "gpu":
-            decoded, _ = engine.beam_search(self._beam_decoder, inputs[names.prediction_lengths])
-        elif self._beam_decoder is not None:  # net.py:444-451: beam search scored by the language model
-            decoded, _ = self._beam_decoder.decode(engine.cur.probs.cpu().numpy(),
-                                                   inputs[names.prediction_lengths])
-        else:
-            decoded, _ = self._decode(engine)
+        decoded = self._decode_for_evaluation(engine, inputs[names.prediction_lengths], lengths_are_set=True)
         predictions = [self.grapheme_encoding.decode_graphemes(d, merge_repeated=False) for d in decoded]
         n = len(predictions)
         letter_errors = word_errors = [None] * n  # None: ExpectationVsPrediction counts on the host (net.py:31-37)
@@ -815,6 +820,74 @@ class Wav2Letter:
         return self._positional_labels(self._alignment_batch("asg", labeled_spectrogram_batch), labeled_spectrogram_batch,
                                        seconds_per_input_step)
 
+    # ------------------------------------------------------------------ confidence (extension; alignment.py)
+    @staticmethod
+    def _word_segments(row, alignment):
+        """(b, frame_begin, frame_end, label_begin, label_end) of every word of an alignment of batch row `row`"""
+        from .alignment import word_spans
+        return [(row, first, end, begin, stop)
+                for (_, (first, end)), (begin, stop) in zip(alignment.word_frames, word_spans(alignment.label))]
+
+    def _scored_alignments(self, engine, labels, label_batch, prediction_lengths):
+        """labels aligned and scored on the engine's current forward pass: one ctc_align and one ctc_segment_scores launch,
+        whose segments are every word over its word_frames and, last of each utterance, the whole label over all its frames"""
+        from .alignment import CtcAlignment, ScoredAlignment
+        lengths = [len(label) for label in labels]
+        frames = np.asarray(prediction_lengths).reshape(-1)
+        paths, scores = engine.ctc_align(label_batch, lengths, prediction_lengths)
+        alignments = [CtcAlignment.from_path(label, score, path) for label, score, path in zip(labels, scores, paths)]
+        segments, whole = [], []
+        for row, (alignment, n) in enumerate(zip(alignments, lengths)):
+            segments.extend(self._word_segments(row, alignment))
+            whole.append(len(segments))
+            segments.append((row, 0, int(frames[row]), 0, n))
+        log_posteriors = engine.ctc_segment_scores(label_batch, np.asarray(segments, dtype=np.int64))
+        first = [0] + [i + 1 for i in whole[:-1]]
+        return [ScoredAlignment(alignment, log_posteriors[i:j], log_posteriors[j])
+                for alignment, i, j in zip(alignments, first, whole)]
+
+    def word_confidence_batch(self, labeled_spectrogram_batch):
+        """Extension (no reference counterpart): alignment_batch with confidences.  One forward pass on the evaluation engine,
+        one sl_ctc_align launch and one sl_ctc_segment_scores launch over the distribution the CTC loss sees: every word is
+        scored over the frames the alignment gives it -- the probability that those frames, read on their own, say exactly
+        that word -- and the whole label over all frames, which is minus the CTC loss.  Inputs and lengths are packed as
+        test_and_predict_batch packs them.  Returns a list of alignment.ScoredAlignment (frames = output frames)."""
+        self._require_alignment_kind("ctc", "word_confidence_batch", "predict_with_confidence_batch")
+        inputs = self._input_dictionary_for_loss_net(labeled_spectrogram_batch)
+        names = Wav2Letter.InputNames
+        engine = self.eval_engine
+        engine.forward(inputs[names.input_batch])
+        return self._scored_alignments(engine, [x.label for x in labeled_spectrogram_batch], inputs[names.label_batch],
+                                       inputs[names.prediction_lengths])
+
+    def _predict_with_confidence(self, spectrograms, greedy):
+        self._require_alignment_kind("ctc", "word_confidence_batch", "predict_with_confidence_batch")
+        input_batch, prediction_lengths = self._input_batch_and_prediction_lengths(spectrograms)
+        engine = self.eval_engine
+        engine.forward(input_batch)
+        if greedy:
+            decoded, _ = self._decode(engine, prediction_lengths)
+        else:
+            decoded = self._decode_for_evaluation(engine, np.reshape(np.array(prediction_lengths), (len(spectrograms), 1)))
+        transcripts = [self.grapheme_encoding.decode_graphemes(d, merge_repeated=False) for d in decoded]
+        return self._scored_alignments(engine, transcripts, self.grapheme_encoding.encode_label_batch(transcripts),
+                                       prediction_lengths)
+
+    def predict_with_confidence_batch(self, spectrograms):
+        """Extension (no reference counterpart): predict_batch_greedily with confidences.  The transcripts are exactly those of
+        predict_batch_greedily; each is then aligned and scored as word_confidence_batch scores a label, on the same forward
+        pass.  Returns a list of alignment.ScoredAlignment whose `label` is the transcript; an empty transcript (or one the
+        frames cannot hold) has no words."""
+        return self._predict_with_confidence(spectrograms, greedy=True)
+
+    def predict_with_confidence(self, labeled_spectrogram):
+        """predict with confidences: the transcript is exactly what predict returns for this net -- the beam search scored by
+        the language model when the net has one (kenlm_directory) -- aligned and scored on the same forward pass.  Returns an
+        alignment.ScoredAlignment whose `label` is the transcript."""
+        # (the example twice, as test_and_predict runs it)
+        spectrogram = labeled_spectrogram.z_normalized_transposed_spectrogram()
+        return self._predict_with_confidence([spectrogram, spectrogram], greedy=False)[0]
+
     # ------------------------------------------------------------------ long recordings (extension; longform.py)
     def _recording_spectrogram(self, spectrogram_or_example, what):
         if self.use_raw_wave_input:
@@ -841,10 +914,15 @@ class Wav2Letter:
         return self.grapheme_encoding.decode_graphemes(decoded, merge_repeated=False)
 
     def _align_recording(self, kind, example, window_input_frames):
+        return self._aligned_recording(kind, example, window_input_frames)[0]
+
+    def _aligned_recording(self, kind, example, window_input_frames, method=None):
+        """the alignment of a recording with what it was computed from: (alignment, engine, logq, labels (1, L), frames)"""
         from . import longform
         self._require_alignment_kind(kind, "align_recording", "positional_label_of_recording")
         asg = kind == "asg"
-        method, entry = ("asg_align_recording", "sl_asg_align_long") if asg else ("align_recording", "sl_ctc_align_long")
+        own, entry = ("asg_align_recording", "sl_asg_align_long") if asg else ("align_recording", "sl_ctc_align_long")
+        method = method or own
         spectrogram = self._recording_spectrogram(example, method)
         enc = self.grapheme_encoding
         encoded = enc.encode(example.label) if asg else None  # (CTC: one index per letter, encoded behind the forward pass)
@@ -856,15 +934,46 @@ class Wav2Letter:
         engine = self.eval_engine
         _, logq = engine.forward_long(spectrogram, window_input_frames)
         labels = np.asarray(encoded, dtype=np.int32).reshape(1, -1) if asg else enc.encode_label_batch([example.label])
-        paths, scores = (engine.asg_align_long if asg else engine.ctc_align_long)(
-            logq, labels, [letters], [spectrogram.shape[0] // self.input_to_prediction_length_ratio])
-        return self._alignment_from_path(kind, example.label, encoded, scores[0], paths[0])
+        frames = spectrogram.shape[0] // self.input_to_prediction_length_ratio
+        paths, scores = (engine.asg_align_long if asg else engine.ctc_align_long)(logq, labels, [letters], [frames])
+        return self._alignment_from_path(kind, example.label, encoded, scores[0], paths[0]), engine, logq, labels, frames
 
     def align_recording(self, example, window_input_frames=None):
         """alignment_batch for ONE recording of any length and a label of up to longform.ALIGN_MAX_LABEL letters:
         Engine.forward_long over windows, then one sl_ctc_align_long launch over the stitched logq.  Returns an
         alignment.CtcAlignment (frames = output frames); alignment.cut_sections cuts it into utterances."""
         return self._align_recording("ctc", example, window_input_frames)
+
+    def confidence_of_recording(self, example, max_section_frames=None, window_input_frames=None):
+        """word_confidence_batch for ONE recording of any length (align_recording's limits), and the check a corpus built
+        with alignment.cut_sections needs: Engine.forward_long over windows, one sl_ctc_align_long launch, then ONE
+        sl_ctc_segment_scores launch over the stitched logq that scores every word over its frames and -- if max_section_frames
+        is given -- every section of alignment.cut_section_spans(alignment, max_section_frames) over the section's own frames: a
+        section whose transcript does not match its audio scores far below its neighbours.  Returns (alignment.ScoredAlignment,
+        [(text, (first, end), log_posterior)]): the sections are those of cut_sections, none without max_section_frames.  The
+        ScoredAlignment's log_posterior is that of the whole label over all frames where the label has at most
+        longform.SEGMENT_MAX_LABEL letters, else nan.  A section of more letters than that raises a ValueError: lower
+        max_section_frames."""
+        from . import longform
+        from .alignment import ScoredAlignment, cut_section_spans
+        self._require_alignment_kind("ctc", "confidence_of_recording", "align_recording")
+        alignment, engine, logq, labels, frames = self._aligned_recording("ctc", example, window_input_frames,
+                                                                          "confidence_of_recording")
+        segments = self._word_segments(0, alignment)
+        n_words = len(segments)
+        sections = [] if max_section_frames is None else cut_section_spans(alignment, max_section_frames)
+        for text, (first, end), (begin, stop) in sections:
+            if stop - begin > longform.SEGMENT_MAX_LABEL:
+                raise ValueError("max_section_frames = {}: the section at frames [{}, {}) has {} letters, a segment takes at most "
+                                 "{} (sl_ctc_segment_scores); lower max_section_frames".format(
+                                     max_section_frames, first, end, stop - begin, longform.SEGMENT_MAX_LABEL))
+            segments.append((0, first, end, begin, stop))
+        whole = labels.shape[1] <= longform.SEGMENT_MAX_LABEL
+        if whole:
+            segments.append((0, 0, frames, 0, int(labels.shape[1])))
+        scores = engine.ctc_segment_scores_long(logq, labels, [frames], np.asarray(segments, dtype=np.int64)) if segments else []
+        scored = ScoredAlignment(alignment, scores[:n_words], scores[-1] if whole else float("nan"))
+        return scored, [(text, span, float(score)) for (text, span, _), score in zip(sections, scores[n_words:])]
 
     def positional_label_of_recording(self, example, seconds_per_input_step=None, window_input_frames=None):
         """positional_label_batch for ONE recording of any length (align_recording): its word timings in seconds, None where
