@@ -27,6 +27,14 @@ EPI_RELU_MASK = 3
 EPI_BIAS_ELU = 4
 EPI_ELU_MASK = 5
 
+# sl_conv1d_nt's out_f32: the output in the element type, as fp32 rows, or as hi + lo planes out of the epilogue
+NT_OUT_ELEM, NT_OUT_F32, NT_OUT_PLANES = 0, 1, 2
+# sl_split3 / sl_splitf16 `mode`: fp32 rows into planes as they are, through ReLU / ELU, or times the ReLU / ELU derivative
+# taken from the stored activation (`mask`)
+SPLIT_COPY, SPLIT_RELU, SPLIT_ELU, SPLIT_RELU_MASK, SPLIT_ELU_MASK = 0, 1, 2, 3, 4
+# sl_split3_dropout / sl_splitf16_dropout `mode`: forward; the 1 / (1 - rate) left behind a ReLU mask; keep * elu' behind an ELU
+DROP_FORWARD, DROP_SCALE, DROP_ELU_BACKWARD = 0, 1, 2
+
 
 class AdamLayer(ctypes.Structure):
     """Mirror of sl_adam_layer (include/speechless_hip.h)."""

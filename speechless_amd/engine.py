@@ -22,13 +22,14 @@ from ._lib import lib
 from .buffers import _Buffers
 from .engine_decode import DecodeAlignMixin, check_label_batch
 from .engine_front import FrontLayerMixin
+from .engine_launch import LaunchMixin, forward_epilogue, mask_epilogue
 from .engine_split import SplitTopMixin
 from .engine_x3 import X3Mixin
 from ._hipevents import TimingEvent
 from .plan import HALO, TIME_TILE, LayerPlan, LayerSpec, _round_up, same_padding, wav2letter_layer_specs  # noqa: F401
 
 
-class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
+class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
     """Forward / CTC / backward / Adam on one MI355X.  dtype 'bf16' (bf16 storage, fp32 accumulate, fp32 CTC: the
     benchmarked path), 'f32' (parity path: fp32 storage, exact-fp32 MFMA) or 'bf16x3' (the fast parity path: every value as
     hi + lo bf16 planes, three bf16 MFMA terms per product, fp32 accumulate; csrc/split3.hip) or 'f16x3' (the same scheme on
@@ -651,8 +652,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
         buf = self.buffers(batch, t_in)
         p0 = self.plans[0]
         if self.planes > 1:
-            self._launch("pack_input", self._x3("sl_split3_pack_input"), src.data_ptr(), buf.x0.data_ptr(), batch, t_in, f, p0.cin_pad,
-                         p0.pad_left, buf.rows0 * p0.cin_pad * self.planes, self._stream())
+            self._pack_input_x3(src, buf, t_in, f, self._stream())
         else:
             self._launch("pack_input", "sl_pack_input_ones", src.data_ptr(), buf.x0.data_ptr(), batch, t_in, f, p0.pad_left,
                          p0.cin_pad, buf.rows0 * p0.cin_pad, p0.cin_pad - 1 if self._has_ones_input() else -1, self.dtype_code,
@@ -733,20 +733,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
         if self.planes > 1:
             return self._forward_x3(buf, st, rate)
         n = len(self.plans)
-        x = buf.x0
-        seed0 = 0
-        if rate:
-            self._dropout_steps += 1
-            seed0 = (self.dropout_seed * 1000003 + self._dropout_steps) * 64
-            buf.dropout_seed0 = seed0  # ELU layers: backward recomputes the keep decisions (sl_elu_dropout_backward)
-        if self.front_plan is not None:
-            self._front_forward(buf, rate, seed0, st)
-        if rate:
-            if buf.x0_dropped is None:
-                buf.x0_dropped = torch.zeros_like(buf.x0)
-            self._launch("dropout:input", "sl_dropout", buf.x0.data_ptr(), buf.x0_dropped.data_ptr(), buf.x0.numel(),
-                         self.dtype_code, rate, seed0, st)
-            x = buf.x0_dropped
+        x, seed0 = self._forward_prologue(buf, rate, st)
         chained = {}  # first layer of a run -> the run, when it goes through sl_conv1d_chain
         if not rate:
             for (s0, e0) in self.runs:
@@ -778,19 +765,14 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
                              ctypes.byref(buf.fwd_geom[p.index]), self.grapheme_set_size, p.cout_pad,
                              buf.tt_pad * p.cout_pad, self.ctc_epsilon, self.dtype_code, st)
                 return buf.probs
-            self._launch("fwd:" + p.spec.name, "sl_conv1d_nt", x.data_ptr(), self.w_fwd[p.index].data_ptr(), bias.data_ptr(), None,
-                          y.data_ptr(), ctypes.byref(buf.fwd_geom[p.index]),
-                          _lib.EPI_BIAS if last else
-                          (_lib.EPI_BIAS_ELU if p.spec.activation == "elu" else _lib.EPI_BIAS_RELU),
-                          self.dtype_code, 1 if last else 0,
-                          self.nt_cfg.get(("fwd", p.spec.name), 0), buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
+            self._nt(buf, "fwd:" + p.spec.name, x, self.w_fwd[p.index], bias, None, y, buf.fwd_geom[p.index],
+                     _lib.EPI_BIAS if last else forward_epilogue(p.spec.activation),
+                     _lib.NT_OUT_F32 if last else _lib.NT_OUT_ELEM, self.nt_cfg.get(("fwd", p.spec.name), 0), st)
             if rate and (p.index + 1) in self._dropout_layers():
                 self._launch("dropout:" + p.spec.name, "sl_dropout", y.data_ptr(), y.data_ptr(), y.numel(),
                              self.dtype_code, rate, seed0 + p.index + 1, st)
             x = y
-        self._launch("softmax", "sl_softmax_logq", buf.logits.data_ptr(), buf.probs.data_ptr(), buf.logq.data_ptr(), buf.batch,
-                      buf.t_out, self.grapheme_set_size, self.plans[-1].cout_pad, buf.tt_pad * self.plans[-1].cout_pad,
-                      self.ctc_epsilon, st)
+        self._launch_softmax(buf, st)
         return buf.probs
 
     def set_input_lengths(self, prediction_lengths):
@@ -855,8 +837,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
     def _split_loss_grad(self, buf, tag):
         """plane paths, behind the criterion's kernel: the staged fp32 gradient into the planes of g[last]"""
         cp = self.plans[-1].cout_pad
-        self._launch(tag, self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[-1].data_ptr(), None, buf.batch, buf.t_out, cp,
-                     buf.tt_pad * cp, HALO, buf.rows * cp * self.planes, 0, self._stream())
+        self._split_planes(tag, buf.stage32, buf.g[-1], None, buf.batch, buf.t_out, cp, buf.tt_pad * cp, HALO,
+                           buf.rows * cp * self.planes, _lib.SPLIT_COPY, self._stream())
 
     def ctc(self, grad_scale=None, with_grad=True):
         """Per-utterance CTC loss of the current probabilities (tensor (B,) in HBM) and, into g[last], the gradient
@@ -1103,9 +1085,8 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
             return
         x = (buf.x0_dropped if buf.dropped else buf.x0) if i == 0 else buf.y[i - 1]
         dw, _ = self.layer_param_views(self.grads, p)
-        self._launch("wgrad:" + p.spec.name, "sl_conv1d_wgrad", x.data_ptr(), buf.g[i].data_ptr(), dw.data_ptr(),
-                     ctypes.byref(buf.wgrad_geom[i]), self.dtype_code, self.nt_cfg.get(("wgrad", p.spec.name), 0),
-                     buf.wgrad_ws.data_ptr(), buf.wgrad_ws.numel(), st)
+        self._wgrad(buf, "wgrad:" + p.spec.name, x, buf.g[i], dw, buf.wgrad_geom[i],
+                    self.nt_cfg.get(("wgrad", p.spec.name), 0), st)
 
     def _fused_output_backward(self, buf, i, first, grouped, dchain, dchain_skip):
         """layer i's weight AND input gradient in one sl_conv1d_backward_1x1 launch: the 1x1 output layer on the bf16 path"""
@@ -1124,33 +1105,17 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
     def _launch_output_backward(self, buf, i, st):
         p = self.plans[i]
         dw, _ = self.layer_param_views(self.grads, p)
-        epi = _lib.EPI_ELU_MASK if self.specs[i - 1].activation == "elu" else _lib.EPI_RELU_MASK
         self._launch("bwd:" + p.spec.name, "sl_conv1d_backward_1x1", buf.y[i - 1].data_ptr(), buf.g[i].data_ptr(),
                      self.w_dgrad[i].data_ptr(), buf.g[i - 1].data_ptr(), dw.data_ptr(), ctypes.byref(buf.wgrad_geom[i]),
-                     epi, self.grapheme_set_size, self.dtype_code, 0, buf.bwd1x1_ws.data_ptr(), buf.bwd1x1_ws.numel(), st)
+                     mask_epilogue(self.specs[i - 1].activation), self.grapheme_set_size, self.dtype_code, 0,
+                     buf.bwd1x1_ws.data_ptr(), buf.bwd1x1_ws.numel(), st)
 
     def _launch_dgrad(self, buf, i, st):
         """input gradient of layer i into g[i - 1], through the activation of layer i - 1 (and its dropout)"""
-        p = self.plans[i]
-        elu = self.specs[i - 1].activation == "elu"
-        elu_dropped = elu and buf.dropped and i in self._dropout_layers()
-        self._launch("dgrad:" + p.spec.name, "sl_conv1d_nt", buf.g[i].data_ptr(), self.w_dgrad[i].data_ptr(),
-                     None, None if elu_dropped else buf.y[i - 1].data_ptr(), buf.g[i - 1].data_ptr(),
-                     ctypes.byref(buf.dgrad_geom[i]),
-                     _lib.EPI_NONE if elu_dropped else (_lib.EPI_ELU_MASK if elu else _lib.EPI_RELU_MASK),
-                     self.dtype_code, 0, self.nt_cfg.get(("dgrad", p.spec.name), 0),
-                     buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
-        if elu_dropped:
-            # a stored zero is ambiguous behind an ELU (dropped, or elu(z) == 0): both factors of the chain rule
-            # in one elementwise pass that recomputes the keep decisions from the step's seed
-            self._launch("dropout_elu_bwd:" + p.spec.name, "sl_elu_dropout_backward", buf.g[i - 1].data_ptr(),
-                         buf.y[i - 1].data_ptr(), buf.g[i - 1].numel(), self.dtype_code, self.dropout_rate,
-                         buf.dropout_seed0 + i, st)
-        elif buf.dropped and i in self._dropout_layers():
-            # the dgrad epilogue's mask (stored activation > 0) already applied the keep mask: the stored
-            # activation is post-dropout; what is left of d dropout / dx is the 1 / (1 - rate) factor
-            self._launch("dropout_scale:" + p.spec.name, "sl_scale", buf.g[i - 1].data_ptr(), buf.g[i - 1].numel(),
-                         self.dtype_code, 1.0 / (1.0 - self.dropout_rate), st)
+        name = self.specs[i].name
+        self._dgrad_through(buf, name, buf.g[i], self.w_dgrad[i], buf.y[i - 1], buf.g[i - 1], buf.dgrad_geom[i],
+                            self.specs[i - 1].activation, buf.dropped and i in self._dropout_layers(), buf.dropout_seed0 + i,
+                            self.nt_cfg.get(("dgrad", name), 0), st)
 
     def _wgrad_multi_layers(self, first, grouped=None):
         """layers whose weight gradients go into ONE sl_conv1d_wgrad_multi launch (at the lowest of them): the runs of
@@ -1250,7 +1215,6 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
                 side_busy[0] = False
 
         n = len(self.plans)
-        hint = on_bucket_ready is not None and self.comm_cus
         split = buf.split_pending
         if split:  # the CTC ran in two parts: so do the input gradients of the top three layers (see self.split_top)
             self._backward_top_split(buf, main, split)
@@ -1275,14 +1239,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
             else:
                 self._launch_wgrad(buf, i, grouped, main.cuda_stream)
             if closes_bucket:
-                b, layers = bucket_at[i]
-                rows = [j for j in layers if j in ones_in]
-                if rows:
-                    self._bias_grads_from_wgrad(rows, bool(ones_db), main)
-                join_side()
-                self._bucket_ready(on_bucket_ready, b)
-                if hint and b == 0:  # from here on communication kernels may own CUs: the choosers plan for the rest
-                    self._eager_op(self._set_cu_hint, 256 - self.comm_cus)
+                self._close_bucket(on_bucket_ready, *bucket_at[i], ones_in, ones_db, main, join_side)
             if i in dchain:
                 layers = dchain[i]
                 ys, ws, masks = self._chain_table("dgrad", layers, buf)
@@ -1292,17 +1249,7 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
                              main.cuda_stream)
             elif i > first and i not in dchain_skip and not fused_bwd and not (split and i >= n - 3):
                 self._launch_dgrad(buf, i, main.cuda_stream)
-        if on_bucket_ready is None:
-            if ones_in:
-                self._bias_grads_from_wgrad(ones_in, bool(ones_db), main)
-            join_side()
-        if self.front_plan is not None and first == 0 and not self.front_frozen:
-            self._front_backward(buf, main.cuda_stream)
-            if on_bucket_ready is not None:  # the front layer's parameters: the last bucket of bucket_plan()
-                b = len(self.bucket_plan()) - 1
-                self._bucket_ready(on_bucket_ready, b)
-        if hint:
-            self._eager_op(self._set_cu_hint, 0)
+        self._backward_tail(buf, on_bucket_ready, ones_in, ones_db, main, join_side)
 
     def adam_step(self, fused=True):
         """Keras-2.0 Adam on the flat fp32 masters.  fused=True: one kernel per trainable layer that applies Adam AND
@@ -1467,20 +1414,19 @@ class Engine(X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
         """Fused update + operand repack of the given layers on stream st (self.adam_iterations already counts this step):
         ONE launch for all of them (sl_*adam_pack_layers; another rule: sl_*optimizer_pack_layers), 16 layers per call at
         most."""
-        # per operand format: the entry point's prefix and its arguments in front of / behind the rule's coefficients
+        # per operand format: the entry point and its arguments in front of / behind the rule's coefficients
         # (bf16x3: the [w_hi | w_hi | w_lo] operand rows are rewritten in the same pass, layer 0's pair view behind it)
-        if self.planes == 3 and self.x3_f16:
-            prefix, pre, post, pair = "sl_splitf16_", (), (self.w_scale,), self.w_dgrad[0] is not None
-        elif self.planes == 3:
-            prefix, pre, post, pair = "sl_split3_", (), (), self.w_dgrad[0] is not None
+        if self.planes == 3:
+            name, scaled = self._plane_entry("sl_split3_adam_pack_layers")
+            pre, post, pair = (), (self.w_scale,) if scaled else (), self.w_dgrad[0] is not None
         else:
-            prefix, pre, post, pair = "sl_", (self.dtype_code,), (), False
+            name, pre, post, pair = "sl_adam_pack_layers", (self.dtype_code,), (), False
         layers = list(layers)
         for lo in range(0, len(layers), 16):
             chunk = layers[lo:lo + 16]
             tag = "adam:{}..{}".format(self.all_plans[chunk[0]].spec.name, self.all_plans[chunk[-1]].spec.name)
             what = [t.data_ptr() if t is not None else None for t in self._state_buffers()]
-            self._launch_update(tag, prefix + "adam_pack_layers", (*what, self._adam_table(chunk), len(chunk)), pre, post, st)
+            self._launch_update(tag, name, (*what, self._adam_table(chunk), len(chunk)), pre, post, st)
             if pair and 0 in chunk:
                 self._pack_pair_dgrad_x3(st)
 

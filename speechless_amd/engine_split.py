@@ -5,6 +5,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .engine_launch import forward_epilogue, mask_epilogue
 from .plan import HALO
 
 
@@ -106,11 +107,8 @@ class SplitTopMixin:
                 p = self.plans[i]
                 _, bias = self.layer_param_views(self.params, p)
                 y = buf.y[i]
-                self._launch("fwd:" + p.spec.name, "sl_conv1d_nt", self._utt_ptr(xin, first), self.w_fwd[i].data_ptr(),
-                             bias.data_ptr(), None, self._utt_ptr(y, first),
-                             ctypes.byref(self._part_geom(buf, "fwd", i, count)),
-                             _lib.EPI_BIAS_ELU if p.spec.activation == "elu" else _lib.EPI_BIAS_RELU, self.dtype_code, 0, 0,
-                             buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
+                self._nt(buf, "fwd:" + p.spec.name, self._utt_ptr(xin, first), self.w_fwd[i], bias, None, self._utt_ptr(y, first),
+                         self._part_geom(buf, "fwd", i, count), forward_epilogue(p.spec.activation), _lib.NT_OUT_ELEM, 0, st)
                 xin = y
             self._eager_op(self._top_part_tail, buf, h, first, count, grad_scale)
         buf.split_pending = a
@@ -169,17 +167,15 @@ class SplitTopMixin:
             self._eager_op(self._wait_ctc_half, buf, h, main)
             p = self.plans[last]
             dw, _ = self.layer_param_views(self.grads, p)
-            epi = _lib.EPI_ELU_MASK if self.specs[last - 1].activation == "elu" else _lib.EPI_RELU_MASK
             self._launch("bwd:" + p.spec.name, "sl_conv1d_backward_1x1_part", self._utt_ptr(buf.y[last - 1], first),
                          self._utt_ptr(buf.g[last], first), self.w_dgrad[last].data_ptr(),
                          self._utt_ptr(buf.g[last - 1], first), dw.data_ptr(),
-                         ctypes.byref(self._part_geom(buf, "wgrad", last, count)), epi, self.grapheme_set_size,
+                         ctypes.byref(self._part_geom(buf, "wgrad", last, count)),
+                         mask_epilogue(self.specs[last - 1].activation), self.grapheme_set_size,
                          self.dtype_code, 0, h, buf.bwd1x1_ws.data_ptr(), buf.bwd1x1_ws.numel(), st)
             for i in (n - 2, n - 3):
                 q = self.plans[i]
-                elu = self.specs[i - 1].activation == "elu"
-                self._launch("dgrad:" + q.spec.name, "sl_conv1d_nt", self._utt_ptr(buf.g[i], first), self.w_dgrad[i].data_ptr(),
-                             None, self._utt_ptr(buf.y[i - 1], first), self._utt_ptr(buf.g[i - 1], first),
-                             ctypes.byref(self._part_geom(buf, "dgrad", i, count)),
-                             _lib.EPI_ELU_MASK if elu else _lib.EPI_RELU_MASK, self.dtype_code, 0, 0, buf.nt_ws.data_ptr(),
-                             buf.nt_ws.numel(), st)
+                self._nt(buf, "dgrad:" + q.spec.name, self._utt_ptr(buf.g[i], first), self.w_dgrad[i], None,
+                         self._utt_ptr(buf.y[i - 1], first), self._utt_ptr(buf.g[i - 1], first),
+                         self._part_geom(buf, "dgrad", i, count), mask_epilogue(self.specs[i - 1].activation), _lib.NT_OUT_ELEM,
+                         0, st)

@@ -1,7 +1,5 @@
 """The bf16x3 path of the engine (Engine(dtype="bf16x3")): every fp32 value as hi + lo bf16 planes, a product as three bf16 MFMA
 terms through the unchanged NT / TN kernels (csrc/split3.hip; DESIGN.md section 3.1, HISTORY.md section 3.6).  Methods of Engine."""
-import ctypes
-
 import torch
 
 from . import _lib
@@ -9,15 +7,6 @@ from .plan import HALO
 
 
 class X3Mixin:
-    def _x3(self, name):
-        """the entry point of a plane helper for this engine's plane format: sl_split3* (bf16 pairs) or its fp16 twin"""
-        return name.replace("sl_split3", "sl_splitf16", 1) if self.x3_f16 else name
-
-    def _pack_weights_x3(self, tag, w_master, w_fwd, w_dgrad, k, cin, cout, st):
-        """both operand copies [w_hi | w_hi | w_lo] of one layer from its fp32 master (f16x3: of w_scale * w)"""
-        args = (w_master.data_ptr(), w_fwd.data_ptr(), w_dgrad.data_ptr() if w_dgrad is not None else None, k, cin, cout)
-        self._launch(tag, self._x3("sl_split3_pack_weights"), *args, *((self.w_scale,) if self.x3_f16 else ()), st)
-
     def _repack_weights_x3(self):
         """bf16x3 operand copies: rows [w_hi | w_hi | w_lo] in both operand layouts, w_hi = bf16(w), w_lo = bf16(w - w_hi),
         one launch per layer (sl_split3_pack_weights; the five-launch sequence it replaces -- split, two packs, two
@@ -57,11 +46,6 @@ class X3Mixin:
             buf.plane_geoms[(kind, i)] = g
         return g
 
-    def _dropout_x3(self, tag, src, dst, y, channels, mode, seed, st):
-        """sl_split3_dropout over a whole plane tensor (halo rows and padding included: zeros stay zeros)"""
-        self._launch(tag, self._x3("sl_split3_dropout"), src.data_ptr(), dst.data_ptr(), y.data_ptr() if y is not None else None,
-                     src.numel() // (self.planes * channels), channels, mode, self.dropout_rate, seed, st)
-
     def _forward_x3(self, buf, st, rate=None):
         """bf16x3: every layer = the unchanged NT kernel over the three planes.  ReLU layers: bias, ReLU and the split into
         planes in the kernel's own epilogue (out_f32 = 2); ELU layers: fp32 into the staging buffer + sl_split3.  The last
@@ -69,50 +53,28 @@ class X3Mixin:
         on the packed input (into a second buffer) and in place on every activation that feeds a layer with a Dropout in
         front of it -- the same (seed, element) keep decisions as sl_dropout draws on the single-plane paths."""
         n = len(self.plans)
-        x = buf.x0
-        seed0 = 0
-        if rate:
-            self._dropout_steps += 1
-            seed0 = buf.dropout_seed0 = (self.dropout_seed * 1000003 + self._dropout_steps) * 64
-        if self.front_plan is not None:
-            self._front_forward(buf, rate, seed0, st)
-        if rate:
-            if buf.x0_dropped is None:
-                buf.x0_dropped = torch.zeros_like(buf.x0)
-            self._dropout_x3("dropout:input", buf.x0, buf.x0_dropped, None, self.plans[0].cin_pad, 0, seed0, st)
-            x = buf.x0_dropped
-
-        def drop(p):
-            if rate and (p.index + 1) in self._dropout_layers():
-                y = buf.y[p.index]
-                self._dropout_x3("dropout:" + p.spec.name, y, y, None, p.cout_pad, 0, seed0 + p.index + 1, st)
-
+        x, seed0 = self._forward_prologue(buf, rate, st)
         for p in self.plans:
             last = p.index == n - 1
             _, bias = self.layer_param_views(self.params, p)
             cfg = self.nt_cfg.get(("fwd", p.spec.name), 0)
-            if not last and p.spec.activation == "relu" and self.x3_fused_epilogue:
-                y = buf.y[p.index]
-                self._launch("fwd:" + p.spec.name, "sl_conv1d_nt", x.data_ptr(), self.w_fwd[p.index].data_ptr(),
-                             bias.data_ptr(), None, y.data_ptr(), ctypes.byref(self._plane_geom(buf, "fwd", p.index, p.cout_pad)),
-                             _lib.EPI_BIAS_RELU, self.dtype_code, 2, cfg, buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
-                drop(p)
-                x = y
-                continue
-            out = buf.logits if last else buf.stage32
-            self._launch("fwd:" + p.spec.name, "sl_conv1d_nt", x.data_ptr(), self.w_fwd[p.index].data_ptr(), bias.data_ptr(),
-                         None, out.data_ptr(), ctypes.byref(buf.fwd_geom[p.index]), _lib.EPI_BIAS, self.dtype_code, 1,
-                         cfg, buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
-            if not last:
-                y = buf.y[p.index]
-                self._launch("split:" + p.spec.name, self._x3("sl_split3"), buf.stage32.data_ptr(), y.data_ptr(), None, buf.batch,
-                             buf.t_out, p.cout_pad, buf.tt_pad * p.cout_pad, HALO, buf.rows * p.cout_pad * self.planes,
-                             2 if p.spec.activation == "elu" else 1, st)
-                drop(p)
-                x = y
-        self._launch("softmax", "sl_softmax_logq", buf.logits.data_ptr(), buf.probs.data_ptr(), buf.logq.data_ptr(), buf.batch,
-                     buf.t_out, self.grapheme_set_size, self.plans[-1].cout_pad, buf.tt_pad * self.plans[-1].cout_pad,
-                     self.ctc_epsilon, st)
+            name, w, geom = p.spec.name, self.w_fwd[p.index], buf.fwd_geom[p.index]
+            if last:
+                self._nt(buf, "fwd:" + name, x, w, bias, None, buf.logits, geom, _lib.EPI_BIAS, _lib.NT_OUT_F32, cfg, st)
+                break
+            y = buf.y[p.index]
+            if p.spec.activation == "relu" and self.x3_fused_epilogue:
+                self._nt(buf, "fwd:" + name, x, w, bias, None, y, self._plane_geom(buf, "fwd", p.index, p.cout_pad),
+                         _lib.EPI_BIAS_RELU, _lib.NT_OUT_PLANES, cfg, st)
+            else:
+                self._nt(buf, "fwd:" + name, x, w, bias, None, buf.stage32, geom, _lib.EPI_BIAS, _lib.NT_OUT_F32, cfg, st)
+                self._split_planes("split:" + name, buf.stage32, y, None, buf.batch, buf.t_out, p.cout_pad, buf.tt_pad * p.cout_pad,
+                                   HALO, buf.rows * p.cout_pad * self.planes,
+                                   _lib.SPLIT_ELU if p.spec.activation == "elu" else _lib.SPLIT_RELU, st)
+            if rate and (p.index + 1) in self._dropout_layers():
+                self._dropout_x3("dropout:" + name, y, y, None, p.cout_pad, _lib.DROP_FORWARD, seed0 + p.index + 1, st)
+            x = y
+        self._launch_softmax(buf, st)
         return buf.probs
 
     def _backward_x3(self, buf, st, on_bucket_ready=None):
@@ -129,7 +91,6 @@ class X3Mixin:
         main = torch.cuda.current_stream(self.device)
         plan = self.bucket_plan() if on_bucket_ready is not None else []
         bucket_at = {layers[0]: (b, layers) for b, (layers, _) in enumerate(plan)}
-        hint = on_bucket_ready is not None and self.comm_cus  # (as _backward_eager: the choosers plan for 256 - comm_cus)
         # the runs of identical layers (inner_conv_1..7): their 2 x 7 partial weight gradients (x planes against g_hi, against
         # g_lo) in ONE balanced launch (sl_conv1d_wgrad_multi, a job per partial) at the lowest layer of the run -- they
         # were 14 launches of 31 us + their reductions, 0.6 ms of the 6.8 ms step
@@ -137,88 +98,39 @@ class X3Mixin:
         for launch_layers in self._x3_multi_runs(first):
             for i in launch_layers:
                 multi[i] = launch_layers
-
-        def combine(p, ra, rb):
-            dw, _ = self.layer_param_views(self.grads, p)
-            frames = 2 if p.spec.stride == 2 else 1
-            fstride = pl * p.cin_pad if frames == 2 else 0
-            window = frames == 2 and buf.x3_window  # RB's x operand was the [hi0 | hi1] window of the pair row
-            args = (ra.data_ptr(), rb.data_ptr(), dw.data_ptr(), p.spec.kernel_size, p.cin_pad, p.cout_pad, frames, fstride,
-                    buf.wgrad_geom[p.index].cin, buf.wgrad_geom_b[p.index].cin, p.cin_pad if window else fstride)
-            if self.x3_f16:  # the partial sums are g_scale * dW (the gradient planes are stored scaled)
-                self._launch("combine:" + p.spec.name, "sl_split3_wgrad_combine_scaled", *args, 1.0 / self.g_scale, st)
-            else:
-                self._launch("combine:" + p.spec.name, "sl_split3_wgrad_combine", *args, st)
-
         for p in reversed(self.plans[first:]):
             i = p.index
+            name = p.spec.name
             x = (buf.x0_dropped if buf.dropped else buf.x0) if i == 0 else buf.y[i - 1]
             dw, db = self.layer_param_views(self.grads, p)
-            wa, wb = buf.wgrad_geom[i], buf.wgrad_geom_b[i]
+            if i in ones_db:
+                db = None  # (out of row cin_pad - 1 of dW)
+            g_stride = buf.rows * p.cout_pad * pl
             if i in multi:
                 if i == multi[i][0]:  # every gradient tensor of the run is complete here
-                    self._launch_wgrad_multi_x3(buf, multi[i], st, combine)
+                    self._launch_wgrad_multi_x3(buf, multi[i], st)
+                if db is not None:
+                    self._bias_grad_x3("bgrad:" + name, buf.g[i], db, buf.batch, buf.t_out, p.cout_pad, HALO, g_stride, st)
             else:
-                ra = buf.wgrad_r
-                rb = buf.wgrad_r[p.taps_view * wa.cin * p.cout_pad:]
-                g_lo = buf.g[i].data_ptr() + p.cout_pad * 2  # plane P1 of every row
-                cfg = self.nt_cfg.get(("wgrad", p.spec.name), 0)
-                self._launch("wgrad:" + p.spec.name, "sl_conv1d_wgrad", x.data_ptr(), buf.g[i].data_ptr(), ra.data_ptr(),
-                             ctypes.byref(wa), self.dtype_code, cfg, buf.wgrad_ws.data_ptr(), buf.wgrad_ws.numel(), st)
-                x_b = x.data_ptr() + (2 * p.cin_pad * 2 if (i == 0 and p.spec.stride == 2 and buf.x3_window) else 0)
-                self._launch("wgrad_lo:" + p.spec.name, "sl_conv1d_wgrad", x_b, g_lo, rb.data_ptr(),
-                             ctypes.byref(wb), self.dtype_code, cfg, buf.wgrad_ws.data_ptr(), buf.wgrad_ws.numel(), st)
-                combine(p, ra, rb)
-            if i not in ones_db:
-                if self._x3_bias_ws is None:
-                    self._x3_bias_ws = torch.empty((self.lib.raw("sl_split3_bias_grad_workspace_bytes")(
-                        max(q.cout_pad for q in self.plans)),), dtype=torch.uint8, device=self.device)
-                args = (buf.g[i].data_ptr(), db.data_ptr(), buf.batch, buf.t_out, p.cout_pad, HALO, buf.rows * p.cout_pad * pl)
-                scale = (1.0 / self.g_scale,) if self.x3_f16 else ()  # (f16x3: the gradient planes are stored scaled)
-                self._launch("bgrad:" + p.spec.name, self._x3("sl_split3_bias_grad"), *args, *scale,
-                             self._x3_bias_ws.data_ptr(), self._x3_bias_ws.numel(), st)
+                # the striding layer's pair view: two frames' planes per row; RB's x operand may be the [hi0 | hi1] window of
+                # the pair row (buf.x3_window)
+                frames = 2 if p.spec.stride == 2 else 1
+                fstride = pl * p.cin_pad if frames == 2 else 0
+                window = frames == 2 and buf.x3_window
+                x_b = x.data_ptr() + (2 * p.cin_pad * 2 if (i == 0 and window) else 0)
+                self._wgrad_bias_x3(buf, name, x, x_b, buf.g[i], dw, db, buf.wgrad_geom[i], buf.wgrad_geom_b[i],
+                                    p.spec.kernel_size, p.cin_pad, p.cout_pad, frames, fstride, p.cin_pad if window else fstride,
+                                    1.0 / self.g_scale, buf.t_out, HALO, g_stride, self.nt_cfg.get(("wgrad", name), 0), st)
             if i in bucket_at:
-                b, layers = bucket_at[i]
-                rows = [j for j in layers if j in ones_in]
-                if rows:
-                    self._bias_grads_from_wgrad(rows, bool(ones_db), main)
-                self._bucket_ready(on_bucket_ready, b)
-                if hint and b == 0:  # from here on communication kernels may own CUs
-                    self._eager_op(self._set_cu_hint, 256 - self.comm_cus)
-            dropped_in = buf.dropped and i in self._dropout_layers()  # a Dropout sits between y[i - 1] and layer i
-            elu = i > first and self.specs[i - 1].activation == "elu"
-            # a stored zero is ambiguous behind an ELU: plain input gradient (no mask), then both factors of the chain rule with
-            # the keep decisions recomputed from the step's seed (cf. sl_elu_dropout_backward)
-            elu_dropped = elu and dropped_in
-            if i > first and self.specs[i - 1].activation == "relu" and self.x3_fused_epilogue:
-                # the ReLU mask (the hi plane of the stored activation) and the split into planes in the NT kernel's epilogue
-                self._launch("dgrad:" + p.spec.name, "sl_conv1d_nt", buf.g[i].data_ptr(), self.w_dgrad[i].data_ptr(), None,
-                             buf.y[i - 1].data_ptr(), buf.g[i - 1].data_ptr(),
-                             ctypes.byref(self._plane_geom(buf, "dgrad", i, p.cin_pad)), _lib.EPI_RELU_MASK, self.dtype_code,
-                             2, self.nt_cfg.get(("dgrad", p.spec.name), 0), buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
-            elif i > first:
-                self._launch("dgrad:" + p.spec.name, "sl_conv1d_nt", buf.g[i].data_ptr(), self.w_dgrad[i].data_ptr(), None,
-                             None, buf.stage32.data_ptr(), ctypes.byref(buf.dgrad_geom[i]), _lib.EPI_NONE, self.dtype_code, 1,
-                             self.nt_cfg.get(("dgrad", p.spec.name), 0), buf.nt_ws.data_ptr(), buf.nt_ws.numel(), st)
-                self._launch("split:dgrad:" + p.spec.name, self._x3("sl_split3"), buf.stage32.data_ptr(), buf.g[i - 1].data_ptr(),
-                             None if elu_dropped else buf.y[i - 1].data_ptr(), buf.batch, buf.t_out, p.cin_pad,
-                             buf.tt_pad * p.cin_pad, HALO, buf.rows * p.cin_pad * pl, 0 if elu_dropped else (4 if elu else 3), st)
-            if elu_dropped:
-                self._dropout_x3("dropout_elu_bwd:" + p.spec.name, buf.g[i - 1], buf.g[i - 1], buf.y[i - 1], p.cin_pad, 2,
-                                 buf.dropout_seed0 + i, st)
-            elif i > first and dropped_in:
-                # the ReLU mask (stored activation > 0) already applied the keep mask: the stored activation is the
-                # post-dropout one; what is left of d dropout / dx is the factor 1 / (1 - rate)
-                self._dropout_x3("dropout_scale:" + p.spec.name, buf.g[i - 1], buf.g[i - 1], None, p.cin_pad, 1, 0, st)
-        if on_bucket_ready is None and ones_in:
-            self._bias_grads_from_wgrad(ones_in, bool(ones_db), main)
-        if self.front_plan is not None and first == 0 and not self.front_frozen:
-            self._front_backward(buf, st)
-            if on_bucket_ready is not None:  # the front layer's parameters: the last bucket of bucket_plan()
-                b = len(self.bucket_plan()) - 1
-                self._bucket_ready(on_bucket_ready, b)
-        if hint:
-            self._eager_op(self._set_cu_hint, 0)
+                self._close_bucket(on_bucket_ready, *bucket_at[i], ones_in, ones_db, main)
+            if i > first:
+                fused = self.specs[i - 1].activation == "relu" and self.x3_fused_epilogue
+                self._dgrad_through_x3(buf, name, buf.g[i], self.w_dgrad[i], buf.y[i - 1], buf.g[i - 1], buf.dgrad_geom[i],
+                                       self._plane_geom(buf, "dgrad", i, p.cin_pad) if fused else None,
+                                       self.specs[i - 1].activation, buf.dropped and i in self._dropout_layers(),
+                                       buf.dropout_seed0 + i, self.nt_cfg.get(("dgrad", name), 0), buf.t_out, p.cin_pad,
+                                       buf.tt_pad * p.cin_pad, HALO, buf.rows * p.cin_pad * pl, st)
+        self._backward_tail(buf, on_bucket_ready, ones_in, ones_db, main)
 
     def _wgrad_multi_layers_x3(self, first):
         """bf16x3: no launch writes the weight gradients of the striding layer AND of a run (bucket_plan() merges nothing)"""
@@ -246,7 +158,7 @@ class X3Mixin:
                 out.append(layers)
         return out
 
-    def _launch_wgrad_multi_x3(self, buf, layers, st, combine):
+    def _launch_wgrad_multi_x3(self, buf, layers, st):
         """bf16x3: the partial weight gradients RA (x planes [hi | lo] against g_hi) and RB (x plane hi against g_lo) of
         every layer of a run as jobs of one sl_conv1d_wgrad_multi launch, then sl_split3_wgrad_combine per layer"""
         key = ("x3", buf.dropped) + tuple(layers)
@@ -274,5 +186,8 @@ class X3Mixin:
         table, parts, _, ws = entry
         self._launch("wgrad:{}..{}".format(self.specs[layers[0]].name, self.specs[layers[-1]].name),
                      "sl_conv1d_wgrad_multi", table, len(table), self.dtype_code, ws.data_ptr(), ws.numel(), st)
-        for i, (ra, rb) in zip(layers, parts):
-            combine(self.plans[i], ra, rb)
+        for i, (ra, rb) in zip(layers, parts):  # (stride-1 layers, _x3_multi_runs: one frame per row, no window)
+            p = self.plans[i]
+            dw, _ = self.layer_param_views(self.grads, p)
+            self._combine_x3("combine:" + p.spec.name, ra, rb, dw, p.spec.kernel_size, p.cin_pad, p.cout_pad, 1, 0,
+                             buf.wgrad_geom[i].cin, buf.wgrad_geom_b[i].cin, 0, 1.0 / self.g_scale, st)
