@@ -477,6 +477,43 @@ int sl_asg_align(const float* logq, const float* trans, const float* init, const
                  const int32_t* input_len, int32_t* path, float* score, int batch, int t_out, int k, int l_max, void* workspace,
                  size_t workspace_bytes, void* stream);
 
+/* ---- ASG segment posteriors: the probability that a stretch of frames says exactly a stretch of an encoded label under the
+ *      ASG criterion (the ASG counterpart of sl_ctc_segment_scores).  ASG is globally normalised: over a stretch of frames the
+ *      constrained forward score minus the full-graph forward score is the log of a proper probability, with no approximation;
+ *      over the whole label and all frames it is exactly minus the loss of sl_asg_loss_grad.  No reference counterpart. ---
+ * logq, trans, init, labels, input_len: exactly as sl_asg_align takes them -- emissions e_t(j) = logq[b][t][j] used AS THEY
+ * ARE, trans[i*k + j] = g(i, j), init[j] = g0(j), label values clamped to [0, k); labels are encoded graphemes, there is no blank.
+ * segments: int32[n_segments][5] = {b, frame_begin, frame_end, label_begin, label_end}, half-open ranges into utterance b, clamped
+ * exactly as sl_ctc_segment_scores clamps them: frame_begin and frame_end each into [0, min(max(T_b, 0), t_out)], T = frame_end -
+ * frame_begin (0 if negative); label_begin and label_end each into [0, l_max], L = min(label_end - label_begin, seg_l_max) (0 if
+ * negative); l_i = clamp(labels[b][label_begin + i]), i < L; e_t = logq[b][frame_begin + t], t < T.
+ * Start scores: s(j) = g0(j) if the clamped label_begin is 0, else s(j) = g(p, j) with p = clamp(labels[b][label_begin - 1]), the
+ * grapheme just before the segment: a word in mid-utterance is scored given that the frame before it lay on the grapheme the
+ * label puts before it, and the whole label is scored as the loss scores it.
+ *   numerator    a_0(0) = s(l_0) + e_0(l_0),  a_0(i > 0) = -inf
+ *                a_t(i) = e_t(l_i) + LSE(a_{t-1}(i) + g(l_i, l_i),  a_{t-1}(i-1) + g(l_{i-1}, l_i));      N = a_{T-1}(L-1)
+ *   denominator  d_0(j) = s(j) + e_0(j);   d_t(j) = e_t(j) + LSE_i(d_{t-1}(i) + g(i, j));                Z = LSE_j d_{T-1}(j)
+ *   log_posterior[i] = N - Z, float32, natural logarithm.
+ * Adjacent equal graphemes need no special rule (as in sl_asg_loss_grad).  A per-frame constant added to a logq row cancels in
+ * N - Z, so logq may be sl_softmax_logq's output or log(p + eps), at any magnitude.
+ * L = 0 and T = 0: 0.  L = 0 and T > 0: -inf (without a blank no path says nothing).  T < L: -inf.  N = -inf through -inf entries
+ * of trans / init: -inf; Z = -inf (then N = -inf too): -inf.  Inputs that are finite or -inf never give a NaN.  b outside
+ * [0, batch): -inf, and nothing else of the segment is read.  Only log_posterior[0 .. n_segments) is written.
+ * Limits: 2 <= k <= 64, 0 <= seg_l_max <= 511, n_segments >= 1: SL_ERR_UNSUPPORTED otherwise.  A null pointer (labels may be
+ * null when l_max = 0) or batch, t_out <= 0 or l_max < 0 is SL_ERR_INVALID_ARGUMENT, a workspace below the size asked for
+ * SL_ERR_WORKSPACE_TOO_SMALL; all of these are refused on the host before any launch, in sl_ctc_segment_scores' order.  The score
+ * tables may be as large as sl_asg_loss_grad's denominator supports (exp(g) is held in doubles); the project tests +-30.
+ * Not bit-exact: the numerator is held in doubles in log2 units with each step's log2 of a sum in [1, 2] taken in fp32, the
+ * denominator in doubles in the probability domain, rescaled every frame; against a float64 evaluation of the above over the
+ * same float32 inputs the result is within 1e-6 * (T + |log_posterior|), and -inf matches exactly.
+ * workspace: sl_asg_segment_scores_workspace_bytes(n_segments, seg_l_max, k) bytes -- 0 today: a segment's lattices live in the
+ * registers and LDS of its work-group (workspace may then be null).  One work-group of two waves per segment (numerator beside
+ * denominator); 1 / 2 / 4 / 8 label states per lane for seg_l_max <= 64 / 128 / 256 / 511. */
+size_t sl_asg_segment_scores_workspace_bytes(int n_segments, int seg_l_max, int k);
+int sl_asg_segment_scores(const float* logq, const float* trans, const float* init, const int32_t* labels,
+                          const int32_t* input_len, const int32_t* segments, float* log_posterior, int batch, int t_out, int k,
+                          int l_max, int n_segments, int seg_l_max, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- ASG forced alignment of long recordings: sl_asg_align beyond 511 graphemes.  Arguments, their order and every rule
  *      (states, stay / move, the strict-> compare with a tie that stays, three separately rounded fp32 adds and no multiply,
  *      end state L-1 at T_b-1, infeasible rows -- L = 0, T_b = 0, L > T_b or a score of -inf: score -inf and the whole row -1 --,

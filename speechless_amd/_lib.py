@@ -170,6 +170,11 @@ SIGNATURES = {
     "sl_asg_align_long_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "sl_asg_align_long": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "sl_asg_segment_scores_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    # logq, trans, init, labels, input_len, segments, log_posterior, batch, t_out, k, l_max, n_segments, seg_l_max, workspace,
+    # bytes, stream
+    "sl_asg_segment_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "sl_edit_distance_supported": (c_int, [c_int, c_int]),
     "sl_edit_distance": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p]),

@@ -6,7 +6,8 @@ sections, which LabeledExampleFromFile.sections() (:219-234) uses to cut long re
 utterance's Viterbi alignment (include/speechless_hip.h, sl_ctc_align) turned into character and word frame ranges;
 `AsgAlignment` is the same for the ASG criterion (sl_asg_align / sl_asg_align_long), whose path runs over the run-length-encoded label.
 `ScoredAlignment` adds the confidences of sl_ctc_segment_scores to a `CtcAlignment` (Wav2Letter.word_confidence_batch /
-predict_with_confidence_batch / confidence_of_recording): a `WordConfidence` per word and the posterior of the whole label."""
+predict_with_confidence_batch / confidence_of_recording), or those of sl_asg_segment_scores to an `AsgAlignment` (the asg_ methods
+of the same names): a `WordConfidence` per word and the posterior of the whole label."""
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -158,7 +159,8 @@ def cut_section_spans(alignment, max_frames: int) -> List[Tuple[str, Tuple[int, 
 
 class WordConfidence:
     """One word of a scored alignment: its output frames [first, end) and the log of its segment posterior -- the
-    probability that those frames, read on their own, say exactly the word (sl_ctc_segment_scores)."""
+    probability that those frames, read on their own, say exactly the word (sl_ctc_segment_scores; under ASG
+    sl_asg_segment_scores, where a word in mid-utterance is read given the grapheme the label puts before it)."""
 
     def __init__(self, word: str, first: int, end: int, log_posterior: float):
         self.word = word
@@ -175,11 +177,12 @@ class WordConfidence:
 
 
 class ScoredAlignment:
-    """A CtcAlignment with confidences.  words: a WordConfidence per word of alignment.word_frames, in order (empty when the
-    alignment is infeasible or has no words).  log_posterior: the whole label over all of the utterance's frames, log p(label |
-    audio) = minus the CTC loss (-inf when infeasible)."""
+    """A CtcAlignment or an AsgAlignment (anything with `label` and `word_frames`) with confidences.  words: a WordConfidence
+    per word of alignment.word_frames, in order (empty when the alignment is infeasible or has no words).  log_posterior: the
+    whole label over all of the utterance's frames, log p(label | audio) = minus the CTC loss, or minus the ASG loss (-inf when
+    infeasible)."""
 
-    def __init__(self, alignment: CtcAlignment, word_log_posteriors, log_posterior: float):
+    def __init__(self, alignment, word_log_posteriors, log_posterior: float):
         word_log_posteriors = [float(x) for x in word_log_posteriors]
         if len(word_log_posteriors) != len(alignment.word_frames):
             raise ValueError("{} word scores for the {} words of {!r}".format(len(word_log_posteriors), len(alignment.word_frames),
@@ -212,6 +215,53 @@ def _characters_per_grapheme(label: str) -> List[Tuple[int, bool]]:
         counts.extend([[(1, False)], [(1, False), (1, True)], [(1, False), (2, True)]][j - i - 1])
         i = j
     return counts
+
+
+def grapheme_spans(label: str, char_spans) -> List[Tuple[int, int]]:
+    """(begin, end), half-open, in the ASG encoding of `label` of each (char_begin, char_end) span of `label` (word_spans',
+    or a section's of cut_section_spans): what sl_asg_segment_scores takes as a label range.  A letter and its repeat mark
+    belong wholly to the span that holds the run; a span that begins or ends inside a run of equal characters would split
+    such a pair -- between words only a run of spaces can be split -- and raises ValueError."""
+    first = {0: 0}  # character offset at which a run begins (or the label ends) -> graphemes before it
+    chars = graphemes = 0
+    for count, is_mark in _characters_per_grapheme(label):
+        if not is_mark:
+            first[chars] = graphemes
+        chars += count
+        graphemes += 1
+    first[chars] = graphemes
+    spans = []
+    for begin, end in char_spans:
+        if not 0 <= begin <= end <= len(label):
+            raise ValueError("span ({}, {}) outside the {} characters of {!r}".format(begin, end, len(label), label))
+        for p in (begin, end):
+            if 0 < p < len(label) and label[p - 1] == label[p]:
+                raise ValueError("span ({}, {}) splits the run of {!r} at character {} of {!r}: a letter and its repeat mark "
+                                 "are scored together".format(begin, end, label[p], p, label))
+        spans.append((first[begin], first[end]))
+    return spans
+
+
+def cut_section_grapheme_spans(alignment, max_frames: int) -> List[Tuple[str, Tuple[int, int], Tuple[int, int]]]:
+    """cut_section_spans for an AsgAlignment, with each section's span in the ENCODED label: (text, (first, end),
+    (grapheme_begin, grapheme_end)).  What Wav2Letter.asg_confidence_of_recording scores."""
+    sections = cut_section_spans(alignment, max_frames)
+    spans = grapheme_spans(alignment.label, [chars for _, _, chars in sections])
+    return [(text, frames, span) for (text, frames, _), span in zip(sections, spans)]
+
+
+def encode_transcripts(encoding, transcripts) -> list:
+    """the ASG-encoded label (a list of grapheme indices) of every transcript of a decode under `encoding` (an
+    AsgGraphemeEncoding), or None in place of one the encoding refuses: a decoded grapheme sequence may stack repeat marks
+    (letter, thrice, letter ...) into a run of more than three equal letters, which encode() cannot write.  What
+    Wav2Letter.asg_predict_with_confidence_batch aligns and scores."""
+    rows = []
+    for transcript in transcripts:
+        try:
+            rows.append([int(g) for g in encoding.encode(transcript)])
+        except ValueError:
+            rows.append(None)
+    return rows
 
 
 class AsgAlignment(_WordTimings):

@@ -52,7 +52,7 @@ class _Buffers:
         self._argmax_flat = torch.zeros((batch * self.tt_pad,), dtype=torch.int32, device=dev)
         self.g = [None] * n  # allocated lazily by ensure_backward()
         self.align = None  # _AlignBuffers of Engine.ctc_align / asg_align (frames = tt_pad), on first use
-        self.segment = None  # _SegmentBuffers of Engine.ctc_segment_scores, on first use
+        self.segment = None  # _SegmentBuffers of Engine.ctc_ / asg_segment_scores, on first use
         self.asg_score = self.asg_vit_ws = None  # (B,) result and workspace of Engine.asg_viterbi, on first use
         self.error_counts = self.edit_rows = None  # allocated lazily by ensure_error_counts() / ensure_edit_rows()
         self.decoded_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
@@ -420,13 +420,16 @@ class _AlignBuffers:
 
 
 class _SegmentBuffers:
-    """Tensors of Engine.ctc_segment_scores / ctc_segment_scores_long (engine_decode.py): the labels, the input lengths of a
-    logq tensor handed to the _long method, the (N, 5) segments, their (N,) results and the workspace whose size
-    sl_ctc_segment_scores_workspace_bytes states.  _Buffers.segment serves a buffer set, Engine._long_segment a logq tensor handed
-    over.  Grown only."""
+    """Tensors of Engine.ctc_segment_scores / asg_segment_scores and their _long methods (engine_decode.py): the labels, the
+    input lengths of a logq tensor handed to the _long method, the (N, 5) segments, their (N,) results and the workspace whose
+    size the library's workspace_query(n_segments, seg_l_max, *query_tail) states (the ASG query also takes the class count).
+    One instance serves one entry point (an engine has one criterion): _Buffers.segment a buffer set, Engine._long_segment a
+    logq tensor handed over.  Grown only."""
 
-    def __init__(self, device):
+    def __init__(self, device, workspace_query="sl_ctc_segment_scores_workspace_bytes", query_tail=()):
         self.device = device
+        self.workspace_query = workspace_query
+        self.query_tail = tuple(query_tail)
         self.labels = self.input_len = self.segments = self.out = self.ws = None
 
     def ensure(self, batch, l_max, n_segments, seg_l_max):
@@ -438,6 +441,6 @@ class _SegmentBuffers:
         if self.segments is None or self.segments.shape[0] < n_segments:
             self.segments = torch.zeros((n_segments, 5), dtype=torch.int32, device=dev)
             self.out = torch.zeros((n_segments,), dtype=torch.float32, device=dev)
-        need = lib().raw("sl_ctc_segment_scores_workspace_bytes")(n_segments, seg_l_max)
+        need = lib().raw(self.workspace_query)(n_segments, seg_l_max, *self.query_tail)
         if self.ws is None or self.ws.numel() < need:
             self.ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)

@@ -14,7 +14,7 @@ CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "ctc_long.hip", "misc.hip", "optimizer.hip", "spectrogram.hip", "conv_chain_bf16.hip",
            "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip", "ctc_segment.hip",
            "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
-           "resample.hip"]
+           "asg_segment.hip", "resample.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
 # f16x3 parity path (csrc/common.h: SL_MFMA16; only the fp32 / plane-output instantiations, about a third of the bf16 build)
 F16_VARIANTS = {"conv_nt_f16": "conv_nt_bf16.hip", "wgrad_tn_f16": "wgrad_tn_bf16.hip"}
@@ -51,9 +51,11 @@ def _newest_source_mtime():
 # puts a memory round trip beside every FMA of the tap loop)
 # (ctc_segment.hip: up to 16 lattice states in doubles, their columns and a chunk of staged emissions per lane are register
 # arrays indexed by unrolled constants; scratch there is memory traffic on the per-frame sequential path of a lone wave)
+# (asg_segment.hip: up to 8 label states in doubles with their two scores each, and a chunk of staged emissions per lane, are
+# register arrays indexed by unrolled constants; scratch there is memory traffic on the per-frame sequential path of either wave)
 NO_SCRATCH = {"resample.hip","conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
               "ctc_align_long.hip", "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
-              "ctc_long.hip", "ctc_segment.hip"}
+              "ctc_long.hip", "ctc_segment.hip", "asg_segment.hip"}
 
 
 def _scratch_users(remarks):

@@ -1,12 +1,13 @@
 // lattice.h -- what the lattice kernels that keep their states in registers share (ctc_align.hip, ctc_align_long.hip, asg.hip,
-// asg_align.hip, asg_align_long.hip, ctc_segment.hip):
+// asg_align.hip, asg_align_long.hip, ctc_segment.hip, asg_segment.hip):
 //   - the clamps of lengths and labels, and the neighbour-lane move;
 //   - the windows of whole backpointer rows that a one-wave backtrace pulls from HBM into LDS (load_window / store_window),
 //     and the bands of them that a long aligner's backtrace pulls (load_band / store_band);
 //   - for the four forced aligners, each piece that include/speechless_hip.h defines bit for bit, ONCE: the CTC states of a
 //     thread and their frame step (ctc_states_init / ctc_frame), the ASG ones (asg_states_init / asg_frame), and the stager of
 //     their emissions (EmissionStager, ALIGN_CH);
-//   - for the segment posteriors (ctc_segment.hip), the SUMMING frame step over the same states (ctc_frame_sum), in doubles.
+//   - for the segment posteriors (ctc_segment.hip, asg_segment.hip), the SUMMING frame steps over the same states
+//     (ctc_frame_sum, asg_frame_sum), in doubles.
 // No helper here holds a barrier, a fence or a return: those stay in the kernels, next to the argument for their uniformity.
 #pragma once
 #include "common.h"
@@ -195,6 +196,20 @@ __device__ __forceinline__ void asg_frame(const int (&col)[NS], const float (&gs
         const bool mv = move > stay;
         word[j] = __ballot(mv);
         d[j] = (mv ? move : stay) + e[col[j]];
+    }
+}
+// The same frame with the SUM in place of the max, for the numerator (alpha) lattice of sl_asg_segment_scores: d[] in doubles
+// and log2 units, gs[] / ga[] the same scores in doubles times log2(e); a(s) = log2(2^(a(s) + gs) + 2^(a(s-1) + ga)) + e(l_s) *
+// log2(e), the sum by lse2_long of lse_double.h and the emission by one fma.  No backpointers.  A state beyond the label
+// stays at -inf as above.
+template <int NS>
+__device__ __forceinline__ void asg_frame_sum(const int (&col)[NS], const double (&gs)[NS], const double (&ga)[NS], double (&d)[NS],
+                                              const float* e, double lo) {
+#pragma unroll
+    for (int j = NS - 1; j >= 0; --j) {  // descending: d[j-1] still holds frame t-1
+        const double stay = d[j] + gs[j];
+        const double move = (j >= 1 ? d[j - 1] : lo) + ga[j];
+        d[j] = fma((double)e[col[j]], LOG2E_D, lse2_long(stay, move));
     }
 }
 // Band of a long aligner's backtrace window w: rows w*BT_W .. min(T, w*BT_W + BT_W) - 1, dwords base .. base + BAND - 1 of each

@@ -1,7 +1,7 @@
 """What runs on the probabilities behind forward() outside the training step: greedy / Viterbi / beam decoding, the four forced
-aligners, the CTC segment posteriors, long recordings (longform.py) and the error counts.  One host path each: the aligners
+aligners, the CTC and ASG segment posteriors, long recordings (longform.py) and the error counts.  One host path each: the aligners
 differ by a row of _ALIGNERS, their label batches pass check_label_batch, their tensors live in buffers._AlignBuffers (the
-segment posteriors': _SegmentBuffers).  Methods of Engine."""
+segment posteriors differ by a row of _SEGMENTERS, theirs live in _SegmentBuffers).  Methods of Engine."""
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -30,7 +30,24 @@ _ALIGNERS = {  # (kind, long)
     ("asg", True): _Aligner("sl_asg_align_long", "asg_align_long", longform.ASG_ALIGN_MAX_LABEL,
                             "labels of {} graphemes: ASG forced alignment takes at most {}"),
 }
-_SEGMENTS = "sl_ctc_segment_scores"
+
+
+class _Segmenter(NamedTuple):
+    """one segment-posterior kernel: its entry point (the workspace query is <entry>_workspace_bytes; under ASG it also takes
+    the class count), its launch tag (the _long method's: tag + "_long"), whether it runs under the ASG criterion (labels in
+    [0, K), no blank, the engine's score tables) or over the CTC lattice (labels in [0, K - 1), blank = K - 1), and the most
+    label positions a segment may span with the word the refusal uses for them"""
+    entry: str
+    tag: str
+    asg: bool
+    max_label: int
+    unit: str
+
+
+_SEGMENTERS = {
+    "ctc": _Segmenter("sl_ctc_segment_scores", "segment_scores", False, longform.SEGMENT_MAX_LABEL, "letters"),
+    "asg": _Segmenter("sl_asg_segment_scores", "asg_segment_scores", True, longform.ASG_SEGMENT_MAX_LABEL, "graphemes"),
+}
 _VITERBI = "sl_asg_viterbi"
 _GREEDY = "sl_greedy_decode"
 
@@ -61,20 +78,22 @@ def check_label_batch(labels, lengths, batch, n_labels, *, blank=None, in_len=No
     return labels, lab_len
 
 
-def check_segments(segments, batch):
-    """What the engine asks of the segments of ctc_segment_scores, on the host: (N, 5) integers {b, frame_begin, frame_end,
-    label_begin, label_end} with N >= 1, b in [0, batch), 0 <= begin <= end for both ranges and a label span of at most
-    longform.SEGMENT_MAX_LABEL letters; the first row that breaks a rule is named.  Returns them as contiguous int32 numpy."""
+def check_segments(segments, batch, kind="ctc"):
+    """What the engine asks of the segments of ctc_segment_scores / asg_segment_scores (row _SEGMENTERS[kind]), on the host:
+    (N, 5) integers {b, frame_begin, frame_end, label_begin, label_end} with N >= 1, b in [0, batch), 0 <= begin <= end for both
+    ranges and a label span of at most longform.SEGMENT_MAX_LABEL letters (ASG_SEGMENT_MAX_LABEL encoded graphemes); the first
+    row that breaks a rule is named.  Returns them as contiguous int32 numpy."""
+    row = _SEGMENTERS[kind]
     seg = np.asarray(segments)
     if seg.ndim != 2 or seg.shape[1] != 5 or seg.shape[0] < 1 or not np.issubdtype(seg.dtype, np.integer):
         raise ValueError("segments must be an (N, 5) integer array of (b, frame_begin, frame_end, label_begin, label_end), N >= 1")
     seg = seg.astype(np.int64)
     bad = (seg[:, 0] < 0) | (seg[:, 0] >= batch) | (seg[:, 1] < 0) | (seg[:, 2] < seg[:, 1]) | (seg[:, 3] < 0) | \
-        (seg[:, 4] < seg[:, 3]) | (seg[:, 4] - seg[:, 3] > longform.SEGMENT_MAX_LABEL) | (seg[:, 1:].max(axis=1) >= 2 ** 31)
+        (seg[:, 4] < seg[:, 3]) | (seg[:, 4] - seg[:, 3] > row.max_label) | (seg[:, 1:].max(axis=1) >= 2 ** 31)
     if bad.any():
         i = int(np.argmax(bad))
-        raise ValueError("segment {} = {}: need b in [0, {}), 0 <= begin <= end for frames and letters, and at most {} letters "
-                         "({})".format(i, seg[i].tolist(), batch, longform.SEGMENT_MAX_LABEL, _SEGMENTS))
+        raise ValueError("segment {0} = {1}: need b in [0, {2}), 0 <= begin <= end for frames and {4}, and at most {3} {4} "
+                         "({5})".format(i, seg[i].tolist(), batch, row.max_label, row.unit, row.entry))
     return np.ascontiguousarray(seg, dtype=np.int32)
 
 
@@ -198,9 +217,18 @@ class DecodeAlignMixin:
             lens = buf.input_len
         path = ab.path[:batch * t_out]
         scores = [t.data_ptr() for t in self._asg_views(self.asg_params)] if asg else []  # trans, init
-        self._launch(row.tag, row.entry, logq.data_ptr(), *scores, ab.labels.data_ptr(), ab.label_len.data_ptr(), lens.data_ptr(),
-                     path.data_ptr(), ab.score.data_ptr(), batch, t_out, k, ab.labels.shape[1], ab.ws.data_ptr(), ab.ws.numel(),
-                     self._stream())
+        try:
+            self._launch(row.tag, row.entry, logq.data_ptr(), *scores, ab.labels.data_ptr(), ab.label_len.data_ptr(),
+                         lens.data_ptr(), path.data_ptr(), ab.score.data_ptr(), batch, t_out, k, ab.labels.shape[1],
+                         ab.ws.data_ptr(), ab.ws.numel(), self._stream())
+        except Exception:
+            # a refused launch (labels wider than the entry point takes) must not leave its tensors behind: they are grown
+            # only, and their width is the l_max of every later call on this buffer set
+            if long:
+                self._long_align = None
+            else:
+                buf.align = None
+            raise
         return path.view(batch, t_out).cpu().numpy(), ab.score.cpu().numpy()
 
     def ctc_align(self, label_batch, label_lengths, prediction_lengths):
@@ -238,11 +266,16 @@ class DecodeAlignMixin:
 
     # ------------------------------------------------------------------ segment posteriors
 
-    def _segment_scores(self, long, logq, label_batch, prediction_lengths, segments):
-        """sl_ctc_segment_scores over the current buffer set's logq with its input lengths (tensors: buf.segment), or -- long --
-        over a given logq with its prediction lengths (tensors: _long_segment).  Checks in _align's order: the criterion, logq
-        (long), the segments, the labels -- of each row the letters that some segment covers.  Returns float32 (N,) numpy."""
-        if self.criterion == "asg":
+    def _segment_scores(self, kind, long, logq, label_batch, prediction_lengths, segments):
+        """The two segment-posterior kernels (row _SEGMENTERS[kind]) over the current buffer set's logq with its input lengths
+        (tensors: buf.segment), or -- long -- over a given logq with its prediction lengths (tensors: _long_segment).  Checks in
+        _align's order: the criterion, logq (long), the segments, the labels -- of each row the positions that some segment
+        covers.  Returns float32 (N,) numpy."""
+        row = _SEGMENTERS[kind]
+        tag = row.tag + ("_long" if long else "")
+        if row.asg:
+            self._require_asg(tag + "()")
+        elif self.criterion == "asg":
             raise ValueError("criterion='asg': segment posteriors run over the CTC lattice (blank = K - 1); not supported")
         k = self.grapheme_set_size
         if long:
@@ -251,17 +284,18 @@ class DecodeAlignMixin:
         else:
             buf, in_len = self.cur, None
             logq, batch, t_out = buf.logq, buf.batch, buf.t_out
-        seg = check_segments(segments, batch)
+        seg = check_segments(segments, batch, kind)
         labels = np.asarray(label_batch, dtype=np.int32)
         covered = np.zeros((batch,), dtype=np.int32)
         np.maximum.at(covered, seg[:, 0], seg[:, 4])
-        labels, _ = check_label_batch(labels, np.minimum(covered, labels.shape[1] if labels.ndim == 2 else 0), batch, k - 1,
-                                      blank=k - 1, in_len=in_len)
+        labels, _ = check_label_batch(labels, np.minimum(covered, labels.shape[1] if labels.ndim == 2 else 0), batch,
+                                      k if row.asg else k - 1, blank=None if row.asg else k - 1, in_len=in_len)
         n, seg_l_max = int(seg.shape[0]), int((seg[:, 4] - seg[:, 3]).max())
+        query = (row.entry + "_workspace_bytes", (k,) if row.asg else ())
         if long:
-            sb = self._long_segment = self._long_segment or _SegmentBuffers(self.device)
+            sb = self._long_segment = self._long_segment or _SegmentBuffers(self.device, *query)
         else:
-            sb = buf.segment = buf.segment or _SegmentBuffers(self.device)
+            sb = buf.segment = buf.segment or _SegmentBuffers(self.device, *query)
         sb.ensure(batch, max(int(labels.shape[1]), 1), n, seg_l_max)
         sb.labels.zero_()  # (at least as wide as the labels)
         sb.labels[:, :labels.shape[1]].copy_(torch.from_numpy(np.ascontiguousarray(labels)))
@@ -271,9 +305,10 @@ class DecodeAlignMixin:
             lens.copy_(torch.from_numpy(in_len))
         else:
             lens = buf.input_len
-        self._launch("segment_scores_long" if long else "segment_scores", _SEGMENTS, logq.data_ptr(), sb.labels.data_ptr(),
-                     lens.data_ptr(), sb.segments.data_ptr(), sb.out.data_ptr(), batch, t_out, k, sb.labels.shape[1], n, seg_l_max,
-                     sb.ws.data_ptr(), sb.ws.numel(), self._stream())
+        scores = [t.data_ptr() for t in self._asg_views(self.asg_params)] if row.asg else []  # trans, init
+        self._launch(tag, row.entry, logq.data_ptr(), *scores, sb.labels.data_ptr(), lens.data_ptr(), sb.segments.data_ptr(),
+                     sb.out.data_ptr(), batch, t_out, k, sb.labels.shape[1], n, seg_l_max, sb.ws.data_ptr(), sb.ws.numel(),
+                     self._stream())
         return sb.out[:n].cpu().numpy()
 
     def ctc_segment_scores(self, label_batch, segments):
@@ -284,12 +319,28 @@ class DecodeAlignMixin:
         segment).  With a word's range of a forced alignment: the word's confidence; over all frames and the whole label: minus
         the CTC loss.  Returns float32 (N,) numpy, -inf where the frames cannot hold the letters.  Semantics: the entry point
         sl_ctc_segment_scores of include/speechless_hip.h.  Uses tensors of its own, reused across calls."""
-        return self._segment_scores(False, None, label_batch, None, segments)
+        return self._segment_scores("ctc", False, None, label_batch, None, segments)
 
     def ctc_segment_scores_long(self, logq, label_batch, prediction_lengths, segments):
         """ctc_segment_scores() on a given (B, T', K) fp32 logq tensor in HBM (forward_long's) with its B prediction lengths:
         one launch whatever the number of segments.  Does not touch the current buffer set."""
-        return self._segment_scores(True, logq, label_batch, prediction_lengths, segments)
+        return self._segment_scores("ctc", True, logq, label_batch, prediction_lengths, segments)
+
+    def asg_segment_scores(self, label_batch, segments):
+        """ctc_segment_scores() for the ASG criterion, on the current buffer set's logq -- the emissions asg_viterbi() and
+        asg_align() see -- and the engine's asg_trans / asg_init, under the input lengths of the last set_input_lengths
+        (asg_align sets them): per segment row the constrained forward score of those ENCODED graphemes of row b of label_batch
+        (indices in [0, K), no blank; at most longform.ASG_SEGMENT_MAX_LABEL per segment) over those frames minus the forward
+        score of the full graph over the same frames, both started from g0 where the segment begins the label and else from the
+        scores out of the grapheme before it: the log of a proper probability.  Over all frames and the whole label: minus the
+        ASG loss.  Returns float32 (N,) numpy, -inf where the frames cannot hold the graphemes or -inf scores close every path.
+        Semantics: the entry point sl_asg_segment_scores of include/speechless_hip.h.  Uses tensors of its own."""
+        return self._segment_scores("asg", False, None, label_batch, None, segments)
+
+    def asg_segment_scores_long(self, logq, label_batch, prediction_lengths, segments):
+        """asg_segment_scores() on a given (B, T', K) fp32 logq tensor in HBM (forward_long's) with its B prediction lengths:
+        one launch whatever the number of segments.  Does not touch the current buffer set."""
+        return self._segment_scores("asg", True, logq, label_batch, prediction_lengths, segments)
 
     # ------------------------------------------------------------------ long recordings (longform.py)
 

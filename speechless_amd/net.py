@@ -821,30 +821,48 @@ class Wav2Letter:
                                        seconds_per_input_step)
 
     # ------------------------------------------------------------------ confidence (extension; alignment.py)
+    # kind "ctc": sl_ctc_align + sl_ctc_segment_scores over the label's letters; kind "asg": sl_asg_align + sl_asg_segment_scores
+    # over the encoded label, under the asg_ names.  One body per method pair; a method refuses the net of the other criterion.
     @staticmethod
-    def _word_segments(row, alignment):
-        """(b, frame_begin, frame_end, label_begin, label_end) of every word of an alignment of batch row `row`"""
-        from .alignment import word_spans
-        return [(row, first, end, begin, stop)
-                for (_, (first, end)), (begin, stop) in zip(alignment.word_frames, word_spans(alignment.label))]
+    def _word_segments(kind, row, alignment):
+        """(b, frame_begin, frame_end, label_begin, label_end) of every word of an alignment of batch row `row`: the label
+        range counts letters (ctc) or encoded graphemes (asg: a letter and its repeat mark belong to the word that holds them)"""
+        from .alignment import grapheme_spans, word_spans
+        spans = word_spans(alignment.label)
+        if kind == "asg":
+            spans = grapheme_spans(alignment.label, spans)
+        return [(row, first, end, begin, stop) for (_, (first, end)), (begin, stop) in zip(alignment.word_frames, spans)]
 
-    def _scored_alignments(self, engine, labels, label_batch, prediction_lengths):
-        """labels aligned and scored on the engine's current forward pass: one ctc_align and one ctc_segment_scores launch,
-        whose segments are every word over its word_frames and, last of each utterance, the whole label over all its frames"""
-        from .alignment import CtcAlignment, ScoredAlignment
-        lengths = [len(label) for label in labels]
+    def _scored_alignments(self, kind, engine, labels, label_batch, label_lengths, prediction_lengths):
+        """labels aligned and scored on the engine's current forward pass: one ctc_align / asg_align and one ctc_segment_scores /
+        asg_segment_scores launch, whose segments are every word over its word_frames and, last of each utterance, the whole
+        (ctc: label, asg: encoded label) over all its frames"""
+        from .alignment import ScoredAlignment
+        asg = kind == "asg"
+        lengths = [int(n) for n in np.asarray(label_lengths).reshape(-1)]
         frames = np.asarray(prediction_lengths).reshape(-1)
-        paths, scores = engine.ctc_align(label_batch, lengths, prediction_lengths)
-        alignments = [CtcAlignment.from_path(label, score, path) for label, score, path in zip(labels, scores, paths)]
+        paths, scores = (engine.asg_align if asg else engine.ctc_align)(label_batch, lengths, prediction_lengths)
+        alignments = [self._alignment_from_path(kind, label, encoded[:n], score, path)
+                      for label, encoded, n, score, path in zip(labels, label_batch, lengths, scores, paths)]
         segments, whole = [], []
         for row, (alignment, n) in enumerate(zip(alignments, lengths)):
-            segments.extend(self._word_segments(row, alignment))
+            segments.extend(self._word_segments(kind, row, alignment))
             whole.append(len(segments))
             segments.append((row, 0, int(frames[row]), 0, n))
-        log_posteriors = engine.ctc_segment_scores(label_batch, np.asarray(segments, dtype=np.int64))
+        log_posteriors = (engine.asg_segment_scores if asg else engine.ctc_segment_scores)(
+            label_batch, np.asarray(segments, dtype=np.int64))
         first = [0] + [i + 1 for i in whole[:-1]]
         return [ScoredAlignment(alignment, log_posteriors[i:j], log_posteriors[j])
                 for alignment, i, j in zip(alignments, first, whole)]
+
+    def _word_confidence_batch(self, kind, labeled_spectrogram_batch):
+        self._require_alignment_kind(kind, "word_confidence_batch", "predict_with_confidence_batch")
+        inputs = self._input_dictionary_for_loss_net(labeled_spectrogram_batch)
+        names = Wav2Letter.InputNames
+        engine = self.eval_engine
+        engine.forward(inputs[names.input_batch])
+        return self._scored_alignments(kind, engine, [x.label for x in labeled_spectrogram_batch], inputs[names.label_batch],
+                                       inputs[names.label_lengths], inputs[names.prediction_lengths])
 
     def word_confidence_batch(self, labeled_spectrogram_batch):
         """Extension (no reference counterpart): alignment_batch with confidences.  One forward pass on the evaluation engine,
@@ -852,16 +870,20 @@ class Wav2Letter:
         scored over the frames the alignment gives it -- the probability that those frames, read on their own, say exactly
         that word -- and the whole label over all frames, which is minus the CTC loss.  Inputs and lengths are packed as
         test_and_predict_batch packs them.  Returns a list of alignment.ScoredAlignment (frames = output frames)."""
-        self._require_alignment_kind("ctc", "word_confidence_batch", "predict_with_confidence_batch")
-        inputs = self._input_dictionary_for_loss_net(labeled_spectrogram_batch)
-        names = Wav2Letter.InputNames
-        engine = self.eval_engine
-        engine.forward(inputs[names.input_batch])
-        return self._scored_alignments(engine, [x.label for x in labeled_spectrogram_batch], inputs[names.label_batch],
-                                       inputs[names.prediction_lengths])
+        return self._word_confidence_batch("ctc", labeled_spectrogram_batch)
 
-    def _predict_with_confidence(self, spectrograms, greedy):
-        self._require_alignment_kind("ctc", "word_confidence_batch", "predict_with_confidence_batch")
+    def asg_word_confidence_batch(self, labeled_spectrogram_batch):
+        """word_confidence_batch for criterion='asg': one forward pass, one sl_asg_align launch and one sl_asg_segment_scores
+        launch over the emissions and scores the ASG loss sees.  Every word is scored over the frames asg_alignment_batch gives
+        it with its span of the ENCODED label (a letter and its repeat mark belong to the word that holds them): the constrained
+        forward score minus the full graph's over the same frames, a proper probability under the globally normalised
+        criterion; a word in mid-utterance is read given the grapheme the label puts before it.  The whole encoded label over
+        all frames is minus the ASG loss.  Returns a list of alignment.ScoredAlignment over alignment.AsgAlignment."""
+        return self._word_confidence_batch("asg", labeled_spectrogram_batch)
+
+    def _predict_with_confidence(self, kind, spectrograms, greedy):
+        from .alignment import encode_transcripts
+        self._require_alignment_kind(kind, "word_confidence_batch", "predict_with_confidence_batch")
         input_batch, prediction_lengths = self._input_batch_and_prediction_lengths(spectrograms)
         engine = self.eval_engine
         engine.forward(input_batch)
@@ -869,16 +891,26 @@ class Wav2Letter:
             decoded, _ = self._decode(engine, prediction_lengths)
         else:
             decoded = self._decode_for_evaluation(engine, np.reshape(np.array(prediction_lengths), (len(spectrograms), 1)))
-        transcripts = [self.grapheme_encoding.decode_graphemes(d, merge_repeated=False) for d in decoded]
-        return self._scored_alignments(engine, transcripts, self.grapheme_encoding.encode_label_batch(transcripts),
-                                       prediction_lengths)
+        enc = self.grapheme_encoding
+        transcripts = [enc.decode_graphemes(d, merge_repeated=False) for d in decoded]
+        if kind == "ctc":
+            return self._scored_alignments(kind, engine, transcripts, enc.encode_label_batch(transcripts),
+                                           [len(t) for t in transcripts], prediction_lengths)
+        # a decode may stack repeat marks into a run that the encoding cannot write: such a transcript is not scored
+        rows = encode_transcripts(enc, transcripts)
+        label_batch = np.full((len(rows), max(len(r or ()) for r in rows)), -1, dtype=np.int32)
+        for out, r in zip(label_batch, rows):
+            out[:len(r or ())] = r or ()
+        scored = self._scored_alignments(kind, engine, [t if r is not None else "" for t, r in zip(transcripts, rows)],
+                                         label_batch, [len(r or ()) for r in rows], prediction_lengths)
+        return [s if r is not None else None for s, r in zip(scored, rows)]
 
     def predict_with_confidence_batch(self, spectrograms):
         """Extension (no reference counterpart): predict_batch_greedily with confidences.  The transcripts are exactly those of
         predict_batch_greedily; each is then aligned and scored as word_confidence_batch scores a label, on the same forward
         pass.  Returns a list of alignment.ScoredAlignment whose `label` is the transcript; an empty transcript (or one the
         frames cannot hold) has no words."""
-        return self._predict_with_confidence(spectrograms, greedy=True)
+        return self._predict_with_confidence("ctc", spectrograms, greedy=True)
 
     def predict_with_confidence(self, labeled_spectrogram):
         """predict with confidences: the transcript is exactly what predict returns for this net -- the beam search scored by
@@ -886,7 +918,24 @@ class Wav2Letter:
         alignment.ScoredAlignment whose `label` is the transcript."""
         # (the example twice, as test_and_predict runs it)
         spectrogram = labeled_spectrogram.z_normalized_transposed_spectrogram()
-        return self._predict_with_confidence([spectrogram, spectrogram], greedy=False)[0]
+        return self._predict_with_confidence("ctc", [spectrogram, spectrogram], greedy=False)[0]
+
+    def asg_predict_with_confidence_batch(self, spectrograms):
+        """predict_with_confidence_batch for criterion='asg': the transcripts are exactly those of predict_batch_greedily (the
+        ASG Viterbi decode); each is then ENCODED again, aligned and scored as asg_word_confidence_batch scores a label, on the
+        same forward pass.  Returns a list whose entries are alignment.ScoredAlignment (`label` is the transcript; an empty
+        transcript has no words and log_posterior -inf) -- or None for a transcript that AsgGraphemeEncoding.encode refuses: a
+        decode can stack repeat marks (letter, thrice, letter, ...) into a run of more than three equal letters, which no
+        encoded label can say, so there is nothing to score."""
+        return self._predict_with_confidence("asg", spectrograms, greedy=True)
+
+    def asg_predict_with_confidence(self, labeled_spectrogram):
+        """predict_with_confidence for criterion='asg': the transcript is exactly what predict returns for this net -- the ASG
+        beam search scored by the language model when the net has one on the GPU, else the Viterbi decode -- encoded, aligned
+        and scored on the same forward pass.  Returns an alignment.ScoredAlignment, or None as asg_predict_with_confidence_batch
+        does for a transcript that cannot be encoded."""
+        spectrogram = labeled_spectrogram.z_normalized_transposed_spectrogram()
+        return self._predict_with_confidence("asg", [spectrogram, spectrogram], greedy=False)[0]
 
     # ------------------------------------------------------------------ long recordings (extension; longform.py)
     def _recording_spectrogram(self, spectrogram_or_example, what):
@@ -944,6 +993,33 @@ class Wav2Letter:
         alignment.CtcAlignment (frames = output frames); alignment.cut_sections cuts it into utterances."""
         return self._align_recording("ctc", example, window_input_frames)
 
+    def _confidence_of_recording(self, kind, example, max_section_frames, window_input_frames):
+        from . import longform
+        from .alignment import ScoredAlignment, cut_section_grapheme_spans, cut_section_spans
+        asg = kind == "asg"
+        own = "asg_confidence_of_recording" if asg else "confidence_of_recording"
+        limit, unit, entry = (longform.ASG_SEGMENT_MAX_LABEL, "encoded graphemes", "sl_asg_segment_scores") if asg else \
+            (longform.SEGMENT_MAX_LABEL, "letters", "sl_ctc_segment_scores")
+        self._require_alignment_kind(kind, "confidence_of_recording", "align_recording")
+        alignment, engine, logq, labels, frames = self._aligned_recording(kind, example, window_input_frames, own)
+        segments = self._word_segments(kind, 0, alignment)
+        n_words = len(segments)
+        sections = [] if max_section_frames is None else \
+            (cut_section_grapheme_spans if asg else cut_section_spans)(alignment, max_section_frames)
+        for text, (first, end), (begin, stop) in sections:
+            if stop - begin > limit:
+                raise ValueError("max_section_frames = {}: the section at frames [{}, {}) has {} {}, a segment takes at most "
+                                 "{} ({}); lower max_section_frames".format(
+                                     max_section_frames, first, end, stop - begin, unit, limit, entry))
+            segments.append((0, first, end, begin, stop))
+        whole = labels.shape[1] <= limit
+        if whole:
+            segments.append((0, 0, frames, 0, int(labels.shape[1])))
+        score = engine.asg_segment_scores_long if asg else engine.ctc_segment_scores_long
+        scores = score(logq, labels, [frames], np.asarray(segments, dtype=np.int64)) if segments else []
+        scored = ScoredAlignment(alignment, scores[:n_words], scores[-1] if whole else float("nan"))
+        return scored, [(text, span, float(score)) for (text, span, _), score in zip(sections, scores[n_words:])]
+
     def confidence_of_recording(self, example, max_section_frames=None, window_input_frames=None):
         """word_confidence_batch for ONE recording of any length (align_recording's limits), and the check a corpus built
         with alignment.cut_sections needs: Engine.forward_long over windows, one sl_ctc_align_long launch, then ONE
@@ -954,26 +1030,17 @@ class Wav2Letter:
         ScoredAlignment's log_posterior is that of the whole label over all frames where the label has at most
         longform.SEGMENT_MAX_LABEL letters, else nan.  A section of more letters than that raises a ValueError: lower
         max_section_frames."""
-        from . import longform
-        from .alignment import ScoredAlignment, cut_section_spans
-        self._require_alignment_kind("ctc", "confidence_of_recording", "align_recording")
-        alignment, engine, logq, labels, frames = self._aligned_recording("ctc", example, window_input_frames,
-                                                                          "confidence_of_recording")
-        segments = self._word_segments(0, alignment)
-        n_words = len(segments)
-        sections = [] if max_section_frames is None else cut_section_spans(alignment, max_section_frames)
-        for text, (first, end), (begin, stop) in sections:
-            if stop - begin > longform.SEGMENT_MAX_LABEL:
-                raise ValueError("max_section_frames = {}: the section at frames [{}, {}) has {} letters, a segment takes at most "
-                                 "{} (sl_ctc_segment_scores); lower max_section_frames".format(
-                                     max_section_frames, first, end, stop - begin, longform.SEGMENT_MAX_LABEL))
-            segments.append((0, first, end, begin, stop))
-        whole = labels.shape[1] <= longform.SEGMENT_MAX_LABEL
-        if whole:
-            segments.append((0, 0, frames, 0, int(labels.shape[1])))
-        scores = engine.ctc_segment_scores_long(logq, labels, [frames], np.asarray(segments, dtype=np.int64)) if segments else []
-        scored = ScoredAlignment(alignment, scores[:n_words], scores[-1] if whole else float("nan"))
-        return scored, [(text, span, float(score)) for (text, span, _), score in zip(sections, scores[n_words:])]
+        return self._confidence_of_recording("ctc", example, max_section_frames, window_input_frames)
+
+    def asg_confidence_of_recording(self, example, max_section_frames=None, window_input_frames=None):
+        """confidence_of_recording for criterion='asg' (asg_align_recording's limits): Engine.forward_long over windows, one
+        sl_asg_align_long launch, then ONE sl_asg_segment_scores launch over the stitched logq for every word, every section of
+        alignment.cut_section_grapheme_spans(alignment, max_section_frames) and the whole encoded label.  A word or section in
+        mid-recording is read given the grapheme the label puts before it.  Returns (alignment.ScoredAlignment over an
+        alignment.AsgAlignment, [(text, (first, end), log_posterior)]) as confidence_of_recording does; the whole-label
+        log_posterior is nan where the ENCODED label exceeds longform.ASG_SEGMENT_MAX_LABEL graphemes, and a section of more
+        encoded graphemes than that raises a ValueError: lower max_section_frames."""
+        return self._confidence_of_recording("asg", example, max_section_frames, window_input_frames)
 
     def positional_label_of_recording(self, example, seconds_per_input_step=None, window_input_frames=None):
         """positional_label_batch for ONE recording of any length (align_recording): its word timings in seconds, None where
