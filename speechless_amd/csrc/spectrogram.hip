@@ -48,9 +48,10 @@ __global__ __launch_bounds__(256) void stft_power_db_kernel(const float* __restr
     float* win = (float*)(zbuf + 4 * half);        // periodic Hann window
     const int log2h = log2n - 1;
     for (int n = tid; n < n_fft; n += 256) {
-        float sn, cs;
-        sincospif(2.f * (float)n / (float)n_fft, &sn, &cs);
-        win[n] = 0.5f - 0.5f * cs;
+        // sin^2(pi n / N), not 0.5 - 0.5 cos(2 pi n / N): the cosine next to 1 is rounded to 2^-25, which is 4e-4 of the
+        // window's value one sample from its edge -- what a frame beside digital silence or a lone click is made of
+        const float sn = sinpif((float)n / (float)n_fft);
+        win[n] = sn * sn;
     }
     for (int k = tid; k < half; k += 256) {
         float sn, cs;
