@@ -882,6 +882,50 @@ int sl_stft_power_db(const float* audio, const int64_t* offsets, const int32_t* 
                      int max_frames, int n_fft, int hop, int row_stride, int64_t batch_stride, float min_db,
                      void* stream);
 
+/* sl_stft: the same transform (input layout, frame rule, window, n_fft range, rows and zero padding of sl_stft_power_db) with a
+ * choice of what a row holds -- the spectrogram types of labeled_example.py:17-25, 120-134 and the complex STFT itself (:99-100):
+ *      SL_STFT_POWER        |D|^2
+ *      SL_STFT_AMPLITUDE    |D|
+ *      SL_STFT_COMPLEX      D, interleaved: bin k of a row is the two floats at 2k (re) and 2k + 1 (im); row_stride >= 2 * bins
+ *      SL_STFT_POWER_LEVEL  what sl_stft_power_db writes, bit for bit (the same kernel)
+ * min_db is read in the power-level mode only.  Columns behind the bins (behind 2 * bins for complex rows) and rows
+ * t >= 1 + lengths[b] / hop are zero in every mode.  Digital silence gives exact zeros in the first three.  With a the float64
+ * amplitude and delta_t = 16 log2(n_fft) 2^-24 sum_n |x_t[n]| (w[n] + 2^-23) over the frame (DESIGN.md sections 3.8, 3.9):
+ * each of re and im within delta_t, |amplitude - a| <= delta_t + 1e-5 a, |power - a^2| <= 2 a delta_t + delta_t^2 + 1e-5 a^2.
+ * Errors: SL_ERR_INVALID_ARGUMENT for a null pointer, a mode not listed, n_fft outside the range or rows too short. */
+#define SL_STFT_POWER 0
+#define SL_STFT_AMPLITUDE 1
+#define SL_STFT_COMPLEX 2
+#define SL_STFT_POWER_LEVEL 3
+int sl_stft(const float* audio, const int64_t* offsets, const int32_t* lengths, float* out, int batch, int max_frames,
+            int n_fft, int hop, int row_stride, int64_t batch_stride, int mode, float min_db, void* stream);
+
+/* sl_istft: complex rows in the layout SL_STFT_COMPLEX writes -> audio, as librosa.istft(D, hop_length, win_length=n_fft) with
+ * its defaults (labeled_example.py:162-164), in the form that normalises by the summed squared window:
+ *      frame t = real inverse transform of its 1 + n_fft/2 bins (the imaginary parts of the DC and Nyquist bins are ignored,
+ *                as numpy.fft.irfft does), times the periodic Hann window, added at sample t * hop of a buffer of
+ *                n_fft + hop (frames[b] - 1) samples;
+ *      the buffer is divided by the sum of the squared windows wherever that sum exceeds the smallest normal float and left as
+ *      it is elsewhere; n_fft / 2 samples are cut off both ends.
+ * This normalisation is taken from knowledge of librosa; the 2017 librosa the reference ran on cannot be imported where this
+ * library is built and tested, so the choice is NOT verified against it.
+ *   spec        : float[B][max_frames][row_stride] at batch_stride, row_stride >= 2 * bins; utterance b has frames[b] >= 1 rows
+ *                 (frames: int32 in HBM; capped at max_frames); rows >= frames[b] and columns >= 2 * bins are never read
+ *   audio       : utterance b's hop * (frames[b] - 1) samples go to audio + out_offsets[b]; nothing else is written.  A single
+ *                 frame yields no samples, and that is legal.
+ * One work-group per (utterance, tile of sl_istft_tile_frames(n_fft, hop) * hop consecutive samples): it inverse-transforms the
+ * frames that cover the tile into LDS (the forward kernel's half-length transform run backwards) and every thread sums the up to
+ * 8 windowed contributions of its samples in ascending frame order -- no floating-point atomics, and a sample's value depends on
+ * its utterance's rows alone, not on the tile, the tile size or the batch.  Error bound per sample: DESIGN.md section 3.9.
+ * Limits: n_fft a power of two in [64, 1024]; n_fft / 8 <= hop <= n_fft (at most 8 overlapping frames per sample), outside that
+ * SL_ERR_UNSUPPORTED.  SL_ERR_INVALID_ARGUMENT for a null pointer, batch outside [1, 65535], max_frames or hop < 1, n_fft
+ * outside the range, rows too short, max_frames * hop + n_fft >= 2^31.  All of these on the host, before any launch.
+ * All work on `stream`, no workspace, no allocation, no synchronisation.
+ * sl_istft_tile_frames: frames of output per work-group at (n_fft, hop); 0 outside the limits. */
+int sl_istft_tile_frames(int n_fft, int hop);
+int sl_istft(const float* spec, const int32_t* frames, float* audio, const int64_t* out_offsets, int batch, int max_frames,
+             int n_fft, int hop, int row_stride, int64_t batch_stride, void* stream);
+
 /* z_normalize (labeled_example.py:28-29, 136-140): per utterance (a - mean(a)) / std(a) over its frames[b] x f values
  * (population standard deviation, float64 statistics like numpy), written densely as float[B][max_frames][f]; rows
  * t >= frames[b] are zero -- exactly the zero-padded input batch of net.py:578-587, ready for sl_pack_input.

@@ -20,6 +20,9 @@ SL_BF16 = 0
 SL_F32 = 1
 SL_F16 = 2
 
+# sl_stft `mode` (include/speechless_hip.h)
+STFT_POWER, STFT_AMPLITUDE, STFT_COMPLEX, STFT_POWER_LEVEL = 0, 1, 2, 3
+
 EPI_NONE = 0
 EPI_BIAS = 1
 EPI_BIAS_RELU = 2
@@ -191,6 +194,12 @@ SIGNATURES = {
                                    c_int, c_int, c_float, c_float, c_float, c_float, c_void_p]),
     "sl_stft_power_db": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64,
                                  c_float, c_void_p]),
+    # audio, offsets, lengths, out, batch, max_frames, n_fft, hop, row_stride, batch_stride, mode, min_db, stream
+    "sl_stft": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, c_float,
+                        c_void_p]),
+    "sl_istft_tile_frames": (c_int, [c_int, c_int]),
+    # spec, frames, audio, out_offsets, batch, max_frames, n_fft, hop, row_stride, batch_stride, stream
+    "sl_istft": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "sl_z_normalize_workspace_bytes": (c_size_t, [c_int]),
     "sl_z_normalize": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int64, c_void_p, c_size_t,
                                c_void_p]),

@@ -7,6 +7,12 @@
 //
 // HBM-bound by nature (0.5 MB of samples in, 1.3 MB of dB values out per 1000 frames); the Fourier transform is a
 // radix-2 FFT in LDS, one wave per frame, several frames resident per CU.
+//
+// sl_stft is the same kernel with a choice of what the split step leaves in the row (|D|^2, |D|, D itself or the level:
+// labeled_example.py:17-25, 120-134), and sl_istft (librosa.istft, labeled_example.py:162-164) runs the same half-length
+// transform backwards and overlap-adds the windowed frames as a gather: see istft_kernel.
+#include <cfloat>
+
 #include "common.h"
 
 namespace {
@@ -30,11 +36,69 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 __device__ __forceinline__ float2 cmul(float2 w, float2 x) { return make_float2(w.x * x.x - w.y * x.y, w.x * x.y + w.y * x.x); }
 
-__global__ __launch_bounds__(256) void stft_power_db_kernel(const float* __restrict__ audio,
-                                                           const long* __restrict__ offsets,
-                                                           const int* __restrict__ lengths, float* __restrict__ out,
-                                                           int n_fft, int log2n, int hop, int row_stride,
-                                                           long batch_stride, float min_db, int max_frames) {
+// The window and the twiddle factors of a work-group of THREADS threads (the caller's barrier follows).
+template <int THREADS>
+__device__ __forceinline__ void fft_tables(float2* tw, float* win, int n_fft, int tid) {
+    for (int n = tid; n < n_fft; n += THREADS) {
+        // sin^2(pi n / N), not 0.5 - 0.5 cos(2 pi n / N): the cosine next to 1 is rounded to 2^-25, which is 4e-4 of the
+        // window's value one sample from its edge -- what a frame beside digital silence or a lone click is made of
+        const float sn = sinpif((float)n / (float)n_fft);
+        win[n] = sn * sn;
+    }
+    for (int k = tid; k < n_fft / 2; k += THREADS) {
+        float sn, cs;
+        sincospif(-2.f * (float)k / (float)n_fft, &sn, &cs);
+        tw[k] = make_float2(cs, sn);
+    }
+}
+
+// The butterflies of the half-length complex transform over a wave's own buffer z (n_fft / 2 points, written in bit-reversed
+// order and made visible by the caller); the result is visible to the whole wave on return.
+__device__ __forceinline__ void wave_fft_half(float2* z, const float2* tw, int n_fft, int log2h, int lane) {
+    const int half = n_fft / 2;
+    // two radix-2 stages per pass over the buffer, the four points of a pair of butterflies held in registers (the
+    // arithmetic of the plain radix-2 recursion, half its LDS round trips and index arithmetic)
+    int s = 1;
+    for (; s + 1 <= log2h; s += 2) {
+        const int lq = s - 1, L = 1 << lq;  // quarter of the block this pass completes
+        const int st1 = n_fft >> s, st2 = n_fft >> (s + 1);
+        for (int j = lane; j < half / 4; j += 64) {
+            const int pos = j & (L - 1);
+            const int base = ((j >> lq) << (s + 1)) + pos;
+            const float2 a0 = z[base], a1 = z[base + L], a2 = z[base + 2 * L], a3 = z[base + 3 * L];
+            const float2 w1 = tw[pos * st1], w2 = tw[pos * st2], w3 = tw[(pos + L) * st2];
+            const float2 u1 = cmul(w1, a1), u3 = cmul(w1, a3);
+            const float2 b0 = make_float2(a0.x + u1.x, a0.y + u1.y), b1 = make_float2(a0.x - u1.x, a0.y - u1.y);
+            const float2 b2 = make_float2(a2.x + u3.x, a2.y + u3.y), b3 = make_float2(a2.x - u3.x, a2.y - u3.y);
+            const float2 v2 = cmul(w2, b2), v3 = cmul(w3, b3);
+            z[base] = make_float2(b0.x + v2.x, b0.y + v2.y);
+            z[base + 2 * L] = make_float2(b0.x - v2.x, b0.y - v2.y);
+            z[base + L] = make_float2(b1.x + v3.x, b1.y + v3.y);
+            z[base + 3 * L] = make_float2(b1.x - v3.x, b1.y - v3.y);
+        }
+        wave_lds_sync();
+    }
+    if (s <= log2h) {  // an odd number of stages: the last one alone
+        const int mh = 1 << (s - 1), tstep = n_fft >> s;
+        for (int j = lane; j < half / 2; j += 64) {
+            const int pos = j & (mh - 1);
+            const int i0 = ((j >> (s - 1)) << s) + pos;
+            const float2 u = z[i0], x = cmul(tw[pos * tstep], z[i0 + mh]);
+            z[i0] = make_float2(u.x + x.x, u.y + x.y);
+            z[i0 + mh] = make_float2(u.x - x.x, u.y - x.y);
+        }
+        wave_lds_sync();
+    }
+}
+
+// MODE (SL_STFT_*) picks what the split step leaves in the row; everything before it is the same for every mode, and
+// sl_stft_power_db launches the SL_STFT_POWER_LEVEL instantiation.
+template <int MODE>
+__global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ audio,
+                                                  const long* __restrict__ offsets,
+                                                  const int* __restrict__ lengths, float* __restrict__ out,
+                                                  int n_fft, int log2n, int hop, int row_stride,
+                                                  long batch_stride, float min_db, int max_frames) {
     // LDS (12 KB at n_fft = 512 -> eight work-groups = 32 waves per CU): tw float2[half] | z float2[4][half] | win float[n_fft]
     extern __shared__ float2 stft_lds[];
     const int tid = threadIdx.x;
@@ -47,17 +111,7 @@ __global__ __launch_bounds__(256) void stft_power_db_kernel(const float* __restr
     float2* zbuf = tw + half;                      // one half-length complex buffer per wave
     float* win = (float*)(zbuf + 4 * half);        // periodic Hann window
     const int log2h = log2n - 1;
-    for (int n = tid; n < n_fft; n += 256) {
-        // sin^2(pi n / N), not 0.5 - 0.5 cos(2 pi n / N): the cosine next to 1 is rounded to 2^-25, which is 4e-4 of the
-        // window's value one sample from its edge -- what a frame beside digital silence or a lone click is made of
-        const float sn = sinpif((float)n / (float)n_fft);
-        win[n] = sn * sn;
-    }
-    for (int k = tid; k < half; k += 256) {
-        float sn, cs;
-        sincospif(-2.f * (float)k / (float)n_fft, &sn, &cs);
-        tw[k] = make_float2(cs, sn);
-    }
+    fft_tables<256>(tw, win, n_fft, tid);
     __syncthreads();
     const float* y = audio + offsets[b];
     float2* z = zbuf + wave * half;
@@ -82,40 +136,9 @@ __global__ __launch_bounds__(256) void stft_power_db_kernel(const float* __restr
             z[(int)(__brev((unsigned)n) >> (32 - log2h))] = make_float2(v[0], v[1]);
         }
         wave_lds_sync();
-        // two radix-2 stages per pass over the buffer, the four points of a pair of butterflies held in registers (the
-        // arithmetic of the plain radix-2 recursion, half its LDS round trips and index arithmetic)
-        int s = 1;
-        for (; s + 1 <= log2h; s += 2) {
-            const int lq = s - 1, L = 1 << lq;  // quarter of the block this pass completes
-            const int st1 = n_fft >> s, st2 = n_fft >> (s + 1);
-            for (int j = lane; j < half / 4; j += 64) {
-                const int pos = j & (L - 1);
-                const int base = ((j >> lq) << (s + 1)) + pos;
-                const float2 a0 = z[base], a1 = z[base + L], a2 = z[base + 2 * L], a3 = z[base + 3 * L];
-                const float2 w1 = tw[pos * st1], w2 = tw[pos * st2], w3 = tw[(pos + L) * st2];
-                const float2 u1 = cmul(w1, a1), u3 = cmul(w1, a3);
-                const float2 b0 = make_float2(a0.x + u1.x, a0.y + u1.y), b1 = make_float2(a0.x - u1.x, a0.y - u1.y);
-                const float2 b2 = make_float2(a2.x + u3.x, a2.y + u3.y), b3 = make_float2(a2.x - u3.x, a2.y - u3.y);
-                const float2 v2 = cmul(w2, b2), v3 = cmul(w3, b3);
-                z[base] = make_float2(b0.x + v2.x, b0.y + v2.y);
-                z[base + 2 * L] = make_float2(b0.x - v2.x, b0.y - v2.y);
-                z[base + L] = make_float2(b1.x + v3.x, b1.y + v3.y);
-                z[base + 3 * L] = make_float2(b1.x - v3.x, b1.y - v3.y);
-            }
-            wave_lds_sync();
-        }
-        if (s <= log2h) {  // an odd number of stages: the last one alone
-            const int mh = 1 << (s - 1), tstep = n_fft >> s;
-            for (int j = lane; j < half / 2; j += 64) {
-                const int pos = j & (mh - 1);
-                const int i0 = ((j >> (s - 1)) << s) + pos;
-                const float2 u = z[i0], x = cmul(tw[pos * tstep], z[i0 + mh]);
-                z[i0] = make_float2(u.x + x.x, u.y + x.y);
-                z[i0 + mh] = make_float2(u.x - x.x, u.y - x.y);
-            }
-            wave_lds_sync();
-        }
-        for (int k = lane; k < row_stride; k += 64) {
+        wave_fft_half(z, tw, n_fft, log2h, lane);
+        for (int col = lane; col < row_stride; col += 64) {
+            const int k = MODE == SL_STFT_COMPLEX ? col >> 1 : col;  // complex rows: bin k at columns 2k (re) and 2k + 1 (im)
             float v = 0.f;
             if (k <= half) {
                 const int ka = k & (half - 1), kb = (half - k) & (half - 1);
@@ -126,12 +149,97 @@ __global__ __launch_bounds__(256) void stft_power_db_kernel(const float* __restr
                 const float2 w = k == half ? make_float2(-1.f, 0.f) : tw[ka];
                 const float xr = er + w.x * orr - w.y * oi, xi = ei + w.x * oi + w.y * orr;
                 const float pw = xr * xr + xi * xi;
+                if (MODE == SL_STFT_COMPLEX) v = (col & 1) ? xi : xr;
+                else if (MODE == SL_STFT_POWER) v = pw;
+                else if (MODE == SL_STFT_AMPLITUDE) v = sqrtf(pw);
                 // 10 log10 p = (10 / log2 10) log2 p on the native base-2 logarithm
-                v = pw == 0.f ? min_db : fmaxf(3.0102999566398120f * __log2f(pw), min_db);
+                else v = pw == 0.f ? min_db : fmaxf(3.0102999566398120f * __log2f(pw), min_db);
             }
-            row[k] = v;  // padded lanes are zero: the mel projection contracts over the padded row
+            row[col] = v;  // padded lanes are zero: the mel projection contracts over the padded row
         }
         wave_lds_sync();  // the buffer is rewritten by the wave's next frame
+    }
+}
+
+// ---- the inverse: complex rows -> audio (librosa.istft with its defaults, normalised by the summed squared window) ----------
+// A gather.  A work-group owns tile_frames * hop consecutive output samples of one utterance and inverse-transforms every frame
+// whose window touches them into LDS, one wave per frame at a time: the tile's own frames and (n_fft / 2 - 1) / hop halo frames
+// before, one more behind.  (The halo is transformed again by the neighbouring tile: at 512 / 128 that is 16 transforms for 13
+// frames of output, against atomics to HBM or a second pass over a workspace.)  A frame goes back through the forward
+// kernel's half-length transform: with E and O the spectra of its even and odd samples,
+//      E[k] = (X[k] + conj X[N/2-k]) / 2,   O[k] = e^{+2 pi i k/N} (X[k] - conj X[N/2-k]) / 2,   Z[k] = E[k] + i O[k],  k < N/2,
+// the imaginary parts of X[0] and X[N/2] taken as zero (numpy.fft.irfft ignores them), and z = conj(FFT(conj Z)) / (N/2) holds
+// x[2n] + i x[2n+1].  The frame is stored multiplied by the window.  Each thread then sums the frames that cover its samples in
+// ascending frame order, sums the squared windows in the same order, divides where that sum is a normal number and stores: the
+// value of a sample depends on its utterance's rows alone, not on the tile size, the tile it falls in or the batch.
+// LDS: tw float2[half] | win float[n_fft] | frames float[resident][n_fft];  istft_resident() sizes `resident` from 64 KiB at
+// n_fft = 1024 (14 frames) and caps it at 16 (36 KiB at 512: four work-groups per CU).  Eight waves per work-group, two frames
+// each at most: measured at 32 x 10 s, 512 / 128, 0.070 ms against 0.080 ms with four waves (the LDS footprint, not the
+// registers, limits the work-groups per CU, so the waves have to come from inside the work-group).
+constexpr int ISTFT_LDS_FLOATS = 16 * 1024;
+constexpr int ISTFT_RESIDENT_MAX = 16;
+constexpr int ISTFT_THREADS = 512;
+
+__global__ __launch_bounds__(ISTFT_THREADS) void istft_kernel(const float* __restrict__ spec, const int* __restrict__ frames,
+                                                              float* __restrict__ audio, const long* __restrict__ out_offsets,
+                                                              int n_fft, int log2n, int hop, int row_stride, long batch_stride,
+                                                              int max_frames, int tile_frames, int resident) {
+    extern __shared__ float2 istft_lds[];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y;
+    const int n_frames = min(frames[b], max_frames);
+    const long n_out = (long)hop * (n_frames - 1);  // what is left of n_fft + hop (frames - 1) without n_fft / 2 at both ends
+    const int t_own = blockIdx.x * tile_frames;
+    const long j0 = (long)t_own * hop;
+    if (j0 >= n_out) return;  // (uniform over the work-group; a single frame yields no samples)
+    const int half = n_fft / 2, log2h = log2n - 1;
+    float2* tw = istft_lds;
+    float* win = (float*)(tw + half);
+    float* fbuf = win + n_fft;
+    fft_tables<ISTFT_THREADS>(tw, win, n_fft, tid);
+    __syncthreads();
+    const int reach = (half - 1) / hop;  // frames before the tile's first that still cover its first sample
+    const int t_lo = max(t_own - reach, 0);
+    const int t_hi = min(min(t_own + tile_frames + reach, n_frames - 1), t_lo + resident - 1);  // (the host sized it: no cut)
+    const float inv = 1.f / (float)half;  // a power of two: exact
+    for (int q = wave; q <= t_hi - t_lo; q += ISTFT_THREADS / 64) {
+        const float* row = spec + (long)b * batch_stride + (long)(t_lo + q) * row_stride;
+        float2* z = (float2*)(fbuf + (long)q * n_fft);
+        for (int k = lane; k < half; k += 64) {
+            const int kb = half - k;  // 1 .. half: X[N/2 - k]
+            const float ar = row[2 * k], ai = k == 0 ? 0.f : row[2 * k + 1];
+            const float br = row[2 * kb], bi = k == 0 ? 0.f : row[2 * kb + 1];
+            const float er = 0.5f * (ar + br), ei = 0.5f * (ai - bi);
+            const float dr = 0.5f * (ar - br), di = 0.5f * (ai + bi);
+            const float2 w = tw[k];                                             // e^{-2 pi i k/N}: its conjugate multiplies D
+            const float orr = dr * w.x + di * w.y, oi = di * w.x - dr * w.y;
+            // conj Z = conj(E + i O), written in bit-reversed order
+            z[(int)(__brev((unsigned)k) >> (32 - log2h))] = make_float2(er - oi, -(ei + orr));
+        }
+        wave_lds_sync();
+        wave_fft_half(z, tw, n_fft, log2h, lane);
+        for (int n = lane; n < half; n += 64) {
+            const float2 y = z[n];
+            z[n] = make_float2(win[2 * n] * (y.x * inv), win[2 * n + 1] * (-y.y * inv));
+        }
+    }
+    __syncthreads();
+    float* y = audio + out_offsets[b];
+    const int tile = tile_frames * hop;
+    for (int i = tid; i < tile; i += ISTFT_THREADS) {
+        const long j = j0 + i;
+        if (j >= n_out) break;
+        const int p = (int)(j + half);  // index into the untrimmed buffer: frame t covers [t hop, t hop + n_fft)
+        const int ta = max(p >= n_fft ? (p - n_fft) / hop + 1 : 0, t_lo);
+        const int tb = min(p / hop, t_hi);
+        float acc = 0.f, wsum = 0.f;
+        for (int t = ta; t <= tb; ++t) {
+            const int n = p - t * hop;
+            acc += fbuf[(t - t_lo) * n_fft + n];
+            wsum += win[n] * win[n];
+        }
+        y[j] = wsum > FLT_MIN ? acc / wsum : acc;
     }
 }
 
@@ -203,24 +311,90 @@ __global__ __launch_bounds__(256) void znorm_apply_kernel(const float* __restric
     }
 }
 
+// log2 of n_fft, or -1 unless it is a power of two in [64, FFT_MAX]
+int fft_log2(int n_fft) {
+    int log2n = 0;
+    while ((1 << log2n) < n_fft && log2n < 30) ++log2n;
+    return ((1 << log2n) == n_fft && n_fft >= 64 && n_fft <= FFT_MAX) ? log2n : -1;
+}
+
+int istft_resident(int n_fft) {
+    const int fit = ISTFT_LDS_FLOATS / n_fft - 2;  // beside the twiddles and the window: n_fft floats each
+    return fit < ISTFT_RESIDENT_MAX ? fit : ISTFT_RESIDENT_MAX;
+}
+
+int stft_launch(const char* what, const float* audio, const int64_t* offsets, const int32_t* lengths, float* out, int batch,
+                int max_frames, int n_fft, int hop, int row_stride, int64_t batch_stride, int mode, float min_db,
+                void* stream) {
+    SL_CHECK_ARG(audio && offsets && lengths && out, "%s: null pointer", what);
+    SL_CHECK_ARG(batch > 0 && max_frames > 0 && hop > 0, "%s: batch, max_frames and hop must be positive", what);
+    const int log2n = fft_log2(n_fft);
+    SL_CHECK_ARG(log2n > 0, "%s: n_fft = %d must be a power of two in [64, %d]", what, n_fft, FFT_MAX);
+    SL_CHECK_ARG(mode == SL_STFT_POWER || mode == SL_STFT_AMPLITUDE || mode == SL_STFT_COMPLEX || mode == SL_STFT_POWER_LEVEL,
+                 "%s: mode = %d is none of SL_STFT_POWER, _AMPLITUDE, _COMPLEX, _POWER_LEVEL", what, mode);
+    const int columns = (mode == SL_STFT_COMPLEX ? 2 : 1) * (n_fft / 2 + 1);
+    SL_CHECK_ARG(row_stride >= columns && batch_stride >= (int64_t)max_frames * row_stride,
+                 "%s: output rows are too short for %d bins", what, n_fft / 2 + 1);
+    const size_t lds = (size_t)(n_fft / 2) * 5 * sizeof(float2) + (size_t)n_fft * sizeof(float);
+#define STFT_LAUNCH(M)                                                                                                       \
+    hipLaunchKernelGGL(stft_kernel<M>, dim3((max_frames + FRAMES_PER_WG - 1) / FRAMES_PER_WG, batch), dim3(256), lds,        \
+                       (hipStream_t)stream, audio, (const long*)offsets, lengths, out, n_fft, log2n, hop, row_stride,        \
+                       (long)batch_stride, min_db, max_frames)
+    switch (mode) {
+        case SL_STFT_POWER: STFT_LAUNCH(SL_STFT_POWER); break;
+        case SL_STFT_AMPLITUDE: STFT_LAUNCH(SL_STFT_AMPLITUDE); break;
+        case SL_STFT_COMPLEX: STFT_LAUNCH(SL_STFT_COMPLEX); break;
+        default: STFT_LAUNCH(SL_STFT_POWER_LEVEL); break;
+    }
+#undef STFT_LAUNCH
+    return sl_check_launch(what);
+}
+
 }  // namespace
 
 extern "C" int sl_stft_power_db(const float* audio, const int64_t* offsets, const int32_t* lengths, float* out, int batch,
                                 int max_frames, int n_fft, int hop, int row_stride, int64_t batch_stride, float min_db,
                                 void* stream) {
-    SL_CHECK_ARG(audio && offsets && lengths && out, "sl_stft_power_db: null pointer");
-    SL_CHECK_ARG(batch > 0 && max_frames > 0 && hop > 0, "sl_stft_power_db: batch, max_frames and hop must be positive");
-    int log2n = 0;
-    while ((1 << log2n) < n_fft) ++log2n;
-    SL_CHECK_ARG((1 << log2n) == n_fft && n_fft >= 64 && n_fft <= FFT_MAX,
-                 "sl_stft_power_db: n_fft = %d must be a power of two in [64, %d]", n_fft, FFT_MAX);
-    SL_CHECK_ARG(row_stride >= n_fft / 2 + 1 && batch_stride >= (int64_t)max_frames * row_stride,
-                 "sl_stft_power_db: output rows are too short for %d bins", n_fft / 2 + 1);
-    const size_t lds = (size_t)(n_fft / 2) * 5 * sizeof(float2) + (size_t)n_fft * sizeof(float);
-    hipLaunchKernelGGL(stft_power_db_kernel, dim3((max_frames + FRAMES_PER_WG - 1) / FRAMES_PER_WG, batch), dim3(256), lds,
-                       (hipStream_t)stream, audio, (const long*)offsets, lengths, out, n_fft, log2n, hop, row_stride,
-                       (long)batch_stride, min_db, max_frames);
-    return sl_check_launch("sl_stft_power_db");
+    return stft_launch("sl_stft_power_db", audio, offsets, lengths, out, batch, max_frames, n_fft, hop, row_stride,
+                       batch_stride, SL_STFT_POWER_LEVEL, min_db, stream);
+}
+
+extern "C" int sl_stft(const float* audio, const int64_t* offsets, const int32_t* lengths, float* out, int batch,
+                       int max_frames, int n_fft, int hop, int row_stride, int64_t batch_stride, int mode, float min_db,
+                       void* stream) {
+    return stft_launch("sl_stft", audio, offsets, lengths, out, batch, max_frames, n_fft, hop, row_stride, batch_stride, mode,
+                       min_db, stream);
+}
+
+extern "C" int sl_istft_tile_frames(int n_fft, int hop) {
+    if (fft_log2(n_fft) < 0 || hop < 1 || hop * 8 < n_fft || hop > n_fft) return 0;
+    return istft_resident(n_fft) - (2 * ((n_fft / 2 - 1) / hop) + 1);
+}
+
+extern "C" int sl_istft(const float* spec, const int32_t* frames, float* audio, const int64_t* out_offsets, int batch,
+                        int max_frames, int n_fft, int hop, int row_stride, int64_t batch_stride, void* stream) {
+    SL_CHECK_ARG(spec && frames && audio && out_offsets, "sl_istft: null pointer");
+    SL_CHECK_ARG(batch > 0 && batch <= 65535 && max_frames > 0 && hop > 0,
+                 "sl_istft: batch (at most 65535), max_frames and hop must be positive");
+    const int log2n = fft_log2(n_fft);
+    SL_CHECK_ARG(log2n > 0, "sl_istft: n_fft = %d must be a power of two in [64, %d]", n_fft, FFT_MAX);
+    SL_CHECK_ARG(row_stride >= n_fft + 2 && batch_stride >= (int64_t)max_frames * row_stride,
+                 "sl_istft: rows are too short for %d complex bins", n_fft / 2 + 1);
+    SL_CHECK_ARG((int64_t)max_frames * hop + n_fft <= INT32_MAX, "sl_istft: %d frames at hop %d do not fit 32-bit sample indices",
+                 max_frames, hop);
+    if (hop * 8 < n_fft || hop > n_fft) {
+        sl_set_error("sl_istft: hop = %d is outside [n_fft / 8, n_fft] = [%d, %d] (at most 8 overlapping frames per sample)", hop,
+                     n_fft / 8, n_fft);
+        return SL_ERR_UNSUPPORTED;
+    }
+    if (max_frames == 1) return SL_OK;  // a single frame yields no samples
+    const int resident = istft_resident(n_fft);
+    const int tile_frames = sl_istft_tile_frames(n_fft, hop);
+    const size_t lds = (size_t)(2 + resident) * n_fft * sizeof(float);
+    hipLaunchKernelGGL(istft_kernel, dim3((max_frames - 1 + tile_frames - 1) / tile_frames, batch), dim3(ISTFT_THREADS), lds,
+                       (hipStream_t)stream, spec, frames, audio, (const long*)out_offsets, n_fft, log2n, hop, row_stride,
+                       (long)batch_stride, max_frames, tile_frames, resident);
+    return sl_check_launch("sl_istft");
 }
 
 extern "C" size_t sl_z_normalize_workspace_bytes(int batch) {

@@ -13,9 +13,14 @@ Mirrors the reference's speechless/labeled_example.py: `LabeledExample` with `ge
 `SpectrogramExtractor.batch()` keeps the result in HBM as the zero-padded float32 (B, Tmax, F) batch that
 `Engine.load_input` takes (net.py:578-587's layout), so a training or prediction step on raw audio never moves a
 spectrogram over PCIe; `LabeledExample.z_normalized_transposed_spectrogram()` is the drop-in, numpy-returning form.
+
+The rest of the reference's class (labeled_example.py:17-25, 96-171) stands on two more entry points: `sl_stft`, the same
+Fourier kernel leaving |D|^2, |D| or D itself in the row (`spectrogram(type, frequency_scale)`, `spectrogram_batch`,
+`stft_batch`), and `sl_istft`, librosa.istft as a gather (`reconstructed_audio_from_spectrogram`, `istft_batch`).
 """
 import ctypes
 import logging
+from enum import Enum
 from pathlib import Path
 
 import numpy as np
@@ -25,6 +30,22 @@ from . import _lib
 from ._lib import ConvGeom, lib
 
 TIME_TILE = 256
+
+
+class SpectrogramFrequencyScale(Enum):
+    """labeled_example.py:17-19"""
+    linear = "linear"
+    mel = "mel"
+
+
+class SpectrogramType(Enum):
+    """labeled_example.py:22-25"""
+    power = "power"
+    amplitude = "amplitude"
+    power_level = "power level"
+
+
+_STFT_MODE = {SpectrogramType.power: _lib.STFT_POWER, SpectrogramType.amplitude: _lib.STFT_AMPLITUDE}
 
 
 def _round_up(x, m):
@@ -139,12 +160,7 @@ class SpectrogramExtractor:
         src, src_stride = level, self.bins_pad
         if self.mel_w is not None:
             mel = tensor("mel", (b, rows, self.mel_pad), torch.float32)
-            g = ConvGeom()
-            g.batch, g.t_out, g.taps, g.cin, g.cout = b, t_max, 1, self.bins_pad, self.mel_pad
-            g.x_row0, g.x_row_stride, g.x_batch_stride = 0, self.bins_pad, rows * self.bins_pad
-            g.y_row0, g.y_row_stride, g.y_batch_stride = 0, self.mel_pad, rows * self.mel_pad
-            self.lib.call("sl_conv1d_nt", level.data_ptr(), self.mel_w.data_ptr(), None, None, mel.data_ptr(),
-                          ctypes.byref(g), _lib.EPI_NONE, _lib.SL_F32, 0, 0, None, 0, st)
+            self._mel_project(level, mel, t_max, st)
             src, src_stride = mel, self.mel_pad
         out = tensor("out", (b, t_max, self.features), torch.float32)
         ws = tensor("ws", (self.lib.raw("sl_z_normalize_workspace_bytes")(b),), torch.uint8)
@@ -152,9 +168,95 @@ class SpectrogramExtractor:
                       src_stride, rows * src_stride, ws.data_ptr(), ws.numel(), st)
         return out, frames
 
+    def _mel_project(self, linear, mel, t_max, st):
+        """The filter bank as a 1 x 1 fp32 convolution over the first t_max rows of linear (B, rows, bins_pad) into
+        mel (B, rows, mel_pad)."""
+        b, rows = linear.shape[0], linear.shape[1]
+        g = ConvGeom()
+        g.batch, g.t_out, g.taps, g.cin, g.cout = b, t_max, 1, self.bins_pad, self.mel_pad
+        g.x_row0, g.x_row_stride, g.x_batch_stride = 0, self.bins_pad, rows * self.bins_pad
+        g.y_row0, g.y_row_stride, g.y_batch_stride = 0, self.mel_pad, rows * self.mel_pad
+        self.lib.call("sl_conv1d_nt", linear.data_ptr(), self.mel_w.data_ptr(), None, None, mel.data_ptr(), ctypes.byref(g),
+                      _lib.EPI_NONE, _lib.SL_F32, 0, 0, None, 0, st)
+
     def one(self, raw_audio):
         x, frames = self.batch([raw_audio])
         return x[0, :frames[0]].cpu().numpy()
+
+    def _to_device(self, raw_audio_list):
+        flat, offsets, lengths = self.flatten(raw_audio_list)
+        frames = [self.frame_count(int(n)) for n in lengths]
+        return [torch.from_numpy(a).to(self.device) for a in (flat, offsets, lengths)], frames
+
+    def _stft(self, dev, mode, out, max_frames, row_stride):
+        """One launch over the (flat, offsets, lengths) device tensors of _to_device into out (B, max_frames, row_stride)."""
+        flat_dev, off_dev, len_dev = dev
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        args = (flat_dev.data_ptr(), off_dev.data_ptr(), len_dev.data_ptr(), out.data_ptr(), out.shape[0], max_frames,
+                self.n_fft, self.hop, row_stride, max_frames * row_stride)
+        if mode == _lib.STFT_POWER_LEVEL:
+            self.lib.call("sl_stft_power_db", *args, self.min_decibel, st)
+        else:
+            self.lib.call("sl_stft", *args, mode, self.min_decibel, st)
+
+    def spectrogram_batch(self, raw_audio_list, type=SpectrogramType.power_level,
+                          frequency_scale=SpectrogramFrequencyScale.linear):
+        """LabeledExample.spectrogram (labeled_example.py:120-134) of a batch, time-major: (x, frames) with x float32
+        (B, Tmax, F) in HBM, zero behind short utterances; F = 1 + n_fft // 2 on the linear scale, mel_frequency_count on
+        the mel scale, where the extractor's filter bank is applied to whichever of the three spectrograms was asked for
+        (the reference projects the power LEVEL too: labeled_example.py:128-134).  Nothing is z-normalised."""
+        type, frequency_scale = SpectrogramType(type), SpectrogramFrequencyScale(frequency_scale)
+        mode = _STFT_MODE.get(type, _lib.STFT_POWER_LEVEL)
+        dev, frames = self._to_device(raw_audio_list)
+        b, t_max = len(frames), max(frames)
+        if frequency_scale == SpectrogramFrequencyScale.linear:
+            x = torch.empty((b, t_max, self.bins), dtype=torch.float32, device=self.device)
+            self._stft(dev, mode, x, t_max, self.bins)
+            return x, frames
+        if self.mel_w is None:
+            raise ValueError("this extractor was built with mel_frequency_count=None: it has no mel filter bank")
+        rows = _round_up(t_max, TIME_TILE)  # sl_conv1d_nt reads whole time tiles
+        st = torch.cuda.current_stream(self.device).cuda_stream
+        linear = torch.empty((b, rows, self.bins_pad), dtype=torch.float32, device=self.device)
+        self._stft(dev, mode, linear, rows, self.bins_pad)
+        mel = torch.empty((b, rows, self.mel_pad), dtype=torch.float32, device=self.device)
+        self._mel_project(linear, mel, t_max, st)
+        return mel[:, :t_max, :self.n_mels].contiguous(), frames
+
+    def stft_batch(self, raw_audio_list):
+        """librosa.stft of a batch, time-major: (spec, frames) with spec complex64 (B, Tmax, 1 + n_fft // 2) in HBM, zero
+        behind short utterances."""
+        dev, frames = self._to_device(raw_audio_list)
+        b, t_max = len(frames), max(frames)
+        x = torch.empty((b, t_max, self.bins, 2), dtype=torch.float32, device=self.device)
+        self._stft(dev, _lib.STFT_COMPLEX, x, t_max, 2 * self.bins)
+        return torch.view_as_complex(x), frames
+
+    def istft_batch(self, spec, frames, flat=False):
+        """librosa.istft (hop_length, win_length = n_fft) of spec complex64 (B, Tmax, 1 + n_fft // 2) in HBM, utterance b
+        over its first frames[b] rows.  Returns a list of float32 device tensors of hop * (frames[b] - 1) samples, or with
+        flat=True (flat, offsets, lengths): the utterances back to back in one float32 device tensor, int64 start
+        offsets and int32 sample counts on the host -- the layout of flatten()."""
+        if spec.dtype != torch.complex64 or spec.dim() != 3 or spec.shape[2] != self.bins or len(frames) != spec.shape[0]:
+            raise ValueError("spec must be complex64 (B, Tmax, {}) with one frame count per utterance".format(self.bins))
+        frames = [int(n) for n in frames]
+        if min(frames) < 1 or max(frames) > spec.shape[1]:
+            raise ValueError("frame counts must lie in [1, {}]".format(spec.shape[1]))
+        spec = spec.to(self.device).contiguous()
+        rows = torch.view_as_real(spec)
+        lengths = np.array([self.hop * (n - 1) for n in frames], dtype=np.int32)
+        offsets = np.zeros(len(frames), dtype=np.int64)
+        offsets[1:] = np.cumsum(lengths[:-1])
+        out = torch.empty((max(int(lengths.sum()), 1),), dtype=torch.float32, device=self.device)  # (every sample is written)
+        frames_dev = torch.tensor(frames, dtype=torch.int32, device=self.device)
+        off_dev = torch.from_numpy(offsets).to(self.device)
+        self.lib.call("sl_istft", rows.data_ptr(), frames_dev.data_ptr(), out.data_ptr(), off_dev.data_ptr(), len(frames),
+                      spec.shape[1], self.n_fft, self.hop, 2 * self.bins, spec.shape[1] * 2 * self.bins,
+                      torch.cuda.current_stream(self.device).cuda_stream)
+        out = out[:int(lengths.sum())]
+        if flat:
+            return out, offsets, lengths
+        return [out[o:o + n] for o, n in zip(offsets, lengths)]
 
 
 _EXTRACTORS = {}
@@ -186,10 +288,43 @@ class LabeledExample:
         self.positional_label = positional_label
         self._device = device
 
+    def _extractor(self):
+        return shared_extractor(self.sample_rate, self.fourier_window_length, self.hop_length, self.mel_frequency_count,
+                                self._device)
+
     def z_normalized_transposed_spectrogram(self):
-        extractor = shared_extractor(self.sample_rate, self.fourier_window_length, self.hop_length,
-                                     self.mel_frequency_count, self._device)
-        return extractor.one(self.get_raw_audio())
+        return self._extractor().one(self.get_raw_audio())
+
+    def spectrogram(self, type=SpectrogramType.power_level, frequency_scale=SpectrogramFrequencyScale.linear):
+        """float32 ndarray (frequencies, frames): labeled_example.py:120-134."""
+        x, _ = self._extractor().spectrogram_batch([self.get_raw_audio()], type, frequency_scale)
+        return x[0].cpu().numpy().T
+
+    def reconstructed_audio_from_spectrogram(self):
+        """librosa.istft of the complex spectrogram (labeled_example.py:162-164): hop_length * (len // hop_length) samples."""
+        extractor = self._extractor()
+        spec, frames = extractor.stft_batch([self.get_raw_audio()])
+        return extractor.istft_batch(spec, frames)[0].cpu().numpy()
+
+    def tag_count(self, tag):
+        return self.label_with_tags.count(tag)
+
+    def mel_frequencies(self):
+        """The mel_frequency_count + 2 band edges of the filter bank in Hz: librosa.mel_frequencies(n + 2, fmax=sr / 2)."""
+        return _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(self.sample_rate / 2), self.mel_frequency_count + 2))
+
+    def highest_detectable_frequency(self):
+        return self.sample_rate / 2
+
+    def frequency_count_from_spectrogram(self, spectrogram):
+        return spectrogram.shape[0]
+
+    def time_step_count(self):
+        """The frame count of spectrogram(): 1 + samples // hop_length (no launch is needed to know it)."""
+        return 1 + len(self.get_raw_audio()) // self.hop_length
+
+    def time_step_rate(self):
+        return self.time_step_count() / self.duration_in_s
 
     @property
     def duration_in_s(self):
