@@ -412,6 +412,43 @@ int sl_ctc_segment_scores(const float* logq, const int32_t* labels, const int32_
                           float* log_posterior, int batch, int t_out, int k, int l_max, int n_segments, int seg_l_max,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- CTC phrase search (keyword / phrase spotting): where in an utterance a phrase is said, and how well.  One launch searches
+ *      any number of queries, each a phrase of up to 511 letters in one utterance of the batch: a Viterbi search over the
+ *      phrase's CTC states in which every frame may open a new occurrence at no cost.  A begin-frame tag travels with every
+ *      score, so there are no backpointers and no backtrace.  No reference counterpart. ---
+ * logq: float[B][t_out][k] and input_len: as the aligners take them; blank = k-1; T_b = input_len[b] clamped into [0, t_out].
+ * queries: int32[n_queries][q_max], query_len[n_queries], query_utt[n_queries] (the utterance b a query is searched in); L =
+ * query_len clamped into [0, q_max].  A letter's emission column is clamped into [0, k) as the aligners clamp it; the skip rule
+ * compares the letters as given.  min_score: float[n_queries].
+ * Limits: 1 < k <= 64, 1 <= q_max <= 511, 1 <= max_hits <= 64, n_queries >= 1: SL_ERR_UNSUPPORTED otherwise.  A null pointer
+ * (frame_score and frame_begin may be null) or batch, t_out <= 0 is SL_ERR_INVALID_ARGUMENT, a workspace below the size asked
+ * for SL_ERR_WORKSPACE_TOO_SMALL; all of these are refused on the host before any launch, in this order.
+ * Every operation is an exact compare or ONE fp32 add (no multiply, nothing to contract), so a float32 restatement of the
+ * following reproduces every output bit for bit:
+ *   states s in [0, 2L-1): even s letter s/2, odd s the blank between two letters.  No leading and no trailing blank: a span
+ *   starts and ends on a letter frame.
+ *   Before frame 0 every state is -inf.  A filler below state 0 has score 0 at every frame.
+ *   delta_t(s) = max(candidates) + logq_t(col(s)) for 0 <= t < T_b; the candidates, in order: stay delta_{t-1}(s);
+ *   delta_{t-1}(s-1), which for s = 0 is the filler's 0; delta_{t-1}(s-2), only for an even s >= 2 whose letter differs from
+ *   the letter before it.  A later candidate replaces an earlier one only by strict >, so ties go to the earlier.
+ *   beg_t(s) = the tag of the winning candidate; entering from the filler sets it to t; a state at -inf has tag -1.
+ * Per-frame outputs (optional): frame_score[q][t] = delta_t(2L-2), frame_begin[q][t] = beg_t(2L-2): the best occurrence that
+ * ends at frame t covers the frames [frame_begin, t].  For t >= T_b, for L = 0 and for query_utt outside [0, B): -inf / -1.
+ * Hit picking, on the device in the same launch; repeat up to max_hits times: among the frames not yet suppressed with
+ * frame_score > -inf and frame_score >= min_score[q] take the largest score, on equal scores the smallest t; emit hit =
+ * {frame_begin[t], t+1} (half-open) with that score; suppress every frame u whose span [frame_begin[u], u] intersects
+ * [frame_begin[t], t].  Outputs: hits int32[n_queries][max_hits][2], hit_score float[n_queries][max_hits], n_hits
+ * int32[n_queries]; unused slots hold -1 / -inf.  Hits never overlap and their scores never increase.  NaN in logq is outside
+ * the contract.
+ * workspace: sl_ctc_spot_workspace_bytes(n_queries, t_out, q_max) bytes = n_queries * t_out * 8 (every query's per-frame score and
+ * begin, which the picking reads whether frame_score / frame_begin are given or not): monotonic, 0 for arguments out of range;
+ * t_out is limited by memory only.  One wave per query; 2 / 4 / 8 / 16 states per lane for q_max <= 63 / 127 / 255 / 511. */
+size_t sl_ctc_spot_workspace_bytes(int n_queries, int t_out, int q_max);
+int sl_ctc_spot(const float* logq, const int32_t* input_len, const int32_t* queries, const int32_t* query_len,
+                const int32_t* query_utt, const float* min_score, int32_t* hits, float* hit_score, int32_t* n_hits,
+                float* frame_score, int32_t* frame_begin, int batch, int t_out, int k, int n_queries, int q_max, int max_hits,
+                void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- ASG criterion (auto segmentation criterion of the wav2letter paper, arXiv:1609.03193).  No reference counterpart:
  *      the reference raises NotImplementedError where its ASG loss would be (speechless/net.py:397-399). ----------------------
  * K = k letters and NO blank.  trans: float[k][k], trans[i*k + j] = g(i, j) = the score of moving from letter i to letter

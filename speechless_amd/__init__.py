@@ -12,7 +12,7 @@ def __getattr__(name):
         from . import net
         return getattr(net, name)
     if name in ("PositionalLabel", "CtcAlignment", "AsgAlignment", "cut_sections", "cut_section_spans", "word_spans",
-                "WordConfidence", "ScoredAlignment", "grapheme_spans", "cut_section_grapheme_spans"):
+                "WordConfidence", "ScoredAlignment", "grapheme_spans", "cut_section_grapheme_spans", "PhraseHit"):
         from . import alignment
         return getattr(alignment, name)
     if name == "window_plan":

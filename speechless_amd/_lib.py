@@ -158,6 +158,11 @@ SIGNATURES = {
     # logq, labels, input_len, segments, log_posterior, batch, t_out, k, l_max, n_segments, seg_l_max, workspace, bytes, stream
     "sl_ctc_segment_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_void_p, c_size_t, c_void_p]),
+    "sl_ctc_spot_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    # logq, input_len, queries, query_len, query_utt, min_score, hits, hit_score, n_hits, frame_score, frame_begin, batch, t_out,
+    # k, n_queries, q_max, max_hits, workspace, bytes, stream
+    "sl_ctc_spot": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "sl_asg_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     # probs, logq, trans, init, labels, label_len, input_len, loss, dlogits, dtrans, dinit; then sl_ctc_loss_grad's tail
     "sl_asg_loss_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -7,7 +7,9 @@ utterance's Viterbi alignment (include/speechless_hip.h, sl_ctc_align) turned in
 `AsgAlignment` is the same for the ASG criterion (sl_asg_align / sl_asg_align_long), whose path runs over the run-length-encoded label.
 `ScoredAlignment` adds the confidences of sl_ctc_segment_scores to a `CtcAlignment` (Wav2Letter.word_confidence_batch /
 predict_with_confidence_batch / confidence_of_recording), or those of sl_asg_segment_scores to an `AsgAlignment` (the asg_ methods
-of the same names): a `WordConfidence` per word and the posterior of the whole label."""
+of the same names): a `WordConfidence` per word and the posterior of the whole label.
+`PhraseHit` is one occurrence of a phrase that the phrase search found (sl_ctc_spot; Wav2Letter.find_phrases_batch /
+find_phrases_in_recording)."""
 from typing import Callable, List, Optional, Tuple
 
 import numpy as np
@@ -198,6 +200,37 @@ class ScoredAlignment:
 
     def __repr__(self):
         return "ScoredAlignment({!r}, log_posterior={}, words={})".format(self.label, self.log_posterior, self.words)
+
+
+class PhraseHit:
+    """One occurrence of a phrase found by the phrase search (sl_ctc_spot; Wav2Letter.find_phrases_batch /
+    find_phrases_in_recording): its output frames [first, end) -- the first and the last of them frames of a letter --, the
+    log-probability of its best path over those frames, and the log of its segment posterior: the probability that those frames,
+    read on their own, say exactly the phrase (sl_ctc_segment_scores; nan where it was not asked for)."""
+
+    def __init__(self, phrase: str, first: int, end: int, log_probability: float, log_posterior: float = float("nan")):
+        self.phrase = phrase
+        self.first = int(first)
+        self.end = int(end)
+        self.log_probability = float(log_probability)
+        self.log_posterior = float(log_posterior)
+
+    def confidence(self) -> float:
+        """the segment posterior as a probability; nan without one"""
+        return float(np.exp(self.log_posterior))
+
+    def seconds(self, seconds_per_frame: float) -> Tuple[float, float]:
+        """(start, end) in seconds, where one OUTPUT frame lasts seconds_per_frame"""
+        return self.first * float(seconds_per_frame), self.end * float(seconds_per_frame)
+
+    def __eq__(self, other):
+        return isinstance(other, PhraseHit) and (self.phrase, self.first, self.end, self.log_probability) == \
+            (other.phrase, other.first, other.end, other.log_probability) and \
+            (self.log_posterior == other.log_posterior or (np.isnan(self.log_posterior) and np.isnan(other.log_posterior)))
+
+    def __repr__(self):
+        return "PhraseHit({!r}, ({}, {}), log_probability={:.4f}, confidence={:.4f})".format(
+            self.phrase, self.first, self.end, self.log_probability, self.confidence())
 
 
 def _characters_per_grapheme(label: str) -> List[Tuple[int, bool]]:

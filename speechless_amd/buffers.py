@@ -53,6 +53,7 @@ class _Buffers:
         self.g = [None] * n  # allocated lazily by ensure_backward()
         self.align = None  # _AlignBuffers of Engine.ctc_align / asg_align (frames = tt_pad), on first use
         self.segment = None  # _SegmentBuffers of Engine.ctc_ / asg_segment_scores, on first use
+        self.spot = None  # _SpotBuffers of Engine.ctc_spot, on first use
         self.asg_score = self.asg_vit_ws = None  # (B,) result and workspace of Engine.asg_viterbi, on first use
         self.error_counts = self.edit_rows = None  # allocated lazily by ensure_error_counts() / ensure_edit_rows()
         self.decoded_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
@@ -443,4 +444,36 @@ class _SegmentBuffers:
             self.out = torch.zeros((n_segments,), dtype=torch.float32, device=dev)
         need = lib().raw(self.workspace_query)(n_segments, seg_l_max, *self.query_tail)
         if self.ws is None or self.ws.numel() < need:
+            self.ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+
+
+class _SpotBuffers:
+    """Tensors of Engine.ctc_spot and ctc_spot_long (engine_decode.py): the (N, q_max) queries with their lengths, utterances
+    and thresholds, the input lengths of a logq tensor handed to the _long method, the hits with their scores and counts, and the
+    workspace whose size sl_ctc_spot_workspace_bytes(n_queries, frames, q_max) states: 8 bytes per query and frame.
+    _Buffers.spot serves a buffer set, Engine._long_spot a logq tensor handed over.  Grown only."""
+
+    def __init__(self, device):
+        self.device = device
+        self.input_len = self.queries = self.query_len = self.query_utt = self.min_score = None
+        self.hits = self.hit_score = self.n_hits = self.ws = None
+
+    def ensure(self, batch, frames, n_queries, q_max, max_hits):
+        """room for n_queries queries of up to q_max letters with max_hits hits each over `batch` rows of `frames` frames"""
+        dev = self.device
+        if self.input_len is None or self.input_len.shape[0] != batch:
+            self.input_len = torch.zeros((batch,), dtype=torch.int32, device=dev)
+        if self.queries is None or self.queries.shape[0] < n_queries or self.queries.shape[1] < q_max:
+            self.queries = torch.zeros((n_queries, q_max), dtype=torch.int32, device=dev)
+            self.query_len = torch.zeros((n_queries,), dtype=torch.int32, device=dev)
+            self.query_utt = torch.zeros((n_queries,), dtype=torch.int32, device=dev)
+            self.min_score = torch.zeros((n_queries,), dtype=torch.float32, device=dev)
+            self.n_hits = torch.zeros((n_queries,), dtype=torch.int32, device=dev)
+            self.hits = None
+        if self.hits is None or self.hits.numel() < n_queries * max_hits * 2:
+            self.hits = torch.zeros((n_queries * max_hits * 2,), dtype=torch.int32, device=dev)
+            self.hit_score = torch.zeros((n_queries * max_hits,), dtype=torch.float32, device=dev)
+        need = lib().raw("sl_ctc_spot_workspace_bytes")(n_queries, frames, self.queries.shape[1])  # (the launch states their width)
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = None  # (free the old one first: a thousand queries over a long recording take hundreds of megabytes)
             self.ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)

@@ -12,7 +12,7 @@ HOST_LIB_PATH = PACKAGE_DIR / "libspeechless_host.so"  # plain C++ helpers of th
 HOST_SOURCES = [PACKAGE_DIR / "csrc_host" / "pack_batch.cpp", PACKAGE_DIR / "csrc_host" / "beam_search.cpp"]
 CXX = os.environ.get("CXX", "g++")
 SOURCES = ["capi.hip", "conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_f32.hip", "ctc.hip", "ctc_long.hip", "misc.hip", "optimizer.hip", "spectrogram.hip", "conv_chain_bf16.hip",
-           "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip", "ctc_segment.hip",
+           "conv1x1_bwd_bf16.hip", "split3.hip", "ctc_align.hip", "ctc_align_long.hip", "ctc_segment.hip", "ctc_spot.hip",
            "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
            "asg_segment.hip", "resample.hip"]
 # translation units built a SECOND time from the same source with -DSL_ELEM_F16: the NT / TN kernels on v_mfma_*_f16 for the
@@ -53,9 +53,11 @@ def _newest_source_mtime():
 # arrays indexed by unrolled constants; scratch there is memory traffic on the per-frame sequential path of a lone wave)
 # (asg_segment.hip: up to 8 label states in doubles with their two scores each, and a chunk of staged emissions per lane, are
 # register arrays indexed by unrolled constants; scratch there is memory traffic on the per-frame sequential path of either wave)
+# (ctc_spot.hip: up to 16 lattice states with a begin tag each, their columns and a chunk of staged emissions per lane are register
+# arrays indexed by unrolled constants; scratch there is memory traffic on the per-frame sequential path of a lone wave)
 NO_SCRATCH = {"resample.hip","conv_nt_bf16.hip", "wgrad_tn_bf16.hip", "conv_chain_bf16.hip", "conv1x1_bwd_bf16.hip", "ctc_align.hip",
               "ctc_align_long.hip", "ctc_beam.hip", "output_softmax_bf16.hip", "edit_distance.hip", "asg.hip", "asg_align.hip", "asg_align_long.hip", "asg_beam.hip",
-              "ctc_long.hip", "ctc_segment.hip", "asg_segment.hip"}
+              "ctc_long.hip", "ctc_segment.hip", "asg_segment.hip", "ctc_spot.hip"}
 
 
 def _scratch_users(remarks):
@@ -77,9 +79,10 @@ def _scratch_users(remarks):
 # asg_align.hip: every add of the recurrence is rounded on its own (it has no multiply; the flag states the contract)
 # asg_align_long.hip: the same three separately rounded adds, bit for bit what asg_align.hip returns
 # asg_beam.hip: lm_weight * delta is rounded before it is added (sl_asg_beam_search is defined bit for bit)
+# ctc_spot.hip: one rounded add per state and frame (it has no multiply; the flag states the contract)
 FILE_FLAGS = {"ctc.hip": ["-fno-slp-vectorize"], "ctc_beam.hip": ["-ffp-contract=off"], "asg_align.hip": ["-ffp-contract=off"],
               "asg_align_long.hip": ["-ffp-contract=off"],
-              "asg_beam.hip": ["-ffp-contract=off"]}
+              "asg_beam.hip": ["-ffp-contract=off"], "ctc_spot.hip": ["-ffp-contract=off"]}
 
 
 def _compile(unit):

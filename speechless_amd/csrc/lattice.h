@@ -1,5 +1,5 @@
 // lattice.h -- what the lattice kernels that keep their states in registers share (ctc_align.hip, ctc_align_long.hip, asg.hip,
-// asg_align.hip, asg_align_long.hip, ctc_segment.hip, asg_segment.hip):
+// asg_align.hip, asg_align_long.hip, ctc_segment.hip, asg_segment.hip, ctc_spot.hip):
 //   - the clamps of lengths and labels, and the neighbour-lane move;
 //   - the windows of whole backpointer rows that a one-wave backtrace pulls from HBM into LDS (load_window / store_window),
 //     and the bands of them that a long aligner's backtrace pulls (load_band / store_band);
@@ -7,7 +7,8 @@
 //     thread and their frame step (ctc_states_init / ctc_frame), the ASG ones (asg_states_init / asg_frame), and the stager of
 //     their emissions (EmissionStager, ALIGN_CH);
 //   - for the segment posteriors (ctc_segment.hip, asg_segment.hip), the SUMMING frame steps over the same states
-//     (ctc_frame_sum, asg_frame_sum), in doubles.
+//     (ctc_frame_sum, asg_frame_sum), in doubles;
+//   - for the phrase search (ctc_spot.hip), the frame step that carries a begin-frame tag with every score (ctc_spot_frame).
 // No helper here holds a barrier, a fence or a return: those stay in the kernels, next to the argument for their uniformity.
 #pragma once
 #include "common.h"
@@ -25,6 +26,10 @@ __device__ __forceinline__ void clamp_lengths(const int32_t* label_len, const in
 
 __device__ __forceinline__ float dpp_float_from_lower_lane(float v, float lane0_value) {  // lane l <- lane l-1
     return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(lane0_value), __float_as_int(v), 0x138, 0xf, 0xf, false));
+}
+
+__device__ __forceinline__ int dpp_int_from_lower_lane(int v, int lane0_value) {  // the same move of an integer
+    return __builtin_amdgcn_update_dpp(lane0_value, v, 0x138, 0xf, 0xf, false);
 }
 
 __device__ __forceinline__ double dpp_double_from_lower_lane(double v, double lane0_value) {  // the same move, both halves
@@ -141,6 +146,37 @@ __device__ __forceinline__ uint32_t ctc_frame(const int (&col)[NJ / 2], const bo
         word |= bp << (2 * j);
     }
     return word;
+}
+// The same frame with a begin-frame TAG in place of the backpointer, for the phrase search of sl_ctc_spot (ctc_spot.hip): g[] the
+// tag of each score, lo1g the tag of lo1.  The winning candidate's tag travels with its score (one compare-select more per
+// candidate), and a state that ends the frame at -inf has tag -1.  The same strict > in the same order, then ONE rounded add.
+template <int NJ>
+__device__ __forceinline__ void ctc_spot_frame(const int (&col)[NJ / 2], const bool (&skip)[NJ / 2], float (&d)[NJ], int (&g)[NJ],
+                                               const float* e, float eb, float lo1, int lo1g) {
+#pragma unroll
+    for (int j = NJ - 1; j >= 0; --j) {  // descending: d[j-1], d[j-2] and their tags still hold frame t-1
+        const float p1 = j >= 1 ? d[j - 1] : lo1;
+        const int g1 = j >= 1 ? g[j - 1] : lo1g;
+        float best = d[j];
+        int tag = g[j];
+        if (p1 > best) {
+            best = p1;
+            tag = g1;
+        }
+        if (j & 1) {
+            const float p2 = j >= 2 ? d[j - 2] : lo1;
+            const int g2 = j >= 2 ? g[j - 2] : lo1g;
+            if (skip[j >> 1] && p2 > best) {
+                best = p2;
+                tag = g2;
+            }
+            best += e[col[j >> 1]];
+        } else {
+            best += eb;
+        }
+        d[j] = best;
+        g[j] = best == -INFINITY ? -1 : tag;
+    }
 }
 // The same frame with the SUM in place of the max, for the forward (alpha) lattice of sl_ctc_segment_scores: d[] in doubles and
 // log2 units, a(s) = log2(2^a(s) + 2^a(s-1) [+ 2^a(s-2) where the state may be entered from s-2]) + logq(label(s)) * log2(e),

@@ -220,6 +220,7 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
         self._long_align = None  # buffers._AlignBuffers of ctc_align_long / asg_align_long, on first use
         self._long_viterbi = None  # buffers._AlignBuffers of asg_viterbi_long, on first use
         self._long_segment = None  # buffers._SegmentBuffers of ctc_ / asg_segment_scores_long, on first use
+        self._long_spot = None  # buffers._SpotBuffers of ctc_spot_long, on first use
         self.timeline = None
         self.kernel_timeline = None  # (set of tags, list of (tag, start, stop)): see _around
         self._side_stream = None

@@ -1,14 +1,15 @@
 """What runs on the probabilities behind forward() outside the training step: greedy / Viterbi / beam decoding, the four forced
-aligners, the CTC and ASG segment posteriors, long recordings (longform.py) and the error counts.  One host path each: the aligners
-differ by a row of _ALIGNERS, their label batches pass check_label_batch, their tensors live in buffers._AlignBuffers (the
-segment posteriors differ by a row of _SEGMENTERS, theirs live in _SegmentBuffers).  Methods of Engine."""
+aligners, the CTC and ASG segment posteriors, the CTC phrase search, long recordings (longform.py) and the error counts.  One host
+path each: the aligners differ by a row of _ALIGNERS, their label batches pass check_label_batch, their tensors live in
+buffers._AlignBuffers (the segment posteriors differ by a row of _SEGMENTERS, theirs live in _SegmentBuffers; the phrase search's
+queries pass check_queries, its tensors live in _SpotBuffers).  Methods of Engine."""
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import longform
-from .buffers import _AlignBuffers, _SegmentBuffers
+from .buffers import _AlignBuffers, _SegmentBuffers, _SpotBuffers
 from .error_counts import host_counts, pack_rows
 
 
@@ -48,6 +49,7 @@ _SEGMENTERS = {
     "ctc": _Segmenter("sl_ctc_segment_scores", "segment_scores", False, longform.SEGMENT_MAX_LABEL, "letters"),
     "asg": _Segmenter("sl_asg_segment_scores", "asg_segment_scores", True, longform.ASG_SEGMENT_MAX_LABEL, "graphemes"),
 }
+_SPOT = "sl_ctc_spot"
 _VITERBI = "sl_asg_viterbi"
 _GREEDY = "sl_greedy_decode"
 
@@ -95,6 +97,38 @@ def check_segments(segments, batch, kind="ctc"):
         raise ValueError("segment {0} = {1}: need b in [0, {2}), 0 <= begin <= end for frames and {4}, and at most {3} {4} "
                          "({5})".format(i, seg[i].tolist(), batch, row.max_label, row.unit, row.entry))
     return np.ascontiguousarray(seg, dtype=np.int32)
+
+
+def check_queries(queries, lengths, utterances, min_scores, max_hits, batch, n_labels):
+    """What the engine asks of the queries of ctc_spot, on the host: (N, Qmax) integers with N >= 1 and 1 <= Qmax <=
+    longform.SPOT_MAX_PHRASE, N lengths in [1, Qmax], N utterances in [0, batch), N thresholds that are no NaN, every index of row
+    i below lengths[i] in [0, n_labels), and 1 <= max_hits <= longform.SPOT_MAX_HITS; the first query that breaks a rule is
+    named.  Returns (queries, lengths, utterances int32, thresholds float32, max_hits int), contiguous numpy."""
+    q = np.asarray(queries)
+    if q.ndim != 2 or q.shape[0] < 1 or q.shape[1] < 1 or not np.issubdtype(q.dtype, np.integer):
+        raise ValueError("queries must be an (N, Qmax) integer array, N >= 1 and Qmax >= 1")
+    if q.shape[1] > longform.SPOT_MAX_PHRASE:
+        raise ValueError("queries of {} letters: the phrase search takes at most {} ({})".format(
+            q.shape[1], longform.SPOT_MAX_PHRASE, _SPOT))
+    n = q.shape[0]
+    length = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    utt = np.asarray(utterances, dtype=np.int64).reshape(-1)
+    thresholds = np.asarray(min_scores, dtype=np.float32).reshape(-1)
+    if length.shape[0] != n or utt.shape[0] != n or thresholds.shape[0] != n:
+        raise ValueError("queries must come with N lengths, N utterances and N thresholds")
+    if not 1 <= int(max_hits) <= longform.SPOT_MAX_HITS:
+        raise ValueError("max_hits = {} outside [1, {}] ({})".format(max_hits, longform.SPOT_MAX_HITS, _SPOT))
+    bad = (length < 1) | (length > q.shape[1]) | (utt < 0) | (utt >= batch) | np.isnan(thresholds)
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError("query {}: length {}, utterance {}, threshold {}: need a length in [1, {}], an utterance in [0, {}) and a "
+                         "threshold that is a number".format(i, length[i], utt[i], thresholds[i], q.shape[1], batch))
+    for i in range(n):
+        row = q[i, :length[i]]
+        if row.min() < 0 or row.max() >= n_labels:
+            raise ValueError("query {} holds an index outside [0, {}) (blank is {})".format(i, n_labels, n_labels))
+    return (np.ascontiguousarray(q, dtype=np.int32), length.astype(np.int32), utt.astype(np.int32),
+            np.ascontiguousarray(thresholds), int(max_hits))
 
 
 def _merge_repeats(paths):
@@ -341,6 +375,68 @@ class DecodeAlignMixin:
         """asg_segment_scores() on a given (B, T', K) fp32 logq tensor in HBM (forward_long's) with its B prediction lengths:
         one launch whatever the number of segments.  Does not touch the current buffer set."""
         return self._segment_scores("asg", True, logq, label_batch, prediction_lengths, segments)
+
+    # ------------------------------------------------------------------ phrase search
+
+    def _spot(self, long, logq, queries, query_lengths, query_utterances, min_scores, max_hits, prediction_lengths):
+        """sl_ctc_spot over the current buffer set's logq with its input lengths (tensors: buf.spot), or -- long -- over a given
+        logq with its prediction lengths (tensors: _long_spot).  Checks in _segment_scores' order: the criterion, logq (long),
+        the queries.  Returns (hits int32 (N, max_hits, 2), scores float32 (N, max_hits), counts int32 (N,)) numpy."""
+        tag = "spot_long" if long else "spot"
+        if self.criterion == "asg":
+            raise ValueError("criterion='asg': the phrase search runs over the CTC lattice (blank = K - 1); not supported")
+        k = self.grapheme_set_size
+        if long:
+            buf, in_len = None, np.asarray(prediction_lengths, dtype=np.int32).reshape(-1)
+            logq, batch, t_out = self._long_logq(logq)
+            if in_len.shape[0] != batch:
+                raise ValueError("ctc_spot_long needs B prediction lengths")
+        else:
+            buf = self.cur
+            logq, batch, t_out = buf.logq, buf.batch, buf.t_out
+        queries, lengths, utterances, thresholds, max_hits = check_queries(queries, query_lengths, query_utterances, min_scores,
+                                                                           max_hits, batch, k - 1)
+        n, q_max = queries.shape
+        if long:
+            sp = self._long_spot = self._long_spot or _SpotBuffers(self.device)
+        else:
+            sp = buf.spot = buf.spot or _SpotBuffers(self.device)
+        sp.ensure(batch, t_out, n, q_max, max_hits)
+        sp.queries.zero_()  # (at least as wide as the queries)
+        sp.queries[:n, :q_max].copy_(torch.from_numpy(queries))
+        sp.query_len[:n].copy_(torch.from_numpy(lengths))
+        sp.query_utt[:n].copy_(torch.from_numpy(utterances))
+        sp.min_score[:n].copy_(torch.from_numpy(thresholds))
+        if long:
+            lens = sp.input_len
+            lens.copy_(torch.from_numpy(in_len))
+        else:
+            if prediction_lengths is not None:
+                self.set_input_lengths(prediction_lengths)
+            lens = buf.input_len
+        self._launch(tag, _SPOT, logq.data_ptr(), lens.data_ptr(), sp.queries.data_ptr(), sp.query_len.data_ptr(),
+                     sp.query_utt.data_ptr(), sp.min_score.data_ptr(), sp.hits.data_ptr(), sp.hit_score.data_ptr(),
+                     sp.n_hits.data_ptr(), None, None, batch, t_out, k, n, sp.queries.shape[1], max_hits, sp.ws.data_ptr(),
+                     sp.ws.numel(), self._stream())
+        return (sp.hits[:n * max_hits * 2].view(n, max_hits, 2).cpu().numpy(), sp.hit_score[:n * max_hits].view(n, max_hits).cpu().numpy(),
+                sp.n_hits[:n].cpu().numpy())
+
+    def ctc_spot(self, queries, query_lengths, query_utterances, min_scores, max_hits, prediction_lengths=None):
+        """CTC phrase search on the current buffer set's logq after forward(): where each query -- row i of queries (int (N,
+        Qmax), padded with anything), its first query_lengths[i] letters -- is said in utterance query_utterances[i], under the
+        input lengths of the last set_input_lengths (or prediction_lengths, which sets them).  Up to max_hits (1 .. 64)
+        occurrences per query that do not overlap, best first, each with the log-probability of its best path of at least
+        min_scores[i] (-inf: any finite score).  Returns (hits int32 (N, max_hits, 2) numpy: output frames [first, end), -1 in
+        unused slots; scores float32 (N, max_hits) numpy, -inf there; counts int32 (N,) numpy).  Semantics: the entry point
+        sl_ctc_spot of include/speechless_hip.h.  Uses tensors of its own, reused across calls; one launch whatever the number of
+        queries, outside every recorded launch list."""
+        return self._spot(False, None, queries, query_lengths, query_utterances, min_scores, max_hits, prediction_lengths)
+
+    def ctc_spot_long(self, logq, queries, query_lengths, query_utterances, min_scores, max_hits, prediction_lengths):
+        """ctc_spot() on a given (B, T', K) fp32 logq tensor in HBM (forward_long's) with its B prediction lengths: one launch
+        whatever the number of queries and frames (the workspace takes 8 bytes per query and frame).  Does not touch the current
+        buffer set."""
+        return self._spot(True, logq, queries, query_lengths, query_utterances, min_scores, max_hits, prediction_lengths)
 
     # ------------------------------------------------------------------ long recordings (longform.py)
 

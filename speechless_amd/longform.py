@@ -15,6 +15,8 @@ ASG_ALIGN_MAX_LABEL = 8191        # sl_asg_align_long: ENCODED graphemes per lab
 CTC_LOSS_MAX_LABEL = 2047         # sl_ctc_loss_grad: letters per label (4095 lattice states; two lattices in doubles per utterance)
 SEGMENT_MAX_LABEL = 511           # sl_ctc_segment_scores: letters per SEGMENT (1023 lattice states in one wave's registers)
 ASG_SEGMENT_MAX_LABEL = 511       # sl_asg_segment_scores: ENCODED graphemes per SEGMENT (8 states per lane of one wave)
+SPOT_MAX_PHRASE = 511             # sl_ctc_spot: letters per phrase (the filler and 1021 lattice states in one wave's registers)
+SPOT_MAX_HITS = 64                # sl_ctc_spot: hits per query (one lane per hit slot)
 GREEDY_DECODE_MAX_FRAMES = 38144  # sl_greedy_decode: output frames per recording ((t_out + 256) ints in 150 KB of LDS)
 
 

@@ -1042,6 +1042,91 @@ class Wav2Letter:
         encoded graphemes than that raises a ValueError: lower max_section_frames."""
         return self._confidence_of_recording("asg", example, max_section_frames, window_input_frames)
 
+    # ------------------------------------------------------------------ phrase search (extension; alignment.PhraseHit)
+    def _encoded_phrases(self, phrases, method):
+        """the phrases of find_phrases_batch / find_phrases_in_recording, checked and encoded -> int32 (P, Qmax) padded with -1"""
+        from . import longform
+        self._require_alignment_kind("ctc", method, "PhraseHit")
+        phrases = list(phrases)
+        if not phrases:
+            raise ValueError("{}: no phrases to search for".format(method))
+        for phrase in phrases:
+            if not isinstance(phrase, str) or not phrase:
+                raise ValueError("{}: an empty phrase cannot be searched for".format(method))
+            if len(phrase) > longform.SPOT_MAX_PHRASE:
+                raise ValueError("{}: a phrase of {} letters: the phrase search takes at most {} (sl_ctc_spot)".format(
+                    method, len(phrase), longform.SPOT_MAX_PHRASE))
+        return phrases, self.grapheme_encoding.encode_label_batch(phrases)
+
+    def _find_phrases(self, engine, logq, frames, phrases, encoded, max_hits, min_log_probability_per_letter, with_confidence):
+        """Every phrase searched in every one of the len(frames) utterances: over the engine's last forward pass (logq None), or
+        over a given logq tensor.  One sl_ctc_spot launch with a query per utterance and phrase, and -- with_confidence -- ONE
+        sl_ctc_segment_scores launch over every hit's frames, whose label rows are the concatenated phrases."""
+        from .alignment import PhraseHit
+        batch, count = len(frames), len(phrases)
+        lengths = np.array([len(p) for p in phrases], dtype=np.int32)
+        per_letter = min_log_probability_per_letter
+        thresholds = np.full((count,), -np.inf, dtype=np.float32) if per_letter is None else \
+            (np.float32(per_letter) * lengths).astype(np.float32)
+        queries = np.tile(encoded, (batch, 1))
+        utterances = np.repeat(np.arange(batch, dtype=np.int32), count)
+        if logq is None:
+            hits, scores, counts = engine.ctc_spot(queries, np.tile(lengths, batch), utterances, np.tile(thresholds, batch),
+                                                   max_hits, frames)
+        else:
+            hits, scores, counts = engine.ctc_spot_long(logq, queries, np.tile(lengths, batch), utterances,
+                                                        np.tile(thresholds, batch), max_hits, frames)
+        posteriors = np.full(scores.shape, np.nan, dtype=np.float32)
+        if with_confidence and counts.sum() > 0:
+            starts = np.concatenate([[0], np.cumsum(lengths)])
+            where = [(q, h) for q in range(batch * count) for h in range(counts[q])]
+            segments = np.array([(q // count, hits[q, h, 0], hits[q, h, 1], starts[q % count], starts[q % count + 1])
+                                 for q, h in where], dtype=np.int64)
+            row = np.concatenate([encoded[p, :lengths[p]] for p in range(count)])
+            label_batch = np.tile(row, (batch, 1))
+            if logq is None:
+                scored = engine.ctc_segment_scores(label_batch, segments)
+            else:
+                scored = engine.ctc_segment_scores_long(logq, label_batch, frames, segments)
+            for (q, h), score in zip(where, scored):
+                posteriors[q, h] = score
+        return [[[PhraseHit(phrases[p], hits[q, h, 0], hits[q, h, 1], scores[q, h], posteriors[q, h]) for h in range(counts[q])]
+                 for p, q in ((p, b * count + p) for p in range(count))] for b in range(batch)]
+
+    def find_phrases_batch(self, labeled_spectrogram_batch, phrases, max_hits=8, min_log_probability_per_letter=None,
+                           with_confidence=True):
+        """Extension (no reference counterpart): where each of `phrases` (strings over the net's alphabet, 1 .. 511 letters) is
+        said in each example, whatever the examples' own labels say.  One forward pass on the evaluation engine and one sl_ctc_spot
+        launch over the distribution the CTC loss sees: per example and phrase up to max_hits (1 .. 64) occurrences that do not
+        overlap, best first, each the best path of the phrase's letters over a stretch of frames that starts and ends on a
+        letter.  min_log_probability_per_letter: occurrences whose best path scores below it times the phrase's length are
+        dropped; None keeps every finite score -- then the later hits of a phrase that is said once are its best garbled
+        readings elsewhere, and the confidence tells them apart.  with_confidence: ONE sl_ctc_segment_scores launch scores every
+        hit's frames -- the probability that those frames, read on their own, say exactly the phrase -- into the hit's
+        log_posterior; otherwise that is nan.  Returns, per example, a list with one list of alignment.PhraseHit per phrase
+        (frames = output frames)."""
+        phrases, encoded = self._encoded_phrases(phrases, "find_phrases_batch")
+        spectrograms = [x.z_normalized_transposed_spectrogram() for x in labeled_spectrogram_batch]
+        input_batch, prediction_lengths = self._input_batch_and_prediction_lengths(spectrograms)
+        engine = self.eval_engine
+        engine.forward(input_batch)
+        return self._find_phrases(engine, None, prediction_lengths, phrases, encoded, max_hits, min_log_probability_per_letter,
+                                  with_confidence)
+
+    def find_phrases_in_recording(self, example, phrases, max_hits=8, min_log_probability_per_letter=None, with_confidence=True,
+                                  window_input_frames=None):
+        """find_phrases_batch for ONE recording of any length (a (T, F) spectrogram or an example): Engine.forward_long over
+        windows, then one sl_ctc_spot launch (and one sl_ctc_segment_scores launch) over the stitched logq.  Gives
+        align_recording its anchors where the transcript of a recording is partial or wrong.  Returns one list of
+        alignment.PhraseHit per phrase."""
+        phrases, encoded = self._encoded_phrases(phrases, "find_phrases_in_recording")
+        spectrogram = self._recording_spectrogram(example, "find_phrases_in_recording")
+        engine = self.eval_engine
+        _, logq = engine.forward_long(spectrogram, window_input_frames)
+        frames = spectrogram.shape[0] // self.input_to_prediction_length_ratio
+        return self._find_phrases(engine, logq, [frames], phrases, encoded, max_hits, min_log_probability_per_letter,
+                                  with_confidence)[0]
+
     def positional_label_of_recording(self, example, seconds_per_input_step=None, window_input_frames=None):
         """positional_label_batch for ONE recording of any length (align_recording): its word timings in seconds, None where
         the label cannot be aligned or has no words."""
