@@ -1,8 +1,8 @@
 """Topology and per-layer plans of the Wav2Letter stack (reference net.py:291-341): layer specs, TF 'SAME' padding, padded
 channel counts and the layer's place in the flat parameter buffers.  Shared by the engine and its buffer sets."""
+from ._lib import SL_TIME_TILE as TIME_TILE  # the conv kernels read whole time tiles of up to 256 rows
 
 HALO = 16
-TIME_TILE = 256  # SL_TIME_TILE: the conv kernels read whole time tiles of up to 256 rows
 
 
 def _round_up(x, m):

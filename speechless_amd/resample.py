@@ -19,9 +19,9 @@ PRECISION = 512                      # samples of the window per zero crossing
 ZERO_CROSSINGS = 64
 ROLLOFF = 0.9475937167399596
 KAISER_BETA = 14.769656459379492
-TILE = 2048                          # SL_RESAMPLE_TILE: consecutive outputs of one utterance per work-group
-MAX_PHASES = 1024                    # SL_RESAMPLE_MAX_PHASES
-MAX_TAPS = 4096                      # SL_RESAMPLE_MAX_TAPS
+TILE = _lib.SL_RESAMPLE_TILE         # consecutive outputs of one utterance per work-group
+MAX_PHASES = _lib.SL_RESAMPLE_MAX_PHASES
+MAX_TAPS = _lib.SL_RESAMPLE_MAX_TAPS
 
 
 def kaiser_best_window():

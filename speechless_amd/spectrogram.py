@@ -27,9 +27,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import SL_TIME_TILE as TIME_TILE
 from ._lib import ConvGeom, lib
-
-TIME_TILE = 256
 
 
 class SpectrogramFrequencyScale(Enum):
