@@ -26,10 +26,10 @@ from .engine_launch import LaunchMixin, forward_epilogue, mask_epilogue
 from .engine_split import SplitTopMixin
 from .engine_x3 import X3Mixin
 from ._hipevents import TimingEvent
-from .plan import HALO, TIME_TILE, LayerPlan, LayerSpec, _round_up, same_padding, wav2letter_layer_specs  # noqa: F401
+from .plan import HALO, TIME_TILE, LayerPlan, LayerSpec, StackPlan, _round_up, same_padding, wav2letter_layer_specs  # noqa: F401
 
 
-class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
+class Engine(StackPlan, LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMixin):
     """Forward / CTC / backward / Adam on one MI355X.  dtype 'bf16' (bf16 storage, fp32 accumulate, fp32 CTC: the
     benchmarked path), 'f32' (parity path: fp32 storage, exact-fp32 MFMA) or 'bf16x3' (the fast parity path: every value as
     hi + lo bf16 planes, three bf16 MFMA terms per product, fp32 accumulate; csrc/split3.hip) or 'f16x3' (the same scheme on
@@ -52,51 +52,30 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
                                        "there is no CPU fallback for the hot path")
         self.lib = lib()
         self.device = torch.device(device)
-        self.dtype = dtype
-        self.planes = 1
+        # the layout of the stack and the knobs its launch and bucket plans read (plan.py); complains about dtype and specs
+        StackPlan.__init__(self, specs, grapheme_set_size, dtype, frozen_layer_count)
         if dtype == "bf16":
             self.torch_dtype, self.dtype_code = torch.bfloat16, _lib.SL_BF16
         elif dtype == "f32":
             self.torch_dtype, self.dtype_code = torch.float32, _lib.SL_F32
         elif dtype == "bf16x3":
-            self.torch_dtype, self.dtype_code, self.planes = torch.bfloat16, _lib.SL_BF16, 3
-        elif dtype == "f16x3":
-            # the plane scheme on fp16 pairs (round 6; engine_x3.py): 22 operand bits instead of 16-17 at the same three MFMA
+            self.torch_dtype, self.dtype_code = torch.bfloat16, _lib.SL_BF16
+        else:
+            # f16x3: the plane scheme on fp16 pairs (round 6; engine_x3.py): 22 operand bits instead of 16-17 at the same three MFMA
             # terms.  fp16's range is 65504 and its precision below 2^-3 absolute, so weights and back-propagated gradients
             # are STORED multiplied by powers of two (exact) that bring typical magnitudes to ~1; the kernels divide them
             # out again (sl_conv_geom.acc_scale, the `scale` arguments of the sl_splitf16* helpers).
-            self.torch_dtype, self.dtype_code, self.planes = torch.float16, _lib.SL_F16, 3
-        else:
-            raise ValueError("dtype must be 'bf16', 'f32', 'bf16x3' or 'f16x3'")
+            self.torch_dtype, self.dtype_code = torch.float16, _lib.SL_F16
         self.x3_f16 = dtype == "f16x3"
         # f16x3: operand copies hold w_scale * w (glorot-uniform weights of this stack are 0.01 ... 0.05: x 64 -> ~1; representable
         # up to |w| < 1000), gradient planes hold g_scale * g (the CTC gradient of a frame is <= 1 / B: x 4096 stays below 2^12)
         self.w_scale = 64.0 if self.x3_f16 else 1.0
         self.g_scale = 4096.0 if self.x3_f16 else 1.0
-        # Raw-wave input (reference net.py:310-312: `wave_conv`, 250 taps at stride 160 over the samples, in front of
-        # striding_conv): the FRONT layer.  It is a GEMM over gathered sample windows (sl_wave_frames: K = 250 * Cin
-        # columns per output frame, 3 GFLOP per 32 x 8 s -- nothing next to the stack) whose output lands directly in the
-        # pair-view input buffer of the stack below; the eleven layers behind it, their plans, indices and launches are
-        # untouched.  Internally the front plan has index len(plans) (its parameters sit at the END of the flat buffers);
-        # the public order of set_weights / get_weights / get_gradients puts it first, as the reference's layer list does.
-        self.front_spec = None
-        self.front_frozen = False
-        if specs and specs[0].stride > 2:
-            self.front_spec = specs[0]
-            specs = list(specs[1:])
-            self.front_frozen = frozen_layer_count >= 1
-            frozen_layer_count = max(frozen_layer_count - 1, 0)
-            if self.front_spec.activation not in ("relu", "elu"):
-                raise NotImplementedError("the raw-wave layer takes a relu / elu activation")
         # f16x3 under a raw-wave front layer: the gathered sample windows hold x_scale * x (audio sits in [-1, 1] with quiet
         # passages orders of magnitude below; fp16 planes carry 22 bits only where |v| >= 2^-3: x 2^10 lifts samples down to
         # 2^-13 into that range and keeps full-scale audio a factor of 64 below 65504).  1 on every other path.
         self._x_scale = 1024.0 if (self.x3_f16 and self.front_spec is not None) else 1.0
-        self.specs = specs
-        self.all_specs = ([self.front_spec] if self.front_spec is not None else []) + list(specs)
-        self.grapheme_set_size = grapheme_set_size
         self.ctc_epsilon = ctc_epsilon
-        self.frozen_layer_count = frozen_layer_count
         self.lr, self.beta_1, self.beta_2, self.adam_epsilon = lr, beta_1, beta_2, adam_epsilon
         self.adam_iterations = 0
         # The update rule (Keras 2.0.x optimizers.py; include/speechless_hip.h "Keras-2.0 optimizers beside Adam"): "adam" (the
@@ -125,56 +104,8 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
         self.track_grad_norm = bool(track_grad_norm)
         self._norm_sq = self._norm_out = self._norm_ws = None  # device double; device floats (n, scale); partial sums
         self._norm_tables = {}
-        for i, s in enumerate(specs):
-            if s.stride not in (1, 2) or (s.stride == 2 and i != 0):
-                raise NotImplementedError("only the first layer may stride (spectrogram-input stack, net.py:317)")
-            hidden_ok = s.activation in ("relu", "elu") if i < len(specs) - 1 else s.activation == "softmax"
-            if not hidden_ok:
-                raise NotImplementedError(
-                    "HIP path supports relu/elu hidden layers and a softmax output layer (got {!r} on {})".format(
-                        s.activation, s.name))
-        if specs[-1].cout != grapheme_set_size:
-            raise ValueError("output layer width must equal the grapheme set size")
-        self.plans = []
-        off = 0
-        # pair view of the striding layer = 2*cin_pad channels; the wgrad tile needs that to be a multiple of 128
-        # (a first layer that does not stride reads plain rows: its own padded width must be that multiple -- ADVICE r5)
-        cin_pad = _round_up(specs[0].cin, 64 if specs[0].stride == 2 else 128)
-        for i, s in enumerate(specs):
-            cout_pad = _round_up(s.cout, 128)
-            w_off = off
-            off += s.kernel_size * cin_pad * cout_pad
-            b_off = off
-            off += cout_pad
-            self.plans.append(LayerPlan(i, s, cin_pad, cout_pad, w_off, b_off))
-            cin_pad = cout_pad
-        self.front_plan = None
-        if self.front_spec is not None:
-            fs = self.front_spec
-            p0 = self.plans[0]
-            if fs.cout != specs[0].cin or p0.cin_pad % 128:
-                raise NotImplementedError("the raw-wave layer's filters must be the next layer's inputs, padded to a multiple "
-                                          "of 128 (250 -> 256)")
-            k_real = fs.kernel_size * fs.cin
-            gemm = LayerSpec(fs.name, 1, 1, k_real, fs.cout, fs.activation)  # the layer as the 1 x 1 GEMM it is launched as
-            self.front_plan = LayerPlan(len(self.plans), gemm, _round_up(k_real, 128), p0.cin_pad, off, off + _round_up(k_real, 128) * p0.cin_pad)
-            off = self.front_plan.b_off + p0.cin_pad
-        self.all_plans = self.plans + ([self.front_plan] if self.front_plan is not None else [])
-        self.param_numel = off
-        # runs of >= 2 consecutive stride-1 layers with identical padded geometry (net.py:321-323: inner_conv_1..7)
-        self.runs = []
-        i = 1
-        while i < len(self.plans):
-            j = i
-            key = lambda q: (q.spec.kernel_size, q.spec.stride, q.cin_pad, q.cout_pad)  # noqa: E731
-            while j + 1 < len(self.plans) and key(self.plans[j + 1]) == key(self.plans[i]) and \
-                    self.plans[i].cin_pad == self.plans[i].cout_pad:
-                j += 1
-            if j > i:
-                self.runs.append((i, j))
-            i = j + 1
-        self.group_wgrad = True
         dev = self.device
+        off = self.param_numel
         self.params = torch.zeros((off,), dtype=torch.float32, device=dev)
         # forward_only: an evaluation engine (forward, CTC loss, decode) over masters another engine trains -- no gradient
         # buffer, no moments (Wav2Letter.eval_engine aliases `params` to the training engine's)
@@ -224,30 +155,16 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
         self.timeline = None
         self.kernel_timeline = None  # (set of tags, list of (tag, start, stop)): see _around
         self._side_stream = None
-        # "ones channel": the last padded output channel of every hidden layer carries the constant 1 (bias 1, zero weights),
-        # so the next layer's weight-gradient GEMM -- which multiplies the padding through anyway -- leaves that layer's
-        # BIAS gradient in row cin_pad - 1 of dW (sl_bias_grad_from_wgrad, include/speechless_hip.h): ten of the eleven
-        # sl_bias_grad passes over g (two launches each, on the side stream, 0.07 ms of the config-3 step by taking
-        # bandwidth and power from the GEMMs beside them) become one small launch.  SL_ONES_CHANNEL=0: the old passes.
-        self.ones_channel = os.environ.get("SL_ONES_CHANNEL", "1") == "1"
         self._bgw_tables = {}
         self.fuse_output_softmax = os.environ.get("SL_FUSE_OUTPUT", "1") != "0"  # A/B knob: sl_output_softmax
         # both gradients of the 1x1 output layer in one launch that reads the layer's input once (sl_conv1d_backward_1x1):
         # 0.038 ms against 0.040 + 0.032 ms of dgrad + wgrad launches at config 3.  SL_FUSE_OUTPUT_BWD=0: the two launches.
         self.fuse_output_backward = os.environ.get("SL_FUSE_OUTPUT_BWD", "1") != "0"
-        # the weight gradients of the layers with few 256 x 256 tiles (the run of inner layers, striding_conv) in ONE launch
-        # whose (tile, 64-frame step) space is cut into one equal range per CU (sl_conv1d_wgrad_multi) instead of a grouped
-        # launch + a 128 x 128-tile launch with utterance-granular batch splits.  SL_WGRAD_MULTI=0: those launches.
-        self.use_wgrad_multi = os.environ.get("SL_WGRAD_MULTI", "1") != "0"
-        # ... also for a layer whose input channels are not a multiple of the 256-wide tile (257 bins: the 640-wide pair view
-        # of striding_conv): its last tile starts at cin - 256 and overlaps the one before (A/B knob)
-        self.multi_overlap_tiles = True
         self.small_bias_pass_on_main = os.environ.get("SL_BIAS_MAIN", "1") != "0"  # A/B knob
         self.x3_fused_epilogue = os.environ.get("SL_X3_FUSED_EPILOGUE", "1") != "0"  # bf16x3: activation + plane split in the NT epilogue
         # bf16x3, striding layer: the g_lo partial of its weight gradient against the [hi0 | hi1] window of the pair rows
         # instead of the whole row (buffers.py; A/B knob, read when a buffer set's backward geometries are built)
         self.x3_b_window = os.environ.get("SL_X3_B_WINDOW", "1") != "0"
-        self.nt_cfg = {}  # optional per-launch tile configuration overrides {("fwd"|"dgrad", layer name): cfg word}
         # Launch lists (launch_list.py): the ~60 C-ABI calls and 4 stream hand-overs of a step are recorded the first time a
         # buffer set runs them and replayed afterwards with their arguments already marshalled -- the Python around each launch
         # (tensor views of the flat parameter buffers, data_ptr() calls, geometry look-ups: ~10 us per launch) was what
@@ -258,8 +175,8 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
         # HISTORY.md section 3.1).  SL_CHAIN=0 restores the single launches (A/B measurements).
         self.use_chain = os.environ.get("SL_CHAIN", "1") == "1"
         self.use_launch_lists = os.environ.get("SL_LAUNCH_LISTS", "1") != "0"
-        if self.planes > 1:  # the fused launches read and write single-plane bf16 tensors
-            self.use_chain = self.fuse_output_softmax = self.fuse_output_backward = self.group_wgrad = False
+        if self.planes > 1:  # the fused launches read and write single-plane bf16 tensors (group_wgrad: plan.py)
+            self.use_chain = self.fuse_output_softmax = self.fuse_output_backward = False
             self._x3_bias_ws = None
         # Split top: the CTC lattice is a handful of latency-bound waves (one per utterance and direction, T' sequential
         # frames: 0.106 ms at config 3, 0.39 ms at config 5) with the rest of the chip idle, and it sits between forward and
@@ -277,13 +194,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
         # the library's choosers to plan for 256 - comm_cus (sl_set_available_cus) while an exchange can be in flight -- only
         # then: forward runs with the whole chip.  0 = no hint.  Set by train_step_resident from the reducer (comm_cus).
         self.comm_cus = 0
-        # Data-parallel runs, A/B knob for the first N > 1 run (SL_SPLIT_LAST_BUCKET=1): the one exchange
-        # nothing covers is the last bucket {striding_conv, inner_conv_1..7} (19 MB), closed by the last kernel of backward.
-        # With the flag the run of identical layers is cut at `split_last_at`: its fused input-gradient launch and the balanced
-        # weight-gradient launch become two each (+2 launches per step), and the upper part's gradients (inner_conv_4..7,
-        # 7 MB) close as a bucket of their own under the lower part's launches.  Off by default: on one GPU it only costs.
-        self.split_last_bucket = os.environ.get("SL_SPLIT_LAST_BUCKET", "0") == "1"
-        self.split_last_at = 4
         self._cu_hint_active = 0  # what sl_set_available_cus was last told by this engine's backward (restored after sizing calls)
         self._ctc_streams = None
         self._rec = None
@@ -447,61 +357,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
         b = tensor[plan.b_off: plan.b_off + plan.cout_pad]
         return w, b
 
-    def bucket_plan(self):
-        """Gradient buckets of the data-parallel exchange in the order backward() completes them: a list of
-        (layer indices, (lo, hi)) with [lo, hi) the bucket's contiguous range of the flat gradient buffer.
-        {output_conv, big_conv_2} (17 % of the bytes, complete after the second weight gradient of the step), {big_conv_1}
-        (64 %, its exchange runs under big_conv_1's input gradient and the whole inner run), the run of identical inner layers
-        (one grouped weight-gradient launch at the very end of backward), then what is left (striding_conv, whose weight
-        gradient is the last kernel of backward: the only exchange nothing covers) -- one bucket with the run when
-        sl_conv1d_wgrad_multi writes both (_wgrad_multi_layers).  Frozen layers are in no bucket."""
-        n = len(self.plans)
-        first = self.frozen_layer_count
-        groups = []
-        if n >= 3:
-            groups.append(list(range(max(n - 2, first), n)))
-            groups.append(list(range(max(n - 3, first), n - 2)))
-        else:
-            groups.append(list(range(first, n)))
-        rest_hi = max(n - 3, first) if n >= 3 else first
-        for (s0, e0) in reversed(self.runs):  # runs inside the remaining layers become buckets of their own
-            lo = max(s0, first)
-            if e0 < rest_hi and e0 >= lo:
-                if e0 + 1 < rest_hi:
-                    groups.append(list(range(e0 + 1, rest_hi)))
-                groups.append(list(range(lo, e0 + 1)))
-                rest_hi = lo
-        if rest_hi > first:
-            groups.append(list(range(first, rest_hi)))
-        # one launch writes the weight gradients of the striding layer and of the run above it: one bucket
-        multi = self._wgrad_multi_layers(first)
-        if multi and multi[0] == 0:
-            # every bucket that holds a layer of the launch becomes part of ONE bucket closed at the launch (its lowest
-            # layer) -- whole buckets, so that with several runs a layer between them is neither left out of the merged
-            # range nor reduced twice; the merged layers are then contiguous from layer 0 up
-            span = set(range(multi[0], multi[-1] + 1))
-            merged = sorted(set(l for g in groups if set(g) & span for l in g))
-            groups = [g for g in groups if not set(g) & span]
-            assert merged == list(range(merged[0], merged[-1] + 1)), merged
-            parts = self._wgrad_multi_groups(first)
-            if len(parts) == 2 and sorted(parts[0] + parts[1]) == merged:
-                groups += parts  # split_last_bucket: the upper part of the run closes first, as a bucket of its own
-            else:
-                groups.append(merged)
-        plan = []
-        for layers in groups:
-            if layers:
-                hi_layer = self.plans[layers[-1]]
-                plan.append((layers, (self.plans[layers[0]].w_off, hi_layer.b_off + hi_layer.cout_pad)))
-        if self.front_plan is not None and not self.front_frozen and first == 0:
-            fp = self.front_plan  # (raw-wave front layer: its gradients are the last launches of backward)
-            plan.append(([fp.index], (fp.w_off, fp.b_off + fp.cout_pad)))
-        return plan
-
-    def bucket_ranges(self):
-        """Flat-gradient ranges of bucket_plan(), in completion order (what GradBucketReducer takes)."""
-        return [r for _, r in self.bucket_plan()]
-
     # ------------------------------------------------------------------ weights
 
     def _write_padded(self, flat, arrays, what):
@@ -526,23 +381,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
                 self.layer_param_views(self.params, p)[1][p.cout_pad - 1] = 1.0
         self._packed_dirty = True
         self._weights_set_count += 1
-
-    def _has_ones_output(self, plan):
-        """hidden layer whose output has channel padding: its last padded channel is the constant 1"""
-        hidden = plan is self.front_plan or plan.index < len(self.plans) - 1
-        return self.ones_channel and hidden and plan.cout_pad > plan.spec.cout
-
-    def _has_ones_input(self):
-        """the packed INPUT carries a ones channel (sl_pack_input_ones) where its bins leave a padding channel free: 257 bins in
-        rows of 320 (configuration 5) -- not 128 mel bins, which fill their rows.  Single-plane paths only."""
-        if self.front_plan is not None:  # the front layer's last padded filter is the constant 1 (its bias; _has_ones_output)
-            return self._has_ones_output(self.front_plan)
-        return self.ones_channel and self.planes == 1 and self.plans[0].cin_pad > self.specs[0].cin
-
-    def _ones_input_layers(self, first):
-        """trainable layers whose input carries a ones channel: their bias gradient is row cin_pad - 1 of dW"""
-        lower = [0] if (first == 0 and self._has_ones_input()) else []
-        return lower + [i for i in range(max(first, 1), len(self.plans)) if self._has_ones_output(self.plans[i - 1])]
 
     def _bias_grads_from_wgrad(self, layers, copy, stream):
         """One sl_bias_grad_from_wgrad launch for `layers` (their weight gradients are complete on `stream`)."""
@@ -691,10 +529,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
             return False
         return bool(self.lib.raw("sl_conv1d_chain_supported")(ctypes.byref(buf.fwd_geom[layers[0]]), len(layers),
                                                               self.dtype_code))
-
-    def _dropout_layers(self):
-        """Indices of the layers with a Dropout in front of them (all but the last three, net.py:326-330)."""
-        return range(0, max(len(self.plans) - 3, 0))
 
     def forward(self, input_batch=None, training=False, split_ctc=None):
         """Runs the 11 conv layers + softmax.  Returns the probability tensor (B,T',K) fp32 in HBM.
@@ -1008,17 +842,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
                 self.lib.raw("sl_set_available_cus")(0)
             raise
 
-    def _grouped_wgrad_runs(self, first):
-        """layer index -> (lo, hi) of the run whose weight gradients are one grouped launch (bf16 path)"""
-        grouped = {}
-        if self.group_wgrad and self.dtype == "bf16":
-            for (s0, e0) in self.runs:
-                lo = max(s0, first)
-                if e0 > lo:
-                    for q in range(lo, e0 + 1):
-                        grouped[q] = (lo, e0)
-        return grouped
-
     def _dgrad_chains(self, buf, first):
         """input gradients of a run of identical ReLU layers in one launch (sl_conv1d_chain): {top layer: layers, top
         first}, and the set of layers such a launch covers besides its top layer"""
@@ -1046,28 +869,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
                         dchain[q[0]] = q
                         skip.update(q[1:])
         return dchain, skip
-
-    def _split_last_cut(self, first):
-        """split_last_bucket: the layer at which the balanced weight-gradient launch (and the fused input-gradient launch of
-        the run it covers) is cut in two, or None"""
-        if not self.split_last_bucket or self.planes > 1:
-            return None
-        multi = self._wgrad_multi_layers(first)
-        cut = self.split_last_at
-        if not multi or multi[0] != 0 or not (multi[0] < cut <= multi[-1]) or cut <= first:
-            return None
-        return cut
-
-    def _wgrad_multi_groups(self, first, grouped=None):
-        """the balanced weight-gradient launches of backward, in the order they are enqueued: one for all of
-        _wgrad_multi_layers, or -- split_last_bucket -- the layers from the cut up first, then the rest"""
-        multi = self._wgrad_multi_layers(first, grouped)
-        if not multi:
-            return []
-        cut = self._split_last_cut(first)
-        if cut is None:
-            return [multi]
-        return [[i for i in multi if i >= cut], [i for i in multi if i < cut]]
 
     def _launch_wgrad(self, buf, i, grouped, st):
         """weight gradient of layer i -- or, at the lowest layer of a grouped run, of the whole run"""
@@ -1117,28 +918,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
         self._dgrad_through(buf, name, buf.g[i], self.w_dgrad[i], buf.y[i - 1], buf.g[i - 1], buf.dgrad_geom[i],
                             self.specs[i - 1].activation, buf.dropped and i in self._dropout_layers(), buf.dropout_seed0 + i,
                             self.nt_cfg.get(("dgrad", name), 0), st)
-
-    def _wgrad_multi_layers(self, first, grouped=None):
-        """layers whose weight gradients go into ONE sl_conv1d_wgrad_multi launch (at the lowest of them): the runs of
-        identical layers and the striding layer below them.  The same with and without a data-parallel exchange (the step
-        is then bit-identical either way); bucket_plan() closes the striding layer's bucket together with the run's."""
-        if self.planes > 1:
-            return self._wgrad_multi_layers_x3(first)
-        if grouped is None:
-            grouped = self._grouped_wgrad_runs(first)
-        if not self.use_wgrad_multi or self.dtype != "bf16" or not grouped:
-            return []
-
-        def fits(i):  # (input channels: whole 256-wide tiles, or -- round 4 -- a last tile overlapping its neighbour)
-            cin = self.plans[i].cin_view
-            return cin >= 256 and cin % (64 if self.multi_overlap_tiles else 256) == 0 and \
-                self.plans[i].cout_pad % 256 == 0 and ("wgrad", self.specs[i].name) not in self.nt_cfg
-        layers = sorted(grouped)
-        if not all(fits(i) for i in layers) or len(layers) > 15:
-            return []
-        if first == 0 and self.plans[0].spec.stride == 2 and layers[0] == 1 and fits(0):
-            layers = [0] + layers
-        return layers
 
     def _wgrad_multi_workspace_need(self, table, n_jobs):
         """workspace of a balanced weight-gradient launch: its segment count is 2 * CUs / tiles (_max_over_cu_hints)"""
@@ -1333,21 +1112,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
         self._norm_buffers(self._trainable_ranges())
         return self._norm_out[0]
 
-    def _trainable_ranges(self):
-        """[lo, hi) ranges of the flat gradient buffer that hold the trainable layers (frozen layers contribute nothing).
-        Whole padded blocks: every padding element of the gradient buffer is zero once backward has run (padded channels
-        carry zeros through every GEMM; the ones-channel rows are zeroed by sl_bias_grad_from_wgrad) --
-        tests/test_gpu_optimizer_clip.py holds the norm over these ranges to the norm of the logical elements."""
-        out = []
-        for i in self._trainable_layers():
-            p = self.all_plans[i]
-            lo, hi = p.w_off, p.b_off + p.cout_pad
-            if out and out[-1][1] == lo:
-                out[-1] = (out[-1][0], hi)
-            else:
-                out.append((lo, hi))
-        return out
-
     def _norm_table(self, ranges):
         key = tuple(ranges)
         table = self._norm_tables.get(key)
@@ -1386,13 +1150,6 @@ class Engine(LaunchMixin, X3Mixin, SplitTopMixin, FrontLayerMixin, DecodeAlignMi
     def _launch_clip_scale(self, st):
         self._launch("clip_scale", "sl_clip_scale", self._norm_sq.data_ptr(), 1, self.clipnorm, self._norm_out[1:].data_ptr(),
                      self._norm_out.data_ptr(), st)
-
-    def _trainable_layers(self):
-        """internal indices of the layers the optimizer updates (the front layer, if any, has index len(plans))"""
-        layers = list(range(self.frozen_layer_count, len(self.plans)))
-        if self.front_plan is not None and not self.front_frozen:
-            layers.append(self.front_plan.index)
-        return layers
 
     def _adam_table(self, chunk):
         table = self._adam_tables.get(tuple(chunk))

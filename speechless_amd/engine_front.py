@@ -12,10 +12,6 @@ from .plan import same_padding
 
 
 class FrontLayerMixin:
-    def _public_plans(self):
-        """the plans in the public layer order (the reference's layer list): the front layer first"""
-        return ([self.front_plan] if self.front_plan is not None else []) + self.plans
-
     def _front_to_gemm(self, plan, w):
         """the front layer's Keras kernel (k, Cin, Cout) as the (1, k * Cin, Cout) matrix it is stored and launched as"""
         if plan is self.front_plan and np.ndim(w) == 3 and w.shape[0] == self.front_spec.kernel_size:

@@ -132,32 +132,6 @@ class X3Mixin:
                                        buf.tt_pad * p.cin_pad, HALO, buf.rows * p.cin_pad * pl, st)
         self._backward_tail(buf, on_bucket_ready, ones_in, ones_db, main)
 
-    def _wgrad_multi_layers_x3(self, first):
-        """bf16x3: no launch writes the weight gradients of the striding layer AND of a run (bucket_plan() merges nothing)"""
-        return []
-
-    def _x3_multi_runs(self, first):
-        """bf16x3: the runs of identical layers whose 2 partial weight gradients per layer are jobs of ONE
-        sl_conv1d_wgrad_multi launch at the lowest layer of the run (16 jobs at most): x operands of whole 256-wide tiles
-        against 256-wide output tiles.  Shapes only (the same for every buffer set)."""
-        out = []
-        if not self.use_wgrad_multi:
-            return out
-        for (s0, e0) in self.runs:
-            lo = max(s0, first)
-            layers = list(range(lo, e0 + 1))
-
-            def fits_run(i):
-                p = self.plans[i]  # A: the [hi | lo] prefix (2 cin_pad) against g_hi, B: x_hi (cin_pad) against g_lo
-                return p.cin_pad % 256 == 0 and p.cout_pad % 256 == 0 and p.spec.stride == 1 and \
-                    ("wgrad", self.specs[i].name) not in self.nt_cfg
-            if len(layers) >= 2 and 2 * len(layers) <= 16 and all(fits_run(i) for i in layers):
-                # (round 5: striding_conv's two partials as jobs of the same launch -- 144 more tiles over the 768-wide pair
-                # rows -- were measured SLOWER: 6.328 against 6.215 ms per config-3 step in a same-box A/B,
-                # profiles/r05_x3_multi_striding_ab.txt; they stay two 128 x 128-tile launches)
-                out.append(layers)
-        return out
-
     def _launch_wgrad_multi_x3(self, buf, layers, st):
         """bf16x3: the partial weight gradients RA (x planes [hi | lo] against g_hi) and RB (x plane hi against g_lo) of
         every layer of a run as jobs of one sl_conv1d_wgrad_multi launch, then sl_split3_wgrad_combine per layer"""

@@ -642,7 +642,7 @@ class Wav2Letter:
             ev = Engine(list(train.all_specs), self.grapheme_encoding.grapheme_set_size, dtype=self.eval_dtype,
                         device=self.device, ctc_epsilon=self.ctc_epsilon, frozen_layer_count=self.frozen_layer_count,
                         forward_only=True, criterion=self.criterion)
-            ev.params = train.params  # the masters themselves: same plan, same offsets (Engine.__init__ does not depend on dtype)
+            ev.params = train.params  # the masters themselves: same plan, same offsets
             ev.asg_params = train.asg_params  # (None under CTC; the ASG tables are read in place, never packed)
             assert ev.param_numel == train.param_numel
             self._eval_engine = ev
